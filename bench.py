@@ -88,7 +88,14 @@ def main():
     ap.add_argument("--rehearse-spawn", action="store_true",
                     help="no GPU work: rendezvous, the record gather and the max-over-ranks timing only (CPU test of the "
                          "--gpus N launch path; use with APSE_DIST_BACKEND=gloo)")
+    ap.add_argument("--dump-outputs", type=str, default=None, metavar="DIR",
+                    help="after the timed steps, write what the timed path returned in its LAST step as DIR/<name>.npy "
+                         "(float32 / float64; rank 0): per frame b of the batch the record's arrays frame<b>_<key> and, with one "
+                         "rank, the track ids the association gave that frame (frame<b>_track_ids).  Inputs and weights are "
+                         "seeded, so the same arguments give the same inputs in every run and two builds compare file by file")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        sys.exit("bench.py: --steps must be >= 1 and --warmup >= 0")
 
     # ---- N ranks: one process per GPU.  Under a launcher (torchrun: WORLD_SIZE set) this process IS a rank; without one
     # `--gpus N` starts the N ranks itself -- before anything touches the GPU -- and only relays rank 0's JSON line.
@@ -167,6 +174,7 @@ def main():
 
     lib = _lib.load()
     records = []
+    last = {}               # the last timed step: its results block and, with one rank, the track ids of each frame (--dump-outputs)
     from apse_uav_amd.engines.replay import NativeReplay
     replay = NativeReplay(host_id=1)        # same association rules as RcnnTracker.next_record (tests/test_replay.py)
 
@@ -219,12 +227,15 @@ def main():
         k = i % depth
         with torch.cuda.stream(streams[k]):
             res = models[k].read(B)                   # D2H of the results block + sync of that stream
+        ids = []
         for b in range(B):
             rec = res.record(b)
             if world == 1:
-                replay.step(rec, i * B + b)
+                ids.append(replay.step(rec, i * B + b)[1])
             elif timed:
                 records.append(rec)
+        if timed:
+            last.update(res=res, ids=ids)
         return res
 
     def step(i, timed):
@@ -276,12 +287,14 @@ def main():
             return frames[idx[0]:idx[0] + B] if idx == list(range(idx[0], idx[0] + B)) else frames[idx]
 
         def post(i, res):
+            ids = []
             for b in range(B):
                 rec = res.record(b)
                 if world == 1:
-                    replay.step(rec, i * B + b)
+                    ids.append(replay.step(rec, i * B + b)[1])
                 else:
                     records.append(rec)
+            last.update(res=res, ids=ids)
             account(res)
         first = args.warmup
         ts = time.perf_counter()
@@ -341,6 +354,8 @@ def main():
         tt = torch.tensor([elapsed], device=coll_dev, dtype=torch.float64)
         dist.all_reduce(tt, op=dist.ReduceOp.MAX)
         elapsed = float(tt.item())
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, last["res"], last["ids"] if world == 1 else None, B)
     # ---- separate instrumented pass (NOT part of `value`): HIP-event pairs around every convolution launch, on the stream the
     # kernels run on (recorded inside libapse_hip.so), for the roofline block
     if not args.no_events:
@@ -441,6 +456,31 @@ ACT_ELEMS_4K_R101 = 390.2e6
 WEIGHT_ELEMS_R101 = 63.0e6
 HBM_ACHIEVABLE_TBS = 6.29             # MI355X_MICROARCH.md: measured copy bandwidth (8.0 TB/s data sheet)
 SUSTAINED_16BIT_TFLOPS = 1810.0       # tools/micro/mfma_peak.hip on random operands (profiles/r01b_mfma_peak.txt)
+
+
+DUMP_KEYS = ("boxes", "scores", "classes", "centroids", "mass", "rects", "closest", "embeddings")
+DUMP_MAX_BYTES = 64 << 20
+
+
+def dump_outputs(path, res, ids, B):
+    """--dump-outputs: the records FrameResults.record(b) hands a caller for each frame of the timed path's last step
+    (packed_index, a position inside the results block, is left out), float32 arrays as they are and integer ones as float64
+    (exact), plus the association's track ids of the frame when ``ids`` is given.  At most 100 detections per frame keep
+    this far below DUMP_MAX_BYTES."""
+    arrays = {}
+    for b in range(B):
+        rec = res.record(b)
+        for k in DUMP_KEYS:
+            v = np.asarray(rec[k])
+            arrays["frame%d_%s" % (b, k)] = v if v.dtype == np.float32 else v.astype(np.float64)
+        if ids is not None:
+            arrays["frame%d_track_ids" % b] = np.asarray(ids[b], np.float64)
+    total = sum(v.nbytes for v in arrays.values())
+    if total > DUMP_MAX_BYTES:
+        sys.exit("bench.py: --dump-outputs would write %d bytes (limit %d)" % (total, DUMP_MAX_BYTES))
+    os.makedirs(path, exist_ok=True)
+    for name, v in arrays.items():
+        np.save(os.path.join(path, name + ".npy"), v)
 
 
 def extra_mode(lib, sd, asd, frames, nres, H, W, dev_index, steps, probe_steps, dtype, batch, preproc, warmup=3, in_flight=1):
