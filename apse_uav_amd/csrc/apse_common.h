@@ -10,6 +10,11 @@
 #define APSE_E_NOMEM (-3)
 #define APSE_E_STATE (-4)
 #define APSE_E_MISSING (-5)
+// frame size limits, as include/apse_hip.h documents them
+#define APSE_MAX_FRAME_W 49152
+#define APSE_MAX_FRAME_H 32768
+// LDS of one workgroup on gfx950 (160 KiB per CU)
+#define APSE_LDS_BYTES 163840
 
 typedef __attribute__((ext_vector_type(16))) float f32x16;
 typedef __attribute__((ext_vector_type(4))) float f32x4;

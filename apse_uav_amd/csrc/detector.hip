@@ -816,8 +816,11 @@ int apse_create(const apse_config* cfg, apse_ctx** out) {
     if (cfg->struct_size != (int)sizeof(apse_config)) return fail(nullptr, APSE_E_INVALID, "apse_config size mismatch");
     if (cfg->max_batch < 1 || cfg->max_batch > 64 || cfg->rpn_pre_topk > 1000 || cfg->rpn_post_topk > 1000 ||
         cfg->dets_per_image > 100 || cfg->num_classes < 1 || cfg->num_classes > 6 || cfg->embed_dim > 256 ||
-        (cfg->frame_w & 3) != 0 || cfg->max_batch * cfg->dets_per_image > 1024)
+        cfg->max_batch * cfg->dets_per_image > 1024)
         return fail(nullptr, APSE_E_INVALID, "config out of supported range");
+    if (cfg->frame_h < 1 || cfg->frame_w < 1 || cfg->frame_h > APSE_MAX_FRAME_H || cfg->frame_w > APSE_MAX_FRAME_W)
+        return fail(nullptr, APSE_E_INVALID, "frame size out of supported range (1 <= frame_h <= " + std::to_string(APSE_MAX_FRAME_H) +
+                                             ", 1 <= frame_w <= " + std::to_string(APSE_MAX_FRAME_W) + ")");
     if (cfg->compute_dtype < 0 || cfg->compute_dtype > 2 || (cfg->compute_dtype && !cfg->storage16))
         return fail(nullptr, APSE_E_INVALID, "compute_dtype 1 / 2 (bf16 / f16 matrix cores) needs storage16 = 1: the f32-storage variant "
                                              "of the 16-bit modes was removed in round 4 (no BASELINE configuration uses it)");

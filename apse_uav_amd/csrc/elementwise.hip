@@ -24,10 +24,23 @@ __device__ __forceinline__ int clip8(int v) {
 // FUSED: the row is not copied but COMPUTED while staging -- undistort gather + Lab gamma of the raw frame (preproc_pixel.h,
 // the reference's preprocess_img) -- so a pre-processed 4K frame is never written to / re-read from HBM (2 x 24.9 MB per frame
 // and one launch less than undistort_gamma -> pil_resize_h).  Same per-pixel function, same bytes as the two-kernel form.
+// Rows of a batch whose byte start or length is not a multiple of 4 (a width that is not, or an unaligned frame pointer) are staged by
+// the third branch below: they take PIL_ROW_SLACK bytes more LDS in front of the row, and the row then starts at
+// row + (source address & 15) instead of at `row`.  pil_stage_row returns where the consumers find the row.
+#define PIL_ROW_SLACK 15
+__host__ __device__ __forceinline__ bool pil_row_unaligned(const uint8_t* src, int W) {
+    return ((reinterpret_cast<uintptr_t>(src) | (uintptr_t)(W * 3)) & 3) != 0;
+}
+// bytes [0, n) of a 16-byte chunk kept, the rest zero
+__device__ __forceinline__ uint4 pil_keep_bytes(uint4 v, int n) {
+    const auto keep = [](uint32_t w, int k) { return k >= 4 ? w : (k <= 0 ? 0u : w & ((1u << (8 * k)) - 1u)); };
+    return uint4{keep(v.x, n), keep(v.y, n - 4), keep(v.z, n - 8), keep(v.w, n - 12)};
+}
+
 template <bool FUSED>
-__device__ __forceinline__ void pil_stage_row(uint8_t* row, const uint8_t* __restrict__ src, int y, int b, int W, size_t src_img_stride,
-                                              const UndistortParams& cam, const LabTables* __restrict__ lut,
-                                              const uint32_t* __restrict__ cam_map, unsigned src_bytes) {
+__device__ __forceinline__ uint8_t* pil_stage_row(uint8_t* row, const uint8_t* __restrict__ src, int y, int b, int W, size_t src_img_stride,
+                                                  const UndistortParams& cam, const LabTables* __restrict__ lut,
+                                                  const uint32_t* __restrict__ cam_map, unsigned src_bytes) {
     const uint8_t* srow = src + (size_t)b * src_img_stride + (size_t)y * W * 3;
     const int nbytes = W * 3;
     if constexpr (FUSED) {
@@ -88,8 +101,36 @@ __device__ __forceinline__ void pil_stage_row(uint8_t* row, const uint8_t* __res
                 row[x * 3 + 0] = (uint8_t)c0; row[x * 3 + 1] = (uint8_t)c1; row[x * 3 + 2] = (uint8_t)c2;
             }
         }
+    } else if (pil_row_unaligned(src, W)) {
+        // Any width.  The 16-byte chunks that cover the row are copied verbatim into LDS (16-byte loads and ds_write_b128, both
+        // naturally aligned) and the row is handed on as row + (srow & 15): no funnel shifts, and the consumers read bytes as before.
+        // The loads go through a descriptor based at the first chunk whose range ends at the batch's last byte, rounded up to a
+        // dword (the dword holding the last byte lies inside the allocation's last page): nothing past it is fetched, and
+        // a chunk that crosses that end is loaded as four range-checked dwords, whatever the range-check granularity of a
+        // 16-byte load.  Bytes past the row end are zeroed in registers: the h8 form's zero tap slots overlap the last chunk.
+        // Non-fused launches have the grid (H, B): the batch is gridDim.y contiguous frames.
+        const int mis = (int)(reinterpret_cast<uintptr_t>(srow) & 15);
+        const uint8_t* base = srow - mis;
+        const int span = mis + nbytes, n16 = (span + 15) >> 4;
+        const size_t left = (size_t)(src + (size_t)gridDim.y * src_img_stride - base);
+        const int rec = left < (size_t)(n16 << 4) ? (int)((left + 3) & ~(size_t)3) : (n16 << 4);
+        const __amdgpu_buffer_rsrc_t rs = __builtin_amdgcn_make_buffer_rsrc(const_cast<uint8_t*>(base), 0, rec, 0x00020000);
+        uint4* r16 = reinterpret_cast<uint4*>(row);
+        for (int i = threadIdx.x; i < n16; i += blockDim.x) {
+            const int off = i << 4;
+            uint4 v;
+            if (off + 16 <= rec) {
+                const auto d = __builtin_amdgcn_raw_buffer_load_b128(rs, off, 0, 0);
+                v = uint4{d[0], d[1], d[2], d[3]};
+            } else {
+                v = uint4{__builtin_amdgcn_raw_buffer_load_b32(rs, off, 0, 0), __builtin_amdgcn_raw_buffer_load_b32(rs, off + 4, 0, 0),
+                          __builtin_amdgcn_raw_buffer_load_b32(rs, off + 8, 0, 0), __builtin_amdgcn_raw_buffer_load_b32(rs, off + 12, 0, 0)};
+            }
+            r16[i] = off + 16 > span ? pil_keep_bytes(v, span - off) : v;
+        }
+        return row + mis;
     } else
-    // W*3 is a multiple of 4 for every supported width (W % 4 == 0); rows start 4-byte aligned.
+    // W*3 and the frame pointer are multiples of 4: rows start 4-byte aligned.
     if ((nbytes & 15) == 0) {              // 16-byte rows (W % 16 == 0, e.g. 3840): three 16-byte loads per thread, all in flight
         const uint4* s16 = reinterpret_cast<const uint4*>(srow);
         uint4* r16 = reinterpret_cast<uint4*>(row);
@@ -99,6 +140,7 @@ __device__ __forceinline__ void pil_stage_row(uint8_t* row, const uint8_t* __res
         uint32_t* r4 = reinterpret_cast<uint32_t*>(row);
         for (int i = threadIdx.x; i < (nbytes >> 2); i += blockDim.x) r4[i] = s4[i];
     }
+    return row;
 }
 
 // Any filter length: each thread produces output samples (ox, c) one after the other.
@@ -109,9 +151,8 @@ __global__ __launch_bounds__(256) void pil_resize_h(const uint8_t* __restrict__ 
                                                     size_t tmp_img_stride, const UndistortParams cam, const LabTables* __restrict__ lut,
                                                     const uint32_t* __restrict__ cam_map, int tp, unsigned src_bytes) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
-    uint8_t* row = reinterpret_cast<uint8_t*>(smem);
     const int y = blockIdx.x, b = blockIdx.y;
-    pil_stage_row<FUSED>(row, src, y, b, W, src_img_stride, cam, lut, cam_map, src_bytes);
+    const uint8_t* row = pil_stage_row<FUSED>(reinterpret_cast<uint8_t*>(smem), src, y, b, W, src_img_stride, cam, lut, cam_map, src_bytes);
     __syncthreads();
     uint8_t* orow = tmp + (size_t)b * tmp_img_stride + (size_t)y * tp;
     for (int o = threadIdx.x; o < OW * 3; o += blockDim.x) {
@@ -141,7 +182,8 @@ __global__ __launch_bounds__(256) void pil_resize_h8(const uint8_t* __restrict__
     // bytes; pixel-major (coef[ox * ksize + j]) it touches 28 cache lines, and with every block (= source row) re-reading the
     // whole table that was what paced this pass (TA cycles: 144 us per 8 frames at 1.4 TB/s).
     extern __shared__ __attribute__((aligned(16))) char smem[];
-    uint8_t* row = reinterpret_cast<uint8_t*>(smem);                      // W*3 bytes (+ 32: tap slots past the row end)
+    // W*3 bytes (+ 32: tap slots past the row end; + PIL_ROW_SLACK in front when the rows are not dword-aligned)
+    const size_t rlen = (size_t)W * 3 + 32 + (!FUSED && pil_row_unaligned(src, W) ? PIL_ROW_SLACK : 0);
     int y = blockIdx.x, b = blockIdx.y;
     if (nb > 0) {
         // fused form, 1-D grid: the nb frames of a batch share the camera's remap table.  Blocks are dealt round-robin over the 8
@@ -155,8 +197,8 @@ __global__ __launch_bounds__(256) void pil_resize_h8(const uint8_t* __restrict__
     // the output row sits in LDS at the same offset mod 16 as its destination, so the 16-byte body of the copy-out is
     // aligned on both sides whatever OW is (1333 * 3 bytes per row: rows start at every alignment)
     const int mis = (int)(reinterpret_cast<uintptr_t>(gdst) & 15);
-    uint8_t* orow_l = row + (((size_t)W * 3 + 32 + 15) & ~(size_t)15) + mis;    // OW*3 bytes
-    pil_stage_row<FUSED>(row, src, y, b, W, src_img_stride, cam, lut, cam_map, src_bytes);
+    uint8_t* orow_l = reinterpret_cast<uint8_t*>(smem) + ((rlen + 15) & ~(size_t)15) + mis;    // OW*3 bytes
+    uint8_t* row = pil_stage_row<FUSED>(reinterpret_cast<uint8_t*>(smem), src, y, b, W, src_img_stride, cam, lut, cam_map, src_bytes);
     if (threadIdx.x < 32) row[W * 3 + threadIdx.x] = 0;
     __syncthreads();
     // (requesting the taps of all of a thread's pixels before the row is staged -- one round trip instead of four -- was tried:
@@ -449,19 +491,29 @@ int apse_k_pil_resize(const uint8_t* src, uint8_t* tmp, void* out, int out_st, u
     const int tp = tmp_pitch > 0 ? tmp_pitch : OW * 3;
     if (tp < OW * 3) return APSE_E_INVALID;
     // hcT (optional, device): the horizontal taps tap-major [8][OW], zero-filled (apse_set_resize_tables builds it)
-    if ((W & 3) != 0 || (size_t)W * 3 > 150000) return APSE_E_INVALID;
+    if (H < 1 || W < 1 || H > APSE_MAX_FRAME_H || W > APSE_MAX_FRAME_W) return APSE_E_INVALID;
     UndistortParams none;
     memset(&none, 0, sizeof none);
     const bool fused = cam && (cam->do_undistort || cam->do_gamma);
     if (fused && (cam->H != H || cam->W != W)) return APSE_E_INVALID;
+    // LDS: the staged row (W*3 bytes, + PIL_ROW_SLACK when its rows are not dword-aligned), the fused form's Lab tables (static),
+    // and in the batched form 32 zero tap slots and the output row.  The widest frame fits every form but the batched one with
+    // a wide output row: that one falls back to the per-sample form.
+    const size_t slack = !fused && pil_row_unaligned(src, W) ? PIL_ROW_SLACK : 0;
+    const size_t lds1 = (size_t)W * 3 + (slack ? 32 : 0), lds_static = fused ? sizeof(LabTables) : 0;
+    const size_t lds8 = (((size_t)W * 3 + 32 + slack + 15) & ~(size_t)15) + (size_t)OW * 3 + 32;
+    static_assert(((size_t)APSE_MAX_FRAME_W * 3 + 32 + PIL_ROW_SLACK + 15) / 16 * 16 + sizeof(LabTables) + 16 <= APSE_LDS_BYTES,
+                  "APSE_MAX_FRAME_W: the staged row of the widest frame must fit a workgroup's LDS");
     // at most 8 taps: the batched form
-    const bool h8 = hk <= 8 && (reinterpret_cast<uintptr_t>(hb) & 7) == 0;
-    const size_t lds8 = (((size_t)W * 3 + 32 + 15) & ~(size_t)15) + (size_t)OW * 3 + 32;
+    const bool h8 = hk <= 8 && (reinterpret_cast<uintptr_t>(hb) & 7) == 0 && lds8 + lds_static <= APSE_LDS_BYTES;
     const int2* hb2 = reinterpret_cast<const int2*>(hb);
-    // the compact remap table and the 12-byte gathers need 32-bit byte offsets into the batch of frames
+    // the compact remap table and the 12-byte gathers need 32-bit byte offsets into the batch of frames.  The gathers' range is
+    // the batch rounded up to a dword: a dword that crosses the range's end comes back as zero, and with W % 4 != 0 the batch
+    // can end inside one (the last pixel of the last frame would lose its second and third bytes); the dword that holds the
+    // batch's last byte lies in the allocation's last page
     const size_t src_total = (size_t)B * H * W * 3;
     const uint32_t* map2 = src_total < 0x7ffffff0ull ? reinterpret_cast<const uint32_t*>(cam_map) : nullptr;
-    const unsigned sb = (unsigned)(src_total < 0x7ffffff0ull ? src_total : 0);
+    const unsigned sb = (unsigned)(src_total < 0x7ffffff0ull ? (src_total + 3) & ~(size_t)3 : 0);
     if (h8 && fused)
         hipLaunchKernelGGL(pil_resize_h8<true>, dim3(((H + 7) / 8) * 8 * B), dim3(256), lds8, s, src, tmp, hb2, hc, H, W, OW, hk, (size_t)H * W * 3,
                            (size_t)H * tp, *cam, lut, map2, hcT, tp, sb, B);
@@ -469,10 +521,10 @@ int apse_k_pil_resize(const uint8_t* src, uint8_t* tmp, void* out, int out_st, u
         hipLaunchKernelGGL(pil_resize_h8<false>, dim3(H, B), dim3(256), lds8, s, src, tmp, hb2, hc, H, W, OW, hk, (size_t)H * W * 3,
                            (size_t)H * tp, none, (const LabTables*)nullptr, (const uint32_t*)nullptr, hcT, tp, 0u, 0);
     else if (fused)
-        hipLaunchKernelGGL(pil_resize_h<true>, dim3(H, B), dim3(256), (size_t)W * 3, s, src, tmp, hb, hc, H, W, OW, hk,
+        hipLaunchKernelGGL(pil_resize_h<true>, dim3(H, B), dim3(256), lds1, s, src, tmp, hb, hc, H, W, OW, hk,
                            (size_t)H * W * 3, (size_t)H * tp, *cam, lut, map2, tp, sb);
     else
-        hipLaunchKernelGGL(pil_resize_h<false>, dim3(H, B), dim3(256), (size_t)W * 3, s, src, tmp, hb, hc, H, W, OW, hk,
+        hipLaunchKernelGGL(pil_resize_h<false>, dim3(H, B), dim3(256), lds1, s, src, tmp, hb, hc, H, W, OW, hk,
                            (size_t)H * W * 3, (size_t)H * tp, none, (const LabTables*)nullptr, (const uint32_t*)nullptr, tp, 0u);
     if ((tp & 3) == 0 && vk <= 8 && (reinterpret_cast<uintptr_t>(tmp) & 3) == 0)
         hipLaunchKernelGGL(pil_resize_v_norm_dw, dim3(((OW * 3 + 3) / 4 + 255) / 256, (OH + PIL_VROWS - 1) / PIL_VROWS, B), dim3(256), 0, s, tmp, out,

@@ -32,15 +32,28 @@ extern "C" {
 typedef struct apse_ctx apse_ctx;
 
 /* Hyper-parameters that define results (dcnn/configs/Base-RCNN-FPN.yaml,
- * dcnn/scripts/tests/visualize_uav.py:30-48, dcnn/engines/rcnn_tracker.py:33). */
+ * dcnn/scripts/tests/visualize_uav.py:30-48, dcnn/engines/rcnn_tracker.py:33).
+ *
+ * Limits (apse_create refuses a config outside them with APSE_E_INVALID; every kernel launches for a config inside them):
+ *   1 <= frame_w <= APSE_MAX_FRAME_W (49152), any width (no alignment): the horizontal resize pass stages one source row in LDS,
+ *       W*3 bytes + 15 bytes of slack for rows that are not dword-aligned + 32 zero tap slots, next to the fused form's Lab
+ *       tables (14.7 KB); that has to fit the 160 KiB of one workgroup.  apse_resize_normalize has the same bound.
+ *   1 <= frame_h <= APSE_MAX_FRAME_H (32768): with the width bound, frame_h * frame_w < 2^31 - 64, so the 32-bit pixel keys of
+ *       the mask tail (y * frame_w + x, plus a 64-pixel word) and the host decode of them cannot overflow.  (Batches of more than
+ *       2^31 bytes of frames still run; they take the undistort path without the compact remap table.)
+ *   max_batch <= 64, dets_per_image <= 100, max_batch * dets_per_image <= 1024 (the packed detection list of the mask and
+ *       association heads); num_classes <= 6 (the fused box predictor's 5 * num_classes + 1 <= 32 outputs);
+ *   rpn_pre_topk, rpn_post_topk <= 1000; embed_dim <= 256; compute_dtype 1 / 2 needs storage16 = 1. */
+#define APSE_MAX_FRAME_W 49152
+#define APSE_MAX_FRAME_H 32768
 typedef struct apse_config {
     int struct_size;              /* sizeof(apse_config), ABI check */
     int device;
-    int max_batch;                /* frames per forward (reference: 1) */
-    int frame_h, frame_w;         /* original frame, e.g. 2160 x 3840 */
+    int max_batch;                /* frames per forward (reference: 1), 1..64 */
+    int frame_h, frame_w;         /* original frame, e.g. 2160 x 3840 or 375 x 1242; any size within the limits above */
     int image_h, image_w;         /* after ResizeShortestEdge, e.g. 750 x 1333 */
     int blocks[4];                /* bottlenecks per stage, R-101 = 3,4,23,3 */
-    int num_classes;              /* 4 */
+    int num_classes;              /* 4 (1..6) */
     float score_thresh;           /* 0.5 */
     float box_nms;                /* 0.5 */
     float rpn_nms;                /* 0.7 */
@@ -225,7 +238,8 @@ int apse_mask_closest_dense(const uint8_t* mask_dev, int H, int W, float px, flo
 /* F.normalize(p=2) rows and the squared-distance matrix of rcnn_tracker.py:192-221. */
 int apse_l2_normalize(const float* x_dev, float* y_dev, int n, int D, void* stream);
 int apse_sqdist(const float* a_dev, const float* b_dev, int O, int N, int D, float* out_dev, void* stream);
-/* PIL resize + normalise as a stand-alone op (tables as in apse_set_resize_tables, device pointers). */
+/* PIL resize + normalise as a stand-alone op (tables as in apse_set_resize_tables, device pointers).  Frames of any size with
+ * 1 <= H <= APSE_MAX_FRAME_H and 1 <= W <= APSE_MAX_FRAME_W (APSE_E_INVALID otherwise). */
 /* preprocess_img (visualize_uav.py:56-71): cv2.undistort + Lab-L gamma on u8 BGR frames [B][H][W][3].
  * mtx3x3 row-major, dist up to 14 coefficients (k1 k2 p1 p2 k3 k4 k5 k6 s1..s4 tx ty; tilt must be 0),
  * lut256_host = the 256-entry L-channel table (HOST memory since round 3: the Lab step is integer arithmetic on tables derived
