@@ -13,6 +13,7 @@
 // frame size limits, as include/apse_hip.h documents them
 #define APSE_MAX_FRAME_W 49152
 #define APSE_MAX_FRAME_H 32768
+#define APSE_MAX_CLASSES 80          // num_classes bound (include/apse_hip.h)
 // LDS of one workgroup on gfx950 (160 KiB per CU)
 #define APSE_LDS_BYTES 163840
 

@@ -47,6 +47,11 @@ int apse_k_rank_final(const float*, const float*, int, const int*, const int*, i
                       int, hipStream_t);
 int apse_k_box_candidates(const float*, int, int, const float*, const int*, int, float, float, float, const float*, float,
                           float*, float*, int*, uint32_t*, float*, int, hipStream_t);
+int apse_k_box_candidates_wide(const float*, int, int, const float*, const int*, int, float, float, float, const float*, float,
+                               float*, float*, int*, uint32_t*, float*, int*, int*, int, hipStream_t);
+int apse_k_nms_lists(const float*, const float*, int, const int*, int*, int, const uint32_t*, float, int*, int*, int, void*, int,
+                     hipStream_t);
+int apse_k_rank_wide(const float*, const float*, int, const int*, const int*, int, int, float*, float*, int*, int*, int, hipStream_t);
 int apse_k_pack_detections(const float*, const float*, const int*, const int*, int, int, int, float*, float*, int*, int*,
                            int*, int*, int*, unsigned long long*, hipStream_t);
 int apse_k_roi_align(const FpnMaps*, const float*, const int*, const int*, const int*, int, int, int, void*, int, hipStream_t);
@@ -68,6 +73,7 @@ int apse_k_dense_to_bits(const uint8_t*, int, int, int, uint64_t*, unsigned long
 
 static std::string g_create_error;
 #define NMS_SLOT 1024
+#define APSE_NARROW_CLASSES 6     // up to this many classes: box_candidates / rank_merge (one thread per ROI, ncat <= 8)
 #define APSE_EV_HALF 1024    // HIP events per half of the profiling pool (one pair per timed launch)
 #define APSE_EXPECTED_DETS 8      // list length the packed-list GEMMs are shaped for (static: see add_conv)
 
@@ -112,6 +118,9 @@ struct apse_ctx {
     // box head
     FpnMaps fm;
     float *cand_boxes = nullptr, *cand_scores = nullptr, *probs = nullptr; int* cand_valid = nullptr;
+    int pred_ld = 32;                                    // row length of the fused predictor output: round_up(5 K + 1, 32)
+    bool wide = false;                                   // num_classes > APSE_NARROW_CLASSES: the wide box-inference kernels
+    int *cls_list = nullptr, *cls_cnt = nullptr;         // wide: class-major candidate lists [B][K][P] and counts [B][K]
     float *det_boxes = nullptr, *det_scores = nullptr; int *det_entry = nullptr, *det_cnt = nullptr;
     // results block (device) and layout
     apse_results_layout lay; uint8_t* res = nullptr;
@@ -308,7 +317,10 @@ static int add_conv(apse_ctx* c, std::vector<Step>& plan, const ConvSpec& sp, co
     pack_oihw(rows.data(), Cout, Cin, KH, KW, cin_p, nullptr, packed.data(), KWCp);
     std::vector<float> bias_p(Cout_p, 0.f);
     for (size_t i = 0; i < bias.size(); ++i) bias_p[i] = bias[i];
-    const bool use_bf16 = (c->cfg.compute_dtype >= 1 && Cout > 32 && sp.name != "assoc_fc");      // bf16 or f16 operands
+    // bf16 or f16 operands; the box and mask predictors are decision layers and stay f32 at any width (up to 6 classes they are
+    // narrow anyway: Cout <= 32)
+    const bool use_bf16 = (c->cfg.compute_dtype >= 1 && Cout > 32 && sp.name != "assoc_fc" && sp.name != "box_pred" &&
+                           sp.name != "mask_logits");
     float* wd = nullptr;
     uint16_t* wd16 = nullptr;
     if (use_bf16) {
@@ -718,13 +730,14 @@ static int build_plan(apse_ctx* c) {
     c->dec_scores = dalloc<float>(c, (size_t)B * 5 * PRE);
     c->dec_valid = dalloc<int>(c, (size_t)B * 5 * PRE);
     c->maxc = dalloc<uint32_t>(c, (size_t)2 * B);
-    c->keep_idx = dalloc<int>(c, (size_t)B * 8 * NMS_SLOT);
-    c->keep_cnt = dalloc<int>(c, (size_t)B * 8);
-    c->nms_scratch = dalloc<uint8_t>(c, apse_nms_scratch_bytes(8 * B));
+    const int ncat = K > 8 ? K : 8;                                   // NMS categories per image: 5 RPN levels, K classes
+    c->keep_idx = dalloc<int>(c, (size_t)B * ncat * NMS_SLOT);
+    c->keep_cnt = dalloc<int>(c, (size_t)B * ncat);
+    c->nms_scratch = dalloc<uint8_t>(c, apse_nms_scratch_bytes(ncat * B));
     c->props = dalloc<float>(c, (size_t)B * POST * 4);
     c->prop_scores = dalloc<float>(c, (size_t)B * POST);
     c->prop_entry = dalloc<int>(c, (size_t)B * POST);
-    // ---- box head: ROIAlign 7x7 -> fc1 (7x7 valid conv) -> fc2 -> fused predictor (K+1 logits, 4K deltas), ld 32
+    // ---- box head: ROIAlign 7x7 -> fc1 (7x7 valid conv) -> fc2 -> fused predictor (K+1 logits, 4K deltas), ld round_up(5K+1, 32)
     for (int l = 0; l < 4; ++l) { c->fm.p[l] = pl[l].p; c->fm.H[l] = pl[l].H; c->fm.W[l] = pl[l].W; c->fm.scale[l] = 1.0f / (float)strides[l]; }
     c->fm.st = pl[0].st;
     Tens pooled = make_t(c, "box_pooled", B * POST, 7, 7, 256, storage_type(c));
@@ -737,9 +750,15 @@ static int build_plan(apse_ctx* c) {
     if (rc) return rc;
     rc = add_conv(c, c->boxhead,
                   ConvSpec{"box_pred", {"roi_heads.box_predictor.cls_score", "roi_heads.box_predictor.bbox_pred"}, 1, 1, 1, 0, 0}, f2,
-                  POST, &pr, "box_pred", nullptr, 0, 32, 1);
+                  POST, &pr, "box_pred", nullptr, 0, apse_roundup(5 * K + 1, 32), 1);
     if (rc) return rc;
-    if (pr.C != 32 || 5 * K + 1 > 32) return fail(c, APSE_E_INVALID, "num_classes too large for the fused predictor");
+    c->pred_ld = apse_roundup(5 * K + 1, 32);
+    if (pr.C != c->pred_ld || c->t["box_pred"].st != 0) return fail(c, APSE_E_INVALID, "fused box predictor layout");
+    c->wide = K > APSE_NARROW_CLASSES;
+    if (c->wide) {
+        c->cls_list = dalloc<int>(c, (size_t)B * K * POST, false);
+        c->cls_cnt = dalloc<int>(c, (size_t)B * K);                 // zero; nms_prepare_list leaves it zero after every forward
+    }
     c->cand_boxes = dalloc<float>(c, (size_t)B * POST * K * 4);
     c->cand_scores = dalloc<float>(c, (size_t)B * POST * K);
     c->cand_valid = dalloc<int>(c, (size_t)B * POST * K);
@@ -815,9 +834,21 @@ int apse_create(const apse_config* cfg, apse_ctx** out) {
     if (!cfg || !out) return fail(nullptr, APSE_E_INVALID, "null argument");
     if (cfg->struct_size != (int)sizeof(apse_config)) return fail(nullptr, APSE_E_INVALID, "apse_config size mismatch");
     if (cfg->max_batch < 1 || cfg->max_batch > 64 || cfg->rpn_pre_topk > 1000 || cfg->rpn_post_topk > 1000 ||
-        cfg->dets_per_image > 100 || cfg->num_classes < 1 || cfg->num_classes > 6 || cfg->embed_dim > 256 ||
+        cfg->dets_per_image > 100 || cfg->num_classes < 1 || cfg->num_classes > APSE_MAX_CLASSES || cfg->embed_dim > 256 ||
         cfg->max_batch * cfg->dets_per_image > 1024)
         return fail(nullptr, APSE_E_INVALID, "config out of supported range");
+    {
+        // fewer than 1 / score_thresh classes of one ROI can score above score_thresh: a bound on the box candidates of an image.
+        // detectron2 0.1.2's batched_nms switches to another method (no category offset, unstable sort) from 40000 boxes on; the
+        // library restates only the offset form, so a config that could reach the other one is refused.
+        const double t = cfg->score_thresh;
+        const double per_roi = t > 0.0 ? ceil(1.0 / t) - 1.0 : (double)cfg->num_classes;
+        const double bound = (double)cfg->rpn_post_topk * (per_roi < cfg->num_classes ? per_roi : (double)cfg->num_classes);
+        if (bound >= 40000.0)
+            return fail(nullptr, APSE_E_INVALID,
+                        "box candidate bound rpn_post_topk * min(num_classes, ceil(1 / score_thresh) - 1) = " +
+                            std::to_string((long long)bound) + " reaches 40000, where detectron2's batched_nms changes method");
+    }
     if (cfg->frame_h < 1 || cfg->frame_w < 1 || cfg->frame_h > APSE_MAX_FRAME_H || cfg->frame_w > APSE_MAX_FRAME_W)
         return fail(nullptr, APSE_E_INVALID, "frame size out of supported range (1 <= frame_h <= " + std::to_string(APSE_MAX_FRAME_H) +
                                              ", 1 <= frame_w <= " + std::to_string(APSE_MAX_FRAME_W) + ")");
@@ -974,6 +1005,21 @@ int apse_box_head(apse_ctx* c, int batch, void* stream) {
     const float wts[4] = {10.f, 10.f, 5.f, 5.f};
     if (!c->box_maxc_clean) hipMemsetAsync(c->maxc + g.max_batch, 0, sizeof(uint32_t) * g.max_batch, s);
     c->box_maxc_clean = false;
+    if (c->wide) {
+        // 7..80 classes: wave-per-ROI candidates with class-major lists, list-fed per-class NMS, top-dets_per_image by one sort
+        rc = apse_k_box_candidates_wide(c->t["box_pred"].p, c->pred_ld, K, c->props, propcnt, P, (float)g.image_h, (float)g.image_w,
+                                        g.score_thresh, wts, (float)log(1000.0 / 16.0), c->cand_boxes, c->cand_scores, c->cand_valid,
+                                        c->maxc + g.max_batch, c->probs, c->cls_list, c->cls_cnt, batch, s);
+        if (rc) return fail(c, rc, "box candidates (wide) launch failed");
+        rc = apse_k_nms_lists(c->cand_boxes, c->cand_scores, P * K, c->cls_list, c->cls_cnt, P, c->maxc + g.max_batch, g.box_nms,
+                              c->keep_idx, c->keep_cnt, K, c->nms_scratch, batch, s);
+        if (rc) return fail(c, rc, "box nms (wide) launch failed");
+        rc = apse_k_rank_wide(c->cand_boxes, c->cand_scores, P * K, c->keep_idx, c->keep_cnt, K, g.dets_per_image, c->det_boxes,
+                              c->det_scores, c->det_entry, c->det_cnt, batch, s);
+        if (rc) return fail(c, rc, "box rank (wide) launch failed");
+        rc = pack_from_dets(c, batch, s);
+        return rc ? fail(c, rc, "pack launch failed") : APSE_OK;
+    }
     rc = apse_k_box_candidates(c->t["box_pred"].p, 32, K, c->props, propcnt, P, (float)g.image_h, (float)g.image_w, g.score_thresh,
                                wts, (float)log(1000.0 / 16.0), c->cand_boxes, c->cand_scores, c->cand_valid,
                                c->maxc + g.max_batch, c->probs, batch, s);

@@ -231,6 +231,23 @@ struct NmsScratch {
     int* entry; float* box; float* area; uint64_t* mask; int* n;
 };
 
+// Sorted keys -> the category's slot of the NMS scratch: boxes shifted by cat * (max_coord + 1) in f32 (torchvision batched_nms
+// numbers the categories that are present in the call: `cat` counts from the first one), their areas, entry ids, count.
+__device__ __forceinline__ void nms_store_sorted(const uint64_t* keys, int n, int cat, uint32_t maxc_bits,
+                                                 const float* __restrict__ boxes, NmsScratch S, size_t slot, int tid) {
+    const float off = (float)cat * (__uint_as_float(maxc_bits) + 1.0f);
+    float* bx = S.box + slot * 4 * NMS_MAX;
+    if (tid < n) {
+        const uint32_t e = (uint32_t)keys[tid];
+        const float x0 = boxes[e * 4 + 0] + off, y0 = boxes[e * 4 + 1] + off;
+        const float x1 = boxes[e * 4 + 2] + off, y1 = boxes[e * 4 + 3] + off;
+        bx[tid] = x0; bx[NMS_MAX + tid] = y0; bx[2 * NMS_MAX + tid] = x1; bx[3 * NMS_MAX + tid] = y1;
+        S.area[slot * NMS_MAX + tid] = (x1 - x0) * (y1 - y0);
+        S.entry[slot * NMS_MAX + tid] = (int)e;
+    }
+    if (tid == 0) S.n[slot] = n;
+}
+
 __global__ __launch_bounds__(1024) void nms_prepare(const float* __restrict__ boxes, const float* __restrict__ scores,
                                                     const int* __restrict__ valid, int n_total, int cat_div, int cat_mod,
                                                     const uint32_t* __restrict__ maxc, NmsScratch S, int ncat, int cat_shift,
@@ -269,18 +286,32 @@ __global__ __launch_bounds__(1024) void nms_prepare(const float* __restrict__ bo
     // l * pre_topk + i is rank i of level l's top-k list (sorted by the same key; ties by anchor index = by i) -- so the ordered
     // compaction above IS the sorted list and the 55 barrier steps of the bitonic network are skipped
     if (!presorted) block_bitonic_sort<NMS_MAX / 1024>(keys, tid);
-    // batched_nms numbers the categories that are present in the call: cat_shift = index of the first one
-    const float off = (float)(c - cat_shift) * (__uint_as_float(maxc[b]) + 1.0f);
-    float* bx = S.box + slot * 4 * NMS_MAX;
-    if (tid < n) {
-        const uint32_t e = (uint32_t)keys[tid];
-        const float x0 = boxes[e * 4 + 0] + off, y0 = boxes[e * 4 + 1] + off;
-        const float x1 = boxes[e * 4 + 2] + off, y1 = boxes[e * 4 + 3] + off;
-        bx[tid] = x0; bx[NMS_MAX + tid] = y0; bx[2 * NMS_MAX + tid] = x1; bx[3 * NMS_MAX + tid] = y1;
-        S.area[slot * NMS_MAX + tid] = (x1 - x0) * (y1 - y0);
-        S.entry[slot * NMS_MAX + tid] = (int)e;
-    }
-    if (tid == 0) S.n[slot] = n;
+    nms_store_sorted(keys, n, c - cat_shift, maxc[b], boxes, S, slot, tid);
+}
+
+// Wide box inference (K > 8): the same as nms_prepare, but category c of image b reads only its own candidate list
+// (written by box_candidates_wide: clist[b][c][0 .. ccnt[b][c]) = entry ids, in arrival order) instead of scanning all P * K
+// entries.  The sort makes the arrival order irrelevant (the keys are distinct).  The block leaves its count at zero for the
+// next forward.
+__global__ __launch_bounds__(1024) void nms_prepare_list(const float* __restrict__ boxes, const float* __restrict__ scores,
+                                                         int n_total, const int* __restrict__ clist, int* __restrict__ ccnt,
+                                                         int list_stride, const uint32_t* __restrict__ maxc, NmsScratch S,
+                                                         int ncat) {
+    __shared__ uint64_t keys[NMS_MAX];
+    const int c = blockIdx.x, b = blockIdx.y, tid = threadIdx.x;
+    boxes += (size_t)b * n_total * 4;
+    scores += (size_t)b * n_total;
+    const size_t slot = (size_t)b * ncat + c;
+    int n = ccnt[slot];
+    n = n < list_stride ? n : list_stride;              // list_stride <= NMS_MAX (launcher)
+    const int* src = clist + slot * list_stride;
+    uint64_t k = ~0ull;
+    if (tid < n) { const int e = src[tid]; k = comp_key(scores[e], (uint32_t)e); }
+    keys[tid] = k;
+    __syncthreads();                                    // every thread has read the count
+    if (tid == 0) ccnt[slot] = 0;
+    block_bitonic_sort<NMS_MAX / 1024>(keys, tid);
+    nms_store_sorted(keys, n, c, maxc[b], boxes, S, slot, tid);
 }
 
 // grid (16 column chunks, 16 row chunks, ncat*B), 64 threads: thread t owns row 64*ic + t.
@@ -480,6 +511,133 @@ __global__ __launch_bounds__(256) void box_candidates(const float* __restrict__ 
     if (probs_out) probs_out[roi * (K + 1) + K] = ex[K] / sum;
 }
 
+// Wide form (K > 8, up to 127 classes): one wave per ROI, lane l owns logits l and l + 64 (class k, or the background at k = K).
+// Softmax max and sum are wave reductions (xor butterflies: every lane ends with the same bits, whatever the launch), then each
+// lane decodes, clips and filters its classes exactly as box_candidates does.  Same outputs in the same layout (slot
+// roi * K + k, probs_out, maxc), plus a class-major list of the passing entries: clist[b][k][pos] = r * K + k with pos from
+// ccnt[b][k] (arrival order; nms_prepare_list sorts, and zeroes the counts again).
+__global__ __launch_bounds__(256) void box_candidates_wide(const float* __restrict__ pred, int ld, int K,
+                                                           const float* __restrict__ props, const int* __restrict__ prop_cnt,
+                                                           int P, float img_h, float img_w, float thresh, float wx, float wy,
+                                                           float ww, float wh, float scale_clamp, float* __restrict__ cboxes,
+                                                           float* __restrict__ cscores, int* __restrict__ cvalid,
+                                                           uint32_t* __restrict__ maxc, float* __restrict__ probs_out,
+                                                           int* __restrict__ clist, int* __restrict__ ccnt) {
+    const int b = blockIdx.y, lane = threadIdx.x & 63;
+    const int r = blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (r >= P) return;                                  // wave-uniform
+    const size_t roi = (size_t)b * P + r;
+    const bool live = r < prop_cnt[b];
+    const float* lg = pred + roi * ld;
+    const int k0 = lane, k1 = lane + 64;
+    const float l0 = k0 <= K ? lg[k0] : -INFINITY, l1 = k1 <= K ? lg[k1] : -INFINITY;
+    float mx = fmaxf(l0, l1);
+    for (int o = 32; o > 0; o >>= 1) mx = fmaxf(mx, __shfl_xor(mx, o));
+    const float e0 = k0 <= K ? expf(l0 - mx) : 0.f, e1 = k1 <= K ? expf(l1 - mx) : 0.f;
+    float sum = e0 + e1;
+    for (int o = 32; o > 0; o >>= 1) sum += __shfl_xor(sum, o);
+    const float* pb = props + roi * 4;
+    const float w = pb[2] - pb[0], h = pb[3] - pb[1];
+    const float cx = pb[0] + 0.5f * w, cy = pb[1] + 0.5f * h;
+    uint32_t m = 0u;
+    bool any = false;
+#pragma unroll
+    for (int half = 0; half < 2; ++half) {
+        const int k = half ? k1 : k0;
+        const float ex = half ? e1 : e0;
+        if (k > K) continue;
+        const float p = ex / sum;
+        if (probs_out) probs_out[roi * (K + 1) + k] = p;
+        if (k == K) continue;                            // background: probability only
+        const size_t slot = roi * K + k;
+        const float* d = lg + (K + 1) + 4 * k;
+        float dx = d[0] / wx, dy = d[1] / wy, dw = d[2] / ww, dh = d[3] / wh;
+        dw = dw > scale_clamp ? scale_clamp : dw;
+        dh = dh > scale_clamp ? scale_clamp : dh;
+        const float pcx = dx * w + cx, pcy = dy * h + cy;
+        const float pw = expf(dw) * w, ph = expf(dh) * h;
+        float x0 = pcx - 0.5f * pw, y0 = pcy - 0.5f * ph, x1 = pcx + 0.5f * pw, y1 = pcy + 0.5f * ph;
+        x0 = fminf(fmaxf(x0, 0.f), img_w);
+        y0 = fminf(fmaxf(y0, 0.f), img_h);
+        x1 = fminf(fmaxf(x1, 0.f), img_w);
+        y1 = fminf(fmaxf(y1, 0.f), img_h);
+        const int ok = live && (p > thresh);
+        cboxes[slot * 4 + 0] = x0; cboxes[slot * 4 + 1] = y0; cboxes[slot * 4 + 2] = x1; cboxes[slot * 4 + 3] = y1;
+        cscores[slot] = p;
+        cvalid[slot] = ok;
+        if (ok) {
+            const uint32_t mk = __float_as_uint(fmaxf(fmaxf(x0, x1), fmaxf(y0, y1)));   // >= 0 after the clip: uint order = float order
+            m = mk > m ? mk : m;
+            any = true;
+            const size_t ci = (size_t)b * K + k;
+            const int pos = atomicAdd(ccnt + ci, 1);     // < P: one entry per ROI and class
+            if (pos < P) clist[ci * P + pos] = r * K + k;
+        }
+    }
+    for (int o = 32; o > 0; o >>= 1) {
+        const uint32_t t = __shfl_xor(m, o);
+        m = t > m ? t : m;
+    }
+    if (__ballot(any) && lane == 0) atomicMax(maxc + b, m);
+}
+
+// Final top-`K` of the wide box inference (any number of categories up to 128): each category's kept list is sorted by (score desc, entry
+// asc), so only its first K entries can reach the output.  One block per image loads at most ncat * K keys (<= 8000 for 80
+// classes and 100 detections), pads them to the next power of two of 1024 .. 8192 and sorts them in LDS; the first
+// min(total kept, K) keys are the output, in the order and layout of rank_merge (zero-filled tail, entry -1).
+__global__ __launch_bounds__(1024) void rank_sort_wide(const float* __restrict__ boxes, const float* __restrict__ scores,
+                                                       int n_total, const int* __restrict__ keep_idx,
+                                                       const int* __restrict__ keep_cnt, int ncat, int K,
+                                                       float* __restrict__ out_boxes, float* __restrict__ out_scores,
+                                                       int* __restrict__ out_entry, int* __restrict__ out_count) {
+    extern __shared__ __attribute__((aligned(16))) char smem[];
+    uint64_t* keys = reinterpret_cast<uint64_t*>(smem);      // [<= 8192]
+    __shared__ int cnt[128], beg[129];
+    const int b = blockIdx.x, tid = threadIdx.x;
+    boxes += (size_t)b * n_total * 4;
+    scores += (size_t)b * n_total;
+    if (tid < ncat) cnt[tid] = keep_cnt[b * ncat + tid];
+    __syncthreads();
+    if (tid == 0) {
+        int t = 0;
+        for (int o = 0; o < ncat; ++o) { beg[o] = t; t += cnt[o] < K ? cnt[o] : K; }
+        beg[ncat] = t;
+    }
+    __syncthreads();
+    int total = 0;
+    for (int o = 0; o < ncat; ++o) total += cnt[o];
+    const int nload = beg[ncat];                             // <= ncat * K <= 8192 (checked by the launcher)
+    const int N = nload <= 1024 ? 1024 : nload <= 2048 ? 2048 : nload <= 4096 ? 4096 : 8192;
+    for (int i = tid; i < N; i += 1024) keys[i] = ~0ull;
+    __syncthreads();
+    // wave w loads categories w, w + 16, ..: lanes over the entries of one category
+    for (int o = tid >> 6; o < ncat; o += 16) {
+        const int n = beg[o + 1] - beg[o];
+        const int* src = keep_idx + ((size_t)b * ncat + o) * NMS_MAX;
+        for (int i = tid & 63; i < n; i += 64) { const int e = src[i]; keys[beg[o] + i] = comp_key(scores[e], (uint32_t)e); }
+    }
+    __syncthreads();
+    if (N == 1024) block_bitonic_sort<1>(keys, tid);
+    else if (N == 2048) block_bitonic_sort<2>(keys, tid);
+    else if (N == 4096) block_bitonic_sort<4>(keys, tid);
+    else block_bitonic_sort<8>(keys, tid);
+    const int nout = total < K ? total : K;
+    for (int i = tid; i < K; i += 1024) {
+        float* ob = out_boxes + ((size_t)b * K + i) * 4;
+        if (i < nout) {
+            const uint32_t e = (uint32_t)keys[i];
+            ob[0] = boxes[e * 4 + 0]; ob[1] = boxes[e * 4 + 1]; ob[2] = boxes[e * 4 + 2]; ob[3] = boxes[e * 4 + 3];
+            out_scores[(size_t)b * K + i] = scores[e];
+            out_entry[(size_t)b * K + i] = (int)e;
+        } else {
+            ob[0] = ob[1] = ob[2] = ob[3] = 0.f;
+            out_scores[(size_t)b * K + i] = 0.f;
+            out_entry[(size_t)b * K + i] = -1;
+        }
+    }
+    if (tid == 0) out_count[b] = nout;
+}
+
 // Pack per-image detections into one dense list (image id kept per entry) so the mask tail's
 // GEMMs see a contiguous M.  det_* are [B][Kd]; packed_* are [B*Kd].
 __global__ void pack_detections(const float* __restrict__ det_boxes, const float* __restrict__ det_scores,
@@ -577,6 +735,42 @@ int apse_k_box_candidates(const float* pred, int ld, int K, const float* props, 
     if (K > 7) return APSE_E_INVALID;
     hipLaunchKernelGGL(box_candidates, dim3((P + 255) / 256, B), dim3(256), 0, s, pred, ld, K, props, prop_cnt, P, img_h,
                        img_w, thresh, wts[0], wts[1], wts[2], wts[3], scale_clamp, cboxes, cscores, cvalid, maxc, probs_out);
+    return hipGetLastError() == hipSuccess ? APSE_OK : APSE_E_HIP;
+}
+int apse_k_box_candidates_wide(const float* pred, int ld, int K, const float* props, const int* prop_cnt, int P, float img_h,
+                               float img_w, float thresh, const float* wts, float scale_clamp, float* cboxes, float* cscores,
+                               int* cvalid, uint32_t* maxc, float* probs_out, int* clist, int* ccnt, int B, hipStream_t s) {
+    if (K < 1 || K > 127 || ld < 5 * K + 1 || P > NMS_MAX) return APSE_E_INVALID;
+    hipLaunchKernelGGL(box_candidates_wide, dim3((P + 3) / 4, B), dim3(256), 0, s, pred, ld, K, props, prop_cnt, P, img_h, img_w,
+                       thresh, wts[0], wts[1], wts[2], wts[3], scale_clamp, cboxes, cscores, cvalid, maxc, probs_out, clist, ccnt);
+    return hipGetLastError() == hipSuccess ? APSE_OK : APSE_E_HIP;
+}
+int apse_k_rank_wide(const float* boxes, const float* scores, int n_total, const int* keep_idx, const int* keep_cnt, int ncat,
+                     int K, float* out_boxes, float* out_scores, int* out_entry, int* out_count, int B, hipStream_t s) {
+    if (ncat < 1 || ncat > 128 || K < 1 || (size_t)ncat * K > 8192) return APSE_E_INVALID;      // one block sorts <= 8192 keys
+    static bool done = false;
+    if (!done) {
+        hipFuncSetAttribute(reinterpret_cast<const void*>(&rank_sort_wide), hipFuncAttributeMaxDynamicSharedMemorySize, 8192 * 8);
+        done = true;
+    }
+    hipLaunchKernelGGL(rank_sort_wide, dim3(B), dim3(1024), 8192 * 8, s, boxes, scores, n_total, keep_idx, keep_cnt, ncat, K,
+                       out_boxes, out_scores, out_entry, out_count);
+    return hipGetLastError() == hipSuccess ? APSE_OK : APSE_E_HIP;
+}
+int apse_k_nms_lists(const float* boxes, const float* scores, int n_total, const int* clist, int* ccnt, int list_stride,
+                     const uint32_t* maxc, float thr, int* keep_idx, int* keep_cnt, int ncat, void* scratch, int B, hipStream_t s) {
+    static bool done = false;
+    if (!done) {
+        hipFuncSetAttribute(reinterpret_cast<const void*>(&nms_scan), hipFuncAttributeMaxDynamicSharedMemorySize,
+                            NMS_MAX * 16 * 8);
+        done = true;
+    }
+    if (list_stride > NMS_MAX) return APSE_E_INVALID;
+    NmsScratch S = carve(scratch, ncat * B);
+    hipLaunchKernelGGL(nms_prepare_list, dim3(ncat, B), dim3(1024), 0, s, boxes, scores, n_total, clist, ccnt, list_stride, maxc, S,
+                       ncat);
+    hipLaunchKernelGGL(nms_matrix, dim3(16, 16, ncat * B), dim3(64), 0, s, S, thr);
+    hipLaunchKernelGGL(nms_scan, dim3(ncat, B), dim3(1024), NMS_MAX * 16 * 8, s, S, keep_idx, keep_cnt);
     return hipGetLastError() == hipSuccess ? APSE_OK : APSE_E_HIP;
 }
 int apse_k_pack_detections(const float* det_boxes, const float* det_scores, const int* det_entry, const int* det_cnt, int B,

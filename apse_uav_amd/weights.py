@@ -13,6 +13,7 @@ O(1) through 33 residual blocks in f32, bf16 and f16 (small gamma on each block'
 last norm) and so that a handful of proposals pass the 0.5 score threshold.
 """
 import math
+import pickle
 
 import torch
 
@@ -122,3 +123,47 @@ def load_association_file(path):
     """Plain state_dict, as rcnn_tracker.py:56 loads it."""
     obj = torch.load(path, map_location="cpu", weights_only=True)
     return {k: torch.as_tensor(v).to(torch.float32) for k, v in obj.items()}
+
+
+# Globals a detectron2 model-zoo pickle may name (numpy arrays and dtypes, ordered and builtin containers; protocol 2 carries
+# bytes through _codecs.encode, protocol 5 arrays through numpy's _frombuffer -- both pure data constructors): nothing else is
+# looked up, so a pickle that names any other callable is refused before it runs.
+_ZOO_PICKLE_GLOBALS = {
+    ("numpy.core.multiarray", "_reconstruct"), ("numpy._core.multiarray", "_reconstruct"),
+    ("numpy.core.numeric", "_frombuffer"), ("numpy._core.numeric", "_frombuffer"), ("_codecs", "encode"),
+    ("numpy", "ndarray"), ("numpy", "dtype"), ("numpy.core.multiarray", "ndarray"), ("numpy._core.multiarray", "ndarray"),
+    ("numpy.core.multiarray", "dtype"), ("numpy._core.multiarray", "dtype"),
+    ("collections", "OrderedDict"),
+    ("builtins", "dict"), ("builtins", "list"), ("builtins", "tuple"), ("builtins", "set"), ("builtins", "frozenset"),
+}
+
+
+class _ZooUnpickler(pickle.Unpickler):
+    def find_class(self, module, name):
+        if (module, name) not in _ZOO_PICKLE_GLOBALS:
+            raise pickle.UnpicklingError("model-zoo pickle names %s.%s, which is not an array or a container: refused" % (module, name))
+        return super().find_class(module, name)
+
+
+def convert_model_zoo_pickle(src, dst):
+    """detectron2 model-zoo ``.pkl`` (``{"model": {name: numpy array}, "__author__": ...}``, e.g. the COCO Mask R-CNN R50-FPN
+    of the reference's first demo) -> ``.pth`` ``{"model": {name: f32 tensor}}``, which ``load_detector_file`` reads with the
+    tensor-only loader.  The pickle is read through an allow-list (numpy arrays, dtypes, containers) with latin1 strings, as
+    detectron2's checkpointer reads it; any other global it names is refused without being called.  Returns the state dict."""
+    import numpy as np
+    with open(src, "rb") as f:
+        obj = _ZooUnpickler(f, encoding="latin1").load()
+    if isinstance(obj, dict) and "model" in obj:
+        obj = obj["model"]
+    if not isinstance(obj, dict):
+        raise ValueError("%s: no state dict (expected a dict, or a dict with key 'model')" % src)
+    sd = {}
+    for k, v in obj.items():
+        if not isinstance(k, str):
+            raise ValueError("%s: non-string key %r" % (src, k))
+        a = np.asarray(v)
+        if a.dtype.kind not in "fiub":
+            raise ValueError("%s: entry %s is not numeric (%s)" % (src, k, a.dtype))
+        sd[k] = torch.from_numpy(np.ascontiguousarray(a, dtype=np.float32))
+    torch.save({"model": sd}, dst)
+    return sd

@@ -42,8 +42,15 @@ typedef struct apse_ctx apse_ctx;
  *       the mask tail (y * frame_w + x, plus a 64-pixel word) and the host decode of them cannot overflow.  (Batches of more than
  *       2^31 bytes of frames still run; they take the undistort path without the compact remap table.)
  *   max_batch <= 64, dets_per_image <= 100, max_batch * dets_per_image <= 1024 (the packed detection list of the mask and
- *       association heads); num_classes <= 6 (the fused box predictor's 5 * num_classes + 1 <= 32 outputs);
+ *       association heads);
+ *   1 <= num_classes <= APSE_MAX_CLASSES (80, COCO): up to 6 classes the box head runs the narrow kernels (one thread per ROI, a
+ *       32-wide fused predictor row), from 7 on the wide ones (one wave per ROI, a round_up(5 * num_classes + 1, 32)-wide row,
+ *       class-major candidate lists, one sort of at most num_classes * dets_per_image <= 8192 kept keys per image);
+ *   rpn_post_topk * min(num_classes, ceil(1 / score_thresh) - 1) < 40000: fewer than 1 / score_thresh classes of a ROI can score
+ *       above score_thresh, so this bounds the box candidates of an image below the count at which detectron2 0.1.2's
+ *       batched_nms switches to a method without the category offset (COCO's 1000 x 19 = 19000 passes; 0.01 at 80 classes does not);
  *   rpn_pre_topk, rpn_post_topk <= 1000; embed_dim <= 256; compute_dtype 1 / 2 needs storage16 = 1. */
+#define APSE_MAX_CLASSES 80
 #define APSE_MAX_FRAME_W 49152
 #define APSE_MAX_FRAME_H 32768
 typedef struct apse_config {
@@ -53,7 +60,7 @@ typedef struct apse_config {
     int frame_h, frame_w;         /* original frame, e.g. 2160 x 3840 or 375 x 1242; any size within the limits above */
     int image_h, image_w;         /* after ResizeShortestEdge, e.g. 750 x 1333 */
     int blocks[4];                /* bottlenecks per stage, R-101 = 3,4,23,3 */
-    int num_classes;              /* 4 (1..6) */
+    int num_classes;              /* 4 (1..APSE_MAX_CLASSES = 80) */
     float score_thresh;           /* 0.5 */
     float box_nms;                /* 0.5 */
     float rpn_nms;                /* 0.7 */
