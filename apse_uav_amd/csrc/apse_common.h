@@ -53,6 +53,7 @@ struct ConvParams {
     int prec;             // 0: exact f32 MFMA; 1 / 2: bf16 / f16 operands (rounded at LDS staging unless stored so), f32 accumulate
     int x_st, res_st, y_st;   // storage type of x / res / y: 0 f32, 1 bf16, 2 f16 (pointers are then 16-bit element arrays)
     int no_stream;            // 1: keep this launch on the tiled kernel (a caller forcing a tile shape: tests, sweeps)
+    const float* wu;          // != nullptr: Winograd F(2x2,3x3) filters [Cin/8][16][Cout][8] -> the layer runs as conv_winograd_f32
 };
 
 // cfg: 0=128x128 1=64x64 2=128x32 3=128x64.  ev0/ev1 (optional) are recorded right before / after the
@@ -75,6 +76,11 @@ int apse_launch_conv_skinny(const ConvParams& p, hipStream_t s, hipEvent_t ev0 =
 int apse_launch_conv_glds16(const ConvParams& p, hipStream_t s, hipEvent_t ev0 = nullptr, hipEvent_t ev1 = nullptr);
 // which kernel apse_launch_conv runs for (p, cfg): a special kernel's label (APSE_CFG_STREAM, ...), or cfg itself (a tiled shape)
 int apse_conv_effective_cfg(const ConvParams& p, int cfg);
+// conv_winograd.hip: fused f32 Winograd F(2x2,3x3) for named 3x3 layers of the f32 plan (profiled under the slot of the tiled
+// config the layer would otherwise run, with its algorithmic FLOPs).  max_items: the most images a launch covers.
+bool apse_conv_winograd_ok(const ConvParams& p, int max_items);
+int apse_conv_winograd_blocks(const ConvParams& p);     // blocks per image
+int apse_launch_conv_winograd(const ConvParams& p, hipStream_t s, hipEvent_t ev0 = nullptr, hipEvent_t ev1 = nullptr);
 typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
 
 // ---------------------------------------------------------------- typed 4-element access (device)

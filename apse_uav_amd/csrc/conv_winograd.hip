@@ -1,0 +1,236 @@
+// Fused f32 Winograd F(2x2, 3x3) convolution for gfx950 (CDNA4), exact-f32 MFMA (v_mfma_f32_32x32x2_f32).
+//
+// Takes the 3x3 / stride 1 / pad 1 layers of the f32 mode that the plan names (FPN outputs p2 / p3, RPN conv at p2 / p3,
+// detector.hip add_conv).  16 instead of 36 multiplies per 2x2 output block: 2.25x fewer matrix-pipe FLOPs.
+//
+//   U[xi][co][ci] = (G g G^T)[i][j]   filters, transformed once on the host (float64, rounded once), xi = 4 i + j
+//   V[xi][t][ci]  = (B^T d B)[i][j]   input tile t (4x4 pixels, stride 2), computed here on VALU per k-slice
+//   M[xi][t][co]  = sum_ci V * U      16 independent GEMMs on the matrix pipe, channels ascending
+//   Y[t][co]      = A^T M A + bias    (2x2 output pixels), ReLU optional
+// Nothing transformed goes through HBM: V lives in LDS for one k-slice, M in accumulators until the epilogue.
+//
+// Block = 512 threads = 8 waves, one block per CU (128 KiB LDS).  Block tile = 64 Winograd tiles (WTR x WTC tile rows x
+// columns = 32 x 8 output pixels) x 64 output channels.  Wave w owns xi = 2w, 2w+1: 2 xi x 2 M-tiles x 2 N-tiles of 32x32
+// = 128 accumulators per lane.  Per k-slice of 8 channels (double-buffered, one barrier):
+//   - 512 threads = (tile t, transform row i, channel group cg of 4): two input rows x 4 pixels x 4 channels through a
+//     buffer descriptor (out-of-image taps get an offset past the range: zeros, i.e. the padding and partial tiles at odd
+//     H / W), row combination then column combination -> V[4 i + j][t][cg] into LDS
+//   - the U slice [16][64 co][8] is one contiguous 2 KiB run per xi (global layout [Cin/8][16][Cout][8])
+//   - LDS rows are 8 floats (32 B): the 16-byte half a lane reads is XOR-swizzled with (row >> 3) & 1, so the ds_read_b128
+//     fragment reads (lane half h takes channels 4 h .. 4 h + 3 for the four k-steps) are bank-conflict-free
+// Epilogue: per 32-channel half of the N tile the accumulators go to LDS as [16][64 t][32 co]; each thread then owns one
+// tile x 4 channels, applies A^T . A, bias, ReLU and stores the 2x2 pixels as dwordx4 (pixels past H / W are dropped).
+// No split-K, no atomics: a tile's result depends on nothing but its inputs (not on batch, grid or history).
+#include "apse_common.h"
+
+namespace {
+constexpr int WTR = 16, WTC = 4;          // Winograd tiles per block: rows x columns (64 tiles = 32 x 8 output pixels)
+constexpr int WT = WTR * WTC;
+constexpr int WN = 64;                    // output channels per block
+constexpr int KC = 8;                     // channels per k-slice
+constexpr int NTHR = 512;
+constexpr int SLICE_F = 16 * WT * KC;     // floats of V (and of U: WN == WT) per k-slice buffer
+constexpr size_t WINO_LDS = (size_t)2 * 2 * SLICE_F * sizeof(float);     // [2 buffers][V, U] = 128 KiB
+static_assert(WN == WT, "V and U slices share one size");
+static_assert((size_t)16 * WT * 32 * sizeof(float) <= WINO_LDS, "epilogue chunk must fit the staging LDS");
+}
+
+__global__ __launch_bounds__(NTHR) void conv_winograd_f32(const ConvParams p) {
+    extern __shared__ __attribute__((aligned(16))) char smem[];
+    float* Vs = reinterpret_cast<float*>(smem);          // [2][16][WT][KC]
+    float* Us = Vs + 2 * SLICE_F;                         // [2][16][WN][KC]
+    float* Cs = reinterpret_cast<float*>(smem);          // epilogue view [16][WT][32]
+
+    const int tid = threadIdx.x;
+    const int lane = tid & 63, wave = tid >> 6;
+    const int fr = lane & 31, fh = lane >> 5;
+
+    // block -> (image, tile strip, N tile); blocks are dealt round-robin over 8 XCDs: give each XCD a contiguous range so
+    // the four N tiles of one input patch run on the same L2
+    const int tiles_y = (p.OH + 2 * WTR - 1) / (2 * WTR), tiles_x = (p.OW + 2 * WTC - 1) / (2 * WTC);
+    const int nblk = p.Cout / WN;
+    const int nwg = p.B * tiles_y * tiles_x * nblk;
+    int bid;
+    {
+        const int wg = blockIdx.x;
+        const int q = nwg >> 3, r = nwg & 7, xcd = wg & 7, idx = wg >> 3;
+        bid = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + idx;
+    }
+    const int nb = bid % nblk;
+    int rest = bid / nblk;
+    const int bx = rest % tiles_x; rest /= tiles_x;
+    const int by = rest % tiles_y;
+    const int b = rest / tiles_y;
+    const int oy0 = by * 2 * WTR, ox0 = bx * 2 * WTC, n0 = nb * WN;
+    const int C = 1 << p.cin_log2;
+    const int nsteps = C / KC;
+
+    // ---- staging roles
+    // input: thread = (transform row i, tile t, channel group cg); rows ra / rb of the 4x4 tile give row i of B^T d
+    const int cg = tid & 1, t = (tid >> 1) & (WT - 1), ti = tid >> 7;
+    const int ra = ti == 0 ? 0 : (ti == 2 ? 2 : 1);
+    const int rb = ti == 0 ? 2 : (ti == 1 ? 2 : (ti == 2 ? 1 : 3));
+    const int iy_a = oy0 + 2 * (t / WTC) - 1 + ra, iy_b = oy0 + 2 * (t / WTC) - 1 + rb;
+    const int ix0 = ox0 + 2 * (t % WTC) - 1;
+    const __amdgpu_buffer_rsrc_t xrsrc =
+        __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(p.x), 0, (int)((((unsigned)(p.B * p.H * p.W)) << p.cin_log2) * 4u), 0x00020000);
+    // byte offset of channel 0 of the thread's channel group at each of its 8 taps; a tap outside the image gets a base past
+    // any range (the launcher keeps the activation tensor below 2 GiB), so every k-slice's load of it returns zeros
+    unsigned xoff[2][4];
+#pragma unroll
+    for (int r = 0; r < 2; ++r) {
+        const int iy = r ? iy_b : iy_a;
+#pragma unroll
+        for (int c = 0; c < 4; ++c) {
+            const int ix = ix0 + c;
+            const bool in = (unsigned)iy < (unsigned)p.H && (unsigned)ix < (unsigned)p.W;
+            xoff[r][c] = in ? ((((unsigned)((b * p.H + iy) * p.W + ix)) << p.cin_log2) + (unsigned)(cg * 4)) * 4u : 0x80000000u;
+        }
+    }
+    // U: four 16-byte pieces per thread, piece q = tid + 512 k: xi = q >> 7, row co = (q >> 1) & 63, half q & 1
+    const float* ubase = p.wu + (size_t)n0 * KC;
+    const size_t ustep = (size_t)16 * p.Cout * KC;        // floats per k-slice of the global U
+
+    f32x4 xr[2][4], ur[4];
+    auto fetch = [&](int s) {
+        const unsigned kb = (unsigned)(s * KC * 4);
+#pragma unroll
+        for (int r = 0; r < 2; ++r)
+#pragma unroll
+            for (int c = 0; c < 4; ++c)
+                xr[r][c] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(xrsrc, (int)(xoff[r][c] + kb), 0, 0));
+        const float* us = ubase + (size_t)s * ustep;
+#pragma unroll
+        for (int k = 0; k < 4; ++k) {
+            const int q = tid + NTHR * k;
+            const int xi = q >> 7, co = (q >> 1) & 63, h = q & 1;
+            ur[k] = *reinterpret_cast<const f32x4*>(us + ((size_t)xi * p.Cout + co) * KC + h * 4);
+        }
+    };
+    auto stage = [&](int buf) {
+        // row i of B^T d (4 pixels x 4 channels), then the column combinations: V[4 i + j]
+        f32x4 x[4];
+#pragma unroll
+        for (int c = 0; c < 4; ++c) x[c] = ti == 1 ? xr[0][c] + xr[1][c] : xr[0][c] - xr[1][c];
+        const f32x4 v[4] = {x[0] - x[2], x[1] + x[2], x[2] - x[1], x[1] - x[3]};
+        const int sw = (cg ^ ((t >> 3) & 1)) * 4;
+#pragma unroll
+        for (int j = 0; j < 4; ++j)
+            *reinterpret_cast<f32x4*>(Vs + buf * SLICE_F + ((4 * ti + j) * WT + t) * KC + sw) = v[j];
+#pragma unroll
+        for (int k = 0; k < 4; ++k) {
+            const int q = tid + NTHR * k;
+            const int xi = q >> 7, co = (q >> 1) & 63, h = q & 1;
+            *reinterpret_cast<f32x4*>(Us + buf * SLICE_F + (xi * WN + co) * KC + ((h ^ ((co >> 3) & 1)) * 4)) = ur[k];
+        }
+    };
+
+    f32x16 acc[2][2][2];
+#pragma unroll
+    for (int a = 0; a < 2; ++a)
+#pragma unroll
+        for (int i = 0; i < 2; ++i)
+#pragma unroll
+            for (int j = 0; j < 2; ++j)
+#pragma unroll
+                for (int v = 0; v < 16; ++v) acc[a][i][j][v] = 0.f;
+
+    fetch(0);
+    stage(0);
+    __syncthreads();
+    const int fsw = (fh ^ ((fr >> 3) & 1)) * 4;          // swizzled half of the fragment rows (row & 15 == fr & 15)
+    for (int s = 0; s < nsteps; ++s) {
+        const int buf = s & 1;
+        const bool more = s + 1 < nsteps;
+        if (more) fetch(s + 1);                          // in flight across this slice's MFMAs
+#pragma unroll
+        for (int a = 0; a < 2; ++a) {
+            const int xi = 2 * wave + a;
+            f32x4 af[2], bf[2];
+#pragma unroll
+            for (int i = 0; i < 2; ++i) af[i] = *reinterpret_cast<const f32x4*>(Vs + buf * SLICE_F + (xi * WT + 32 * i + fr) * KC + fsw);
+#pragma unroll
+            for (int j = 0; j < 2; ++j) bf[j] = *reinterpret_cast<const f32x4*>(Us + buf * SLICE_F + (xi * WN + 32 * j + fr) * KC + fsw);
+#pragma unroll
+            for (int k = 0; k < 4; ++k)
+#pragma unroll
+                for (int i = 0; i < 2; ++i)
+#pragma unroll
+                    for (int j = 0; j < 2; ++j)
+                        acc[a][i][j] = __builtin_amdgcn_mfma_f32_32x32x2f32(af[i][k], bf[j][k], acc[a][i][j], 0, 0, 0);
+        }
+        if (more) stage(buf ^ 1);                        // buf ^ 1 was last read before the previous barrier
+        __syncthreads();
+    }
+
+    // ---- epilogue, one 32-channel half of the N tile at a time
+    const int et = tid >> 3, eg = tid & 7;               // tile, group of 4 channels
+    const int oy = oy0 + 2 * (et / WTC), ox = ox0 + 2 * (et % WTC);
+    typedef unsigned u32x4_t __attribute__((ext_vector_type(4)));
+#pragma unroll
+    for (int j = 0; j < 2; ++j) {
+#pragma unroll
+        for (int a = 0; a < 2; ++a)
+#pragma unroll
+            for (int i = 0; i < 2; ++i)
+#pragma unroll
+                for (int v = 0; v < 16; ++v) {
+                    const int row = 32 * i + (v & 3) + 8 * (v >> 2) + 4 * fh;
+                    Cs[((2 * wave + a) * WT + row) * 32 + fr] = acc[a][i][j][v];
+                }
+        __syncthreads();
+        f32x4 m[16];
+#pragma unroll
+        for (int k = 0; k < 16; ++k) m[k] = *reinterpret_cast<const f32x4*>(Cs + (k * WT + et) * 32 + eg * 4);
+        f32x4 s0[4], s1[4];
+#pragma unroll
+        for (int c = 0; c < 4; ++c) {
+            s0[c] = m[c] + m[4 + c] + m[8 + c];
+            s1[c] = m[4 + c] - m[8 + c] - m[12 + c];
+        }
+        const int co = n0 + 32 * j + 4 * eg;
+        const f32x4 bias4 = p.bias ? *reinterpret_cast<const f32x4*>(p.bias + co) : f32x4{0.f, 0.f, 0.f, 0.f};
+        f32x4 y[2][2] = {{s0[0] + s0[1] + s0[2], s0[1] - s0[2] - s0[3]}, {s1[0] + s1[1] + s1[2], s1[1] - s1[2] - s1[3]}};
+#pragma unroll
+        for (int dy = 0; dy < 2; ++dy)
+#pragma unroll
+            for (int dx = 0; dx < 2; ++dx) {
+                f32x4 val = y[dy][dx] + bias4;
+                if (p.relu) {
+#pragma unroll
+                    for (int k = 0; k < 4; ++k) val[k] = apse_relu(val[k]);
+                }
+                if (oy + dy < p.OH && ox + dx < p.OW)
+                    APSE_NT_STORE(val, reinterpret_cast<f32x4*>(p.y + ((size_t)(b * p.OH + oy + dy) * p.OW + ox + dx) * p.y_ld + p.y_coff + co));
+            }
+        __syncthreads();                                  // Cs is rewritten by the next half
+    }
+}
+
+// the layers this kernel handles: f32 in / out, 3x3 / stride 1 / pad 1, whole 64-channel N tiles, 8-channel k-slices, plain
+// NHWC output with 16-byte aligned rows, no residual, activations below 2 GiB (32-bit descriptor offsets, see xoff)
+bool apse_conv_winograd_ok(const ConvParams& p, int max_items) {
+    return p.prec == 0 && p.x_st == 0 && p.y_st == 0 && p.KH == 3 && p.KW == 3 && p.stride == 1 && p.pad == 1 && p.out_mode == 0 &&
+           p.res_mode == 0 && p.splitk == 1 && p.Cout % WN == 0 && p.cin_log2 >= 3 && p.OH == p.H && p.OW == p.W &&
+           (p.y_ld & 3) == 0 && (p.y_coff & 3) == 0 && ((((size_t)max_items * p.H * p.W) << p.cin_log2) * 4 < 0x7fff0000ull);
+}
+
+// blocks of one image (64 Winograd tiles x 64 output channels each)
+int apse_conv_winograd_blocks(const ConvParams& p) {
+    return ((p.OH + 2 * WTR - 1) / (2 * WTR)) * ((p.OW + 2 * WTC - 1) / (2 * WTC)) * (p.Cout / WN);
+}
+
+int apse_launch_conv_winograd(const ConvParams& p, hipStream_t s, hipEvent_t ev0, hipEvent_t ev1) {
+    if (!p.wu || !apse_conv_winograd_ok(p, p.B) || p.m_count) return APSE_E_INVALID;
+    static bool attr_done = false;
+    if (!attr_done) {
+        hipFuncSetAttribute(reinterpret_cast<const void*>(&conv_winograd_f32), hipFuncAttributeMaxDynamicSharedMemorySize, (int)WINO_LDS);
+        attr_done = true;
+    }
+    const int tiles_y = (p.OH + 2 * WTR - 1) / (2 * WTR), tiles_x = (p.OW + 2 * WTC - 1) / (2 * WTC);
+    const int grid = p.B * tiles_y * tiles_x * (p.Cout / WN);
+    if (ev0) hipEventRecord(ev0, s);
+    hipLaunchKernelGGL(conv_winograd_f32, dim3(grid), dim3(NTHR), WINO_LDS, s, p);
+    if (ev1) hipEventRecord(ev1, s);
+    return hipGetLastError() == hipSuccess ? APSE_OK : APSE_E_HIP;
+}

@@ -75,6 +75,7 @@ static std::string g_create_error;
 #define NMS_SLOT 1024
 #define APSE_NARROW_CLASSES 6     // up to this many classes: box_candidates / rank_merge (one thread per ROI, ncat <= 8)
 #define APSE_EV_HALF 1024    // HIP events per half of the profiling pool (one pair per timed launch)
+#define APSE_WINO_MIN_BLOCKS 128  // f32 Winograd layers: fewest blocks per image (see add_conv)
 #define APSE_EXPECTED_DETS 8      // list length the packed-list GEMMs are shaped for (static: see add_conv)
 
 struct HostW { std::vector<float> v; std::vector<int64_t> shape; };
@@ -97,6 +98,7 @@ struct Step { StepKind kind; ConvStep c; const float* x; float* y; int H, W, C; 
 struct apse_ctx {
     apse_config cfg;
     std::string err;
+    bool f32_winograd = true;    // APSE_F32_WINOGRAD=0 (read once, at apse_create): the named f32 3x3 layers keep the direct kernel
     std::map<std::string, HostW> hw;
     bool finalized = false;
     int PH = 0, PW = 0;
@@ -227,6 +229,31 @@ static uint16_t round16(float v, int dtype) {
     return (uint16_t)((b + 0x7fffu + ((b >> 16) & 1u)) >> 16);
 }
 static int storage_type(const apse_ctx* c) { return (c->cfg.compute_dtype >= 1 && c->cfg.storage16) ? c->cfg.compute_dtype : 0; }
+
+// f32 layers that run as fused Winograd F(2x2,3x3) (conv_winograd.hip): the terminal 3x3 layers at p2 / p3 -- the FPN outputs and
+// the RPN conv, whose results feed no further 3x3 chain (conv_winograd_f32)
+static bool winograd_layer(const std::string& n) {
+    return n == "backbone.fpn_output2" || n == "backbone.fpn_output3" || n == "rpn_t2" || n == "rpn_t3";
+}
+// U = G g G^T per (cout, cin) in float64, rounded to f32 once, stored [cin_p / 8][16][Cout][8] (xi = 4 i + j): the B-operand
+// staging of conv_winograd_f32 reads one contiguous 2 KiB run per xi and k-slice.  Channels past Cin are zero.
+static std::vector<float> winograd_filters(const float* oihw, int Cout, int Cin, int cin_p) {
+    static const double G[4][3] = {{1, 0, 0}, {0.5, 0.5, 0.5}, {0.5, -0.5, 0.5}, {0, 0, 1}};
+    std::vector<float> u((size_t)16 * Cout * cin_p, 0.f);
+    for (int o = 0; o < Cout; ++o)
+        for (int ci = 0; ci < Cin; ++ci) {
+            const float* g = oihw + ((size_t)o * Cin + ci) * 9;
+            double t[4][3];                                  // G g
+            for (int i = 0; i < 4; ++i)
+                for (int s = 0; s < 3; ++s) t[i][s] = G[i][0] * g[s] + G[i][1] * g[3 + s] + G[i][2] * g[6 + s];
+            for (int i = 0; i < 4; ++i)
+                for (int j = 0; j < 4; ++j) {
+                    const double v = t[i][0] * G[j][0] + t[i][1] * G[j][1] + t[i][2] * G[j][2];      // (G g) G^T
+                    u[(((size_t)(ci / 8) * 16 + 4 * i + j) * Cout + o) * 8 + (ci & 7)] = (float)v;
+                }
+        }
+    return u;
+}
 
 static int add_conv(apse_ctx* c, std::vector<Step>& plan, const ConvSpec& sp, const Tens& in, int in_items_mult, Tens* out,
                     const std::string& out_name, const Tens* res, int res_mode, int y_ld_override, int count_kind,
@@ -390,6 +417,15 @@ static int add_conv(apse_ctx* c, std::vector<Step>& plan, const ConvSpec& sp, co
         const size_t need = (size_t)sk * Mfull * Cout;
         if (need > c->ws_floats) c->ws_floats = need;
     }
+    // fused Winograd for the named f32 3x3 layers: a plan constant (layer and shape, never the batch of a forward); cs.cfg stays
+    // the tiled config the layer would otherwise run and labels its profile slot.  Only maps of at least APSE_WINO_MIN_BLOCKS
+    // blocks per image (p3 of a 4K frame: 252): the small-frame configurations keep the direct kernel and its exact results
+    // (conv_winograd_f32)
+    if (c->f32_winograd && winograd_layer(sp.name) && count_kind == 0 && apse_conv_winograd_ok(p, c->cfg.max_batch * in_items_mult) &&
+        apse_conv_winograd_blocks(p) >= APSE_WINO_MIN_BLOCKS) {
+        p.wu = dupload(c, winograd_filters(rows.data(), Cout, Cin, cin_p));
+        if (!p.wu) return fail(c, APSE_E_NOMEM, "weight upload failed at " + sp.name);
+    }
     if (out) *out = o;
     plan.push_back(st);
     return APSE_OK;
@@ -407,8 +443,8 @@ static int run_plan(apse_ctx* c, std::vector<Step>& plan, int batch, hipStream_t
             for (size_t sj = si + 1; sj < plan.size() && sj <= si + 2; ++sj)
                 if (plan[sj].kind == S_CONV) {
                     const ConvParams& q = plan[sj].c.p;
-                    const size_t elems = (size_t)apse_roundup(q.Cout, 128) * q.KH * q.KWCp;
-                    p.next_w = q.w16 ? (const void*)q.w16 : (const void*)q.w;
+                    const size_t elems = q.wu ? (size_t)16 * q.Cout * (1 << q.cin_log2) : (size_t)apse_roundup(q.Cout, 128) * q.KH * q.KWCp;
+                    p.next_w = q.w16 ? (const void*)q.w16 : (q.wu ? (const void*)q.wu : (const void*)q.w);
                     const size_t bytes = elems * (q.w16 ? 2 : 4);
                     p.next_w_bytes = bytes > (64u << 20) ? (64u << 20) : (unsigned)bytes;
                     break;
@@ -453,6 +489,9 @@ static int run_plan(apse_ctx* c, std::vector<Step>& plan, int batch, hipStream_t
                 rc = apse_k_stem_pool16(p.x, p.w16, p.bias, st.c.pool_y, batch, p.H, p.W, p.prec, s, e0 >= 0 ? c->ev_pool[e0] : nullptr,
                                         e0 >= 0 ? c->ev_pool[e0 + 1] : nullptr);
                 cfg = APSE_CFG_STEMPOOL;
+            } else if (p.wu) {
+                // Winograd: profiled in the slot of the tiled config it replaces, with the layer's algorithmic FLOPs
+                rc = apse_launch_conv_winograd(p, s, e0 >= 0 ? c->ev_pool[e0] : nullptr, e0 >= 0 ? c->ev_pool[e0 + 1] : nullptr);
             } else {
                 rc = apse_launch_conv(p, cfg, s, e0 >= 0 ? c->ev_pool[e0] : nullptr, e0 >= 0 ? c->ev_pool[e0 + 1] : nullptr);
                 cfg = apse_conv_effective_cfg(p, cfg);                        // profile label of the kernel that actually ran
@@ -861,6 +900,10 @@ int apse_create(const apse_config* cfg, apse_ctx** out) {
     if (hipSetDevice(cfg->device) != hipSuccess) return fail(nullptr, APSE_E_HIP, "hipSetDevice failed");
     apse_ctx* c = new apse_ctx();
     c->cfg = *cfg;
+    {
+        const char* e = getenv("APSE_F32_WINOGRAD");
+        c->f32_winograd = !(e && atoi(e) == 0);
+    }
     *out = c;
     return APSE_OK;
 }

@@ -70,9 +70,11 @@ items = []
 for r in fr:
     kn = r['Kernel_Name']
     d = (int(r['End_Timestamp']) - int(r['Start_Timestamp'])) / 1e3
-    if any(t in kn.split('(')[0] for t in ('conv_igemm', 'conv1x1_stream', 'conv_glds16', 'stem_s2d_pool16', 'conv_skinny16', 'assoc_fc_slices', 'bottleneck64_fused16')):
+    if any(t in kn.split('(')[0] for t in ('conv_igemm', 'conv_winograd', 'conv1x1_stream', 'conv_glds16', 'stem_s2d_pool16', 'conv_skinny16', 'assoc_fc_slices', 'bottleneck64_fused16')):
         # the __bf16 template argument defeats rocprofv3's demangler: fall back to the raw name
-        if 'stem_s2d_pool16' in kn:
+        if 'conv_winograd' in kn:
+            lab = 'winograd F(2x2,3x3)'       # TF column: algorithmic (direct) FLOPs, 2.25x the matrix-pipe work
+        elif 'stem_s2d_pool16' in kn:
             lab = 'stem+pool fused'
         elif 'assoc_fc_slices' in kn:
             lab = 'K slices + finish'
@@ -104,7 +106,7 @@ for k, (d, fl, n) in agg.items():
 others = collections.Counter()
 for r in fr:
     kn = r['Kernel_Name']
-    if not any(t in kn.split('(')[0] for t in ('conv_igemm', 'conv1x1_stream', 'conv_glds16', 'conv_splitk_reduce', 'stem_s2d_pool16', 'conv_skinny16', 'assoc_fc_', 'bottleneck64_fused16')):
+    if not any(t in kn.split('(')[0] for t in ('conv_igemm', 'conv_winograd', 'conv1x1_stream', 'conv_glds16', 'conv_splitk_reduce', 'stem_s2d_pool16', 'conv_skinny16', 'assoc_fc_', 'bottleneck64_fused16')):
         others[kn.split('(')[0].replace('void ', '')[:40]] += (int(r['End_Timestamp']) - int(r['Start_Timestamp'])) / 1e3
 print('non-conv kernels:')
 for k, v in others.most_common(14):
