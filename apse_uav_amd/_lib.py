@@ -42,6 +42,12 @@ class ResultsLayout(C.Structure):
                     "mass", "centroid", "closest", "embedding")]
 
 
+class RenderItem(C.Structure):
+    """apse_render_item (include/apse_hip.h)."""
+    _fields_ = [("image", C.c_int), ("rect", C.c_int * 4), ("words_per_row", C.c_int), ("bits", C.c_void_p),
+                ("box", C.c_float * 4), ("rgb", C.c_uint8 * 4), ("label_off", C.c_int), ("label_len", C.c_int)]
+
+
 class ConvDesc(C.Structure):
     _fields_ = [(k, C.c_int) for k in ("B", "H", "W", "Cin", "Cout", "KH", "KW", "stride", "pad", "relu", "res_mode",
                                        "cfg", "splitk", "prec", "fuse_reduce", "x_st", "res_st", "y_st")]
@@ -118,6 +124,10 @@ def load():
         "apse_replay_packed": ([vp, vp, C.c_longlong, i, i, i, vp, C.c_longlong], C.c_longlong),
         "apse_replay_max_id": ([vp], i),
         "apse_replay_next_id": ([vp], i),
+        "apse_render_workspace_bytes": ([i, i, i], sz),
+        "apse_render_instances": ([vp, vp, i, i, i, i, vp, i, vp, sz, vp, i, vp, sz, vp], i),
+        "apse_render_pack_mask": ([vp, i, i, vp, vp], i),
+        "apse_render_font_host": ([vp, sz], sz),
         "apse_resize_normalize": ([vp, vp, vp, vp, vp, vp, i, vp, vp, i, i, i, i, i, i, i, i, C.POINTER(f * 3), vp], i),
     }
     for name, (args, ret) in sig.items():
@@ -135,7 +145,8 @@ EXPORTS = ["apse_create", "apse_destroy", "apse_last_error", "apse_version", "ap
            "apse_flops", "apse_profile", "apse_profile_read", "apse_conv_packed_elems", "apse_conv_pack_weight", "apse_conv2d", "apse_maxpool3x3s2",
            "apse_maxpool3x3s2_typed", "apse_roi_align", "apse_roi_align_typed", "apse_roi_pool", "apse_roi_features", "apse_nms_rank", "apse_mask_centroid_dense", "apse_mask_closest_dense",
            "apse_l2_normalize", "apse_sqdist", "apse_undistort_gamma", "apse_lab_tables_host", "apse_resize_normalize", "apse_replay_create", "apse_replay_destroy",
-           "apse_replay_step", "apse_replay_packed", "apse_replay_max_id", "apse_replay_next_id"]
+           "apse_replay_step", "apse_replay_packed", "apse_replay_max_id", "apse_replay_next_id", "apse_render_workspace_bytes",
+           "apse_render_instances", "apse_render_pack_mask", "apse_render_font_host"]
 
 
 def stream_ptr():

@@ -16,6 +16,9 @@ Results are identical to ``RcnnTracker.next_frame`` frame by frame (tests/test_g
     drv = PipelinedRcnnTracker(config, image_size, weights, depth=3, detector_state=sd)
     for frame_idx, objects in drv.run(frames):              # frames: iterable of HxWx3 uint8 BGR arrays
         line, _ = drv.tracker.log_line(objects, host_id, frame_idx)
+
+With the default ``want_masks=False`` the objects carry boxes, classes, scores and ids but no mask bits: TrackVisualizer
+(utils/track_visualizer.py) then draws boxes and labels only.  ``want_masks=True`` copies each frame's mask windows out.
 """
 import collections
 

@@ -285,6 +285,38 @@ int apse_replay_next_id(const apse_replay* r);
  * buffer its H2D starts from.  threads <= 1 or < 1 MB: plain memcpy.  Calls are serialised. */
 int apse_host_copy(void* dst, const void* src, size_t bytes, int threads);
 
+/* ---- track renderer (csrc/render.hip): the picture of utils/track_visualizer.py (TrackVisualizer.draw_instance_predictions,
+ * visualize_uav.py:74-82), drawn on the u8 frames [B][H][W][3] by the integer rules of DESIGN.md "Track rendering".  Stateless:
+ * no context.  One item = one instance, passed in draw order (the host sorts by box area); at most APSE_RENDER_MAX_ITEMS per call
+ * and 100 per image. */
+#define APSE_RENDER_MAX_ITEMS 1024
+#define APSE_RENDER_MAX_BREAKS 64
+#define APSE_RENDER_MAX_LINES 4
+typedef struct apse_render_item {
+    int image;                    /* frame of the batch the item is drawn on */
+    int rect[4];                  /* mask window x0, y0, x1, y1 (frame pixels, half-open) */
+    int words_per_row;            /* 64-bit words per window row; word 0 holds pixels (x0 >> 6) << 6 .. +63, bit i = pixel +i */
+    const uint64_t* bits;         /* device, (y1 - y0) rows of words_per_row words (WindowMask.bits); NULL: no mask */
+    float box[4];                 /* x0, y0, x1, y1 */
+    uint8_t rgb[4];               /* colour R, G, B (4th byte unused); placed in B, G, R byte order when bgr != 0 */
+    int label_off, label_len;     /* label bytes in labels_dev; '\n' separates lines, lines after the 4th are not drawn */
+} apse_render_item;
+/* Workspace bytes of a call with n items on H x W frames. */
+size_t apse_render_workspace_bytes(int H, int W, int n);
+/* Draws n items onto frames_dev and writes the picture to out_dev (out_dev == frames_dev: in place, only the tiles an item reaches
+ * are read and written; otherwise the frames are copied first).  items_dev [n] and labels_dev [label_bytes] are device memory;
+ * scale_breaks_host [nbreaks <= APSE_RENDER_MAX_BREAKS] (host) holds the least label height at which the glyph scale reaches
+ * 2, 3, ... (utils/track_visualizer.py render_scale_breaks).  ws_dev [ws_bytes >= apse_render_workspace_bytes(H, W, n)] is scratch.
+ * Enqueues on `stream` only: no allocation, no synchronisation (capturable into a graph). */
+int apse_render_instances(const uint8_t* frames_dev, uint8_t* out_dev, int B, int H, int W, int bgr,
+                          const apse_render_item* items_dev, int n, const uint8_t* labels_dev, size_t label_bytes,
+                          const float* scale_breaks_host, int nbreaks, void* ws_dev, size_t ws_bytes, void* stream);
+/* Dense bool/u8 mask [H][W] (nonzero = set) -> words [H][(W + 63) >> 6] in the apse_render_item bit layout (x0 = 0). */
+int apse_render_pack_mask(const uint8_t* mask_dev, int H, int W, uint64_t* words_dev, void* stream);
+/* Host only: the renderer's 5x7 font, 95 glyphs (bytes 32..126) x 7 rows, bit 4 = leftmost column.  Returns the size in bytes
+ * (665); writes it to `out` when cap is large enough. */
+size_t apse_render_font_host(uint8_t* out, size_t cap);
+
 #ifdef __cplusplus
 }
 #endif
