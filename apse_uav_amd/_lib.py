@@ -35,6 +35,12 @@ class Config(C.Structure):
     ]
 
 
+class ConfigArch(Config):
+    """apse_config with the appended ``arch`` field (0 FPN, 1 C4).  ``Config`` keeps the earlier layout: a caller that passes its
+    size gets FPN."""
+    _fields_ = [("arch", C.c_int)]
+
+
 class ResultsLayout(C.Structure):
     _fields_ = [("bytes", C.c_size_t), ("n_max", C.c_int), ("dets_per_image", C.c_int), ("embed_dim", C.c_int),
                 ("max_batch", C.c_int)] + [(k, C.c_size_t) for k in (

@@ -56,13 +56,12 @@ class CfgNode(dict):
                 self[k] = CfgNode(v) if isinstance(v, dict) else (tuple(v) if isinstance(v, list) else v)
 
     def merge_from_file(self, path):
-        with open(path) as f:
-            data = yaml.safe_load(f) or {}
-        base = data.pop("_BASE_", None)
-        if base:
-            if not os.path.isabs(base):
-                base = os.path.join(os.path.dirname(path), base)
-            self.merge_from_file(base)
+        data = _load_yaml_chain(path)
+        # a C4 YAML (Base-RCNN-C4 sets ROI_HEADS.NAME: Res5ROIHeads) switches every FPN default this path reads to detectron2's
+        # C4 one first, so keys the YAML chain leaves alone do not stay FPN values (no FPN/C4 hybrid); the chain then wins
+        if (data.get("MODEL", {}).get("ROI_HEADS", {}).get("NAME") == C4_ROI_HEADS and "MODEL" in self
+                and not is_c4(self)):
+            _apply_c4_defaults(self)
         self._merge(data)
 
     def merge_from_list(self, kv):
@@ -72,6 +71,27 @@ class CfgNode(dict):
             for p in parts[:-1]:
                 node = node[p]
             node[parts[-1]] = v
+
+
+def _deep_update(dst, src):
+    for k, v in src.items():
+        if isinstance(v, dict) and isinstance(dst.get(k), dict):
+            _deep_update(dst[k], v)
+        else:
+            dst[k] = v
+    return dst
+
+
+def _load_yaml_chain(path):
+    """A YAML file with its ``_BASE_`` chain resolved into one nested dict (the file's keys over its base's)."""
+    with open(path) as f:
+        data = yaml.safe_load(f) or {}
+    base = data.pop("_BASE_", None)
+    if not base:
+        return data
+    if not os.path.isabs(base):
+        base = os.path.join(os.path.dirname(path), base)
+    return _deep_update(_load_yaml_chain(base), data)
 
 
 def _plain(n):
@@ -115,12 +135,66 @@ def get_cfg():
     })
 
 
+C4_ROI_HEADS = "Res5ROIHeads"
+C4_ANCHOR_SIZES = ((32, 64, 128, 256, 512),)
+C4_ANCHOR_RATIOS = ((0.5, 1.0, 2.0),)
+
+
+def is_c4(cfg):
+    """True for a C4 model (detectron2 Base-RCNN-C4: ``MODEL.ROI_HEADS.NAME == "Res5ROIHeads"``)."""
+    return cfg.MODEL.ROI_HEADS.NAME == C4_ROI_HEADS
+
+
+def _apply_c4_defaults(cfg):
+    """detectron2 0.1.2's values, for a C4 model, of the keys this path reads (Base-RCNN-C4.yaml over the library defaults)."""
+    m = cfg.MODEL
+    m.BACKBONE.NAME = "build_resnet_backbone"
+    m.RESNETS.OUT_FEATURES = ("res4",)
+    m.RESNETS.RES5_DILATION = 1
+    m.ANCHOR_GENERATOR.SIZES = C4_ANCHOR_SIZES
+    m.ANCHOR_GENERATOR.ASPECT_RATIOS = C4_ANCHOR_RATIOS
+    m.RPN.IN_FEATURES = ("res4",)
+    m.RPN.PRE_NMS_TOPK_TEST = 6000
+    m.RPN.POST_NMS_TOPK_TEST = 1000
+    m.ROI_HEADS.NAME = C4_ROI_HEADS
+    m.ROI_HEADS.IN_FEATURES = ("res4",)
+    m.ROI_BOX_HEAD.NAME = ""
+    m.ROI_BOX_HEAD.NUM_FC = 0
+    m.ROI_BOX_HEAD.POOLER_RESOLUTION = 14
+    m.ROI_MASK_HEAD.NUM_CONV = 0
+    m.ROI_MASK_HEAD.POOLER_RESOLUTION = 14
+
+
+def check_c4_supported(cfg):
+    """Refuses C4 settings the HIP path does not restate (raises ValueError)."""
+    m = cfg.MODEL
+    if tuple(tuple(s) for s in m.ANCHOR_GENERATOR.SIZES) != C4_ANCHOR_SIZES or \
+            tuple(tuple(r) for r in m.ANCHOR_GENERATOR.ASPECT_RATIOS) != C4_ANCHOR_RATIOS or \
+            float(m.ANCHOR_GENERATOR.get("OFFSET", 0.0)) != 0.0:
+        raise ValueError("C4: only detectron2's default anchors are supported (sizes %s, ratios %s, offset 0)"
+                         % (C4_ANCHOR_SIZES, C4_ANCHOR_RATIOS))
+    if int(m.RESNETS.get("RES5_DILATION", 1)) != 1:
+        raise ValueError("C4: RES5_DILATION 2 is not supported")
+    if not m.MASK_ON:
+        raise ValueError("C4: box-only models (MASK_ON False) are not supported")
+    if tuple(m.RPN.IN_FEATURES) != ("res4",) or tuple(m.ROI_HEADS.IN_FEATURES) != ("res4",):
+        raise ValueError("C4: the RPN and the ROI heads read res4")
+    if int(m.ROI_BOX_HEAD.POOLER_RESOLUTION) != 14 or int(m.ROI_MASK_HEAD.POOLER_RESOLUTION) != 14 or \
+            int(m.ROI_MASK_HEAD.NUM_CONV) != 0:
+        raise ValueError("C4: pooler resolution 14 and no mask convolutions (NUM_CONV 0) are required")
+
+
 CLASSES_NAMES = ["car", "truck", "bus", "person"]          # visualize_uav.py:31
 
 
-def setup_cfg(weights="", score_thresh=0.5, num_classes=4, device="cuda"):
-    """Counterpart of visualize_uav.py:43-53."""
+def setup_cfg(weights="", score_thresh=0.5, num_classes=4, device="cuda", arch="FPN"):
+    """Counterpart of visualize_uav.py:43-53.  ``arch="C4"``: detectron2's C4 values (Base-RCNN-C4) for a
+    Res5ROIHeads checkpoint such as mask_rcnn_R_50_C4_3x."""
+    if arch not in ("FPN", "C4"):
+        raise ValueError("arch must be 'FPN' or 'C4'")
     cfg = get_cfg()
+    if arch == "C4":
+        _apply_c4_defaults(cfg)
     cfg.MODEL.ROI_HEADS.SCORE_THRESH_TEST = score_thresh
     cfg.MODEL.ROI_HEADS.NUM_CLASSES = num_classes
     cfg.MODEL.WEIGHTS = weights

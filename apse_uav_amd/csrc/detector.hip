@@ -69,6 +69,13 @@ int apse_k_undistort_gamma(const UndistortParams*, const uint8_t*, uint8_t*, con
 int apse_k_bits_to_dense(const uint64_t*, const int*, int, int, int, uint8_t*, hipStream_t);
 int apse_k_copy_mask_windows(const uint64_t*, uint64_t*, int, const long long*, const long long*, const int*, const int*, int, hipStream_t);
 int apse_k_dense_to_bits(const uint8_t*, int, int, int, uint64_t*, unsigned long long*, hipStream_t);
+size_t apse_c4_nms_scratch_bytes(int);
+int apse_k_c4_rpn(const C4Rpn*, int, int, float, float, float, float, float*, float*, int*, void*, float*, float*, int*, int*, int,
+                  hipStream_t);
+int apse_k_roi_align_c4(const float*, int, int, int, float, const float*, const int*, const int*, const int*, int, int, int, float*,
+                        hipStream_t);
+int apse_k_roi_pool_c4(const float*, int, int, int, const float*, const int*, const int*, int, int, float, float*, hipStream_t);
+int apse_k_mean_cells(const float*, int, int, int, float*, hipStream_t);
 }
 
 static std::string g_create_error;
@@ -148,6 +155,11 @@ struct apse_ctx {
     int ev_base = 0, cal_read = -1; std::vector<Pending> pending_read;
     // stateless-op scratch
     uint64_t* op_bits = nullptr; unsigned long long* op_sums = nullptr; size_t op_bits_words = 0;
+    // C4 (cfg.arch 1, Res5ROIHeads): the RPN on res4, the res5 stage on the box ROIs (c4_res5box, then the 7x7 mean and the
+    // predictor in `boxhead`) and again on the detections (the front of `maskhead`)
+    bool c4 = false;
+    C4Rpn c4r; void* c4_nms = nullptr;
+    std::vector<Step> c4_res5box;
 };
 
 static int fail(apse_ctx* c, int code, const std::string& msg) {
@@ -538,6 +550,64 @@ static void layout_results(apse_ctx* c) {
     L.bytes = o;
 }
 
+// Box-inference buffers of both plans: candidates, class lists (wide kernels), kept detections.
+static void alloc_box_inference(apse_ctx* c) {
+    const apse_config& g = c->cfg;
+    const int B = g.max_batch, POST = g.rpn_post_topk, K = g.num_classes, KD = g.dets_per_image;
+    c->wide = K > APSE_NARROW_CLASSES;
+    if (c->wide) {
+        c->cls_list = dalloc<int>(c, (size_t)B * K * POST, false);
+        c->cls_cnt = dalloc<int>(c, (size_t)B * K);                 // zero; nms_prepare_list leaves it zero after every forward
+    }
+    c->cand_boxes = dalloc<float>(c, (size_t)B * POST * K * 4);
+    c->cand_scores = dalloc<float>(c, (size_t)B * POST * K);
+    c->cand_valid = dalloc<int>(c, (size_t)B * POST * K);
+    c->probs = dalloc<float>(c, (size_t)B * POST * (K + 1));
+    c->det_boxes = dalloc<float>(c, (size_t)B * KD * 4);
+    c->det_scores = dalloc<float>(c, (size_t)B * KD);
+    c->det_entry = dalloc<int>(c, (size_t)B * KD);
+    c->det_cnt = dalloc<int>(c, (size_t)B);
+}
+
+// Tail of both plans: mask bit planes, the association head (roi_pool of a feat_C-channel map -> FC -> L2 normalise), the
+// split-K workspace and the resize staging.
+static int finish_plan(apse_ctx* c, int feat_C) {
+    const apse_config& g = c->cfg;
+    const int B = g.max_batch, KD = g.dets_per_image, NM = B * KD;
+    int rc;
+    c->wpr = (g.frame_w + 63) / 64;
+    for (int k = 0; k < 2; ++k) c->bits2[k] = dalloc<uint64_t>(c, (size_t)NM * g.frame_h * c->wpr, false);
+    c->sums = dalloc<unsigned long long>(c, (size_t)NM * 3);      // cleared by pack_detections in front of every mask tail
+    if (!c->bits2[0] || !c->bits2[1]) return fail(c, APSE_E_NOMEM, "mask bit planes alloc");
+    // ---- association head: roi_pool(p2) -> FC (RxR valid conv) -> L2 normalise
+    const int R = g.assoc_roi;
+    Tens ap = make_t(c, "assoc_pooled", NM, R, R, feat_C);
+    Tens er;
+    {
+        ConvSpec sp{"assoc_fc", {"association.fc"}, R, R, 1, 0, 0, R, R};
+        c->emb_raw = dalloc<float>(c, (size_t)NM * g.embed_dim);
+        rc = add_conv(c, c->embedfc, sp, ap, KD, &er, "assoc_fc", nullptr, 0, 0, 2, c->emb_raw);
+        if (rc) return rc;
+        const ConvParams& fp = c->embedfc[0].c.p;
+        // the same filters through the K-sliced form when the shape allows (K = 25600, N = 128 in the reference); APSE_NO_ASSOC_FC
+        // (read when the context is built) keeps the split-K convolution + normalise kernels
+        if (fp.w && fp.KWCp == R * feat_C && apse_assoc_fc_ok(fp.KH * fp.KWCp, g.embed_dim) && !getenv("APSE_NO_ASSOC_FC")) {
+            c->ws_assoc = dalloc<float>(c, (size_t)(fp.KH * fp.KWCp / 128) * NM * g.embed_dim, false);
+            if (!c->ws_assoc) return fail(c, APSE_E_NOMEM, "association FC workspace");
+        }
+    }
+    if (c->ws_floats) {
+        c->ws = dalloc<float>(c, c->ws_floats, false);
+        if (!c->ws) return fail(c, APSE_E_NOMEM, "split-K workspace alloc");
+    }
+    c->tile_cnt = dalloc<int>(c, 65536);        // zero-initialised; every launch leaves it zero
+    c->rs_pitch = (g.image_w * 3 + 15) & ~15;            // row pitch of the intermediate image: dword loads in the vertical pass
+    c->rs_tmp = dalloc<uint8_t>(c, (size_t)B * g.frame_h * c->rs_pitch, false);
+    hipError_t e = hipDeviceSynchronize();
+    if (e != hipSuccess) return fail(c, APSE_E_HIP, std::string("plan build: ") + hipGetErrorString(e));
+    return APSE_OK;
+}
+
 static int build_plan(apse_ctx* c) {
     const apse_config& g = c->cfg;
     const int B = g.max_batch;
@@ -793,19 +863,7 @@ static int build_plan(apse_ctx* c) {
     if (rc) return rc;
     c->pred_ld = apse_roundup(5 * K + 1, 32);
     if (pr.C != c->pred_ld || c->t["box_pred"].st != 0) return fail(c, APSE_E_INVALID, "fused box predictor layout");
-    c->wide = K > APSE_NARROW_CLASSES;
-    if (c->wide) {
-        c->cls_list = dalloc<int>(c, (size_t)B * K * POST, false);
-        c->cls_cnt = dalloc<int>(c, (size_t)B * K);                 // zero; nms_prepare_list leaves it zero after every forward
-    }
-    c->cand_boxes = dalloc<float>(c, (size_t)B * POST * K * 4);
-    c->cand_scores = dalloc<float>(c, (size_t)B * POST * K);
-    c->cand_valid = dalloc<int>(c, (size_t)B * POST * K);
-    c->probs = dalloc<float>(c, (size_t)B * POST * (K + 1));
-    c->det_boxes = dalloc<float>(c, (size_t)B * KD * 4);
-    c->det_scores = dalloc<float>(c, (size_t)B * KD);
-    c->det_entry = dalloc<int>(c, (size_t)B * KD);
-    c->det_cnt = dalloc<int>(c, (size_t)B);
+    alloc_box_inference(c);
     // ---- mask head on the packed detection list
     const int NM = B * KD;
     Tens mp = make_t(c, "mask_pooled", NM, 14, 14, 256, storage_type(c));
@@ -828,37 +886,166 @@ static int build_plan(apse_ctx* c) {
     rc = add_conv(c, c->maskhead, ConvSpec{"mask_logits", {"roi_heads.mask_head.predictor"}, 1, 1, 1, 0, 0}, md, KD, &ml,
                   "mask_logits", nullptr, 0, 0, 2);
     if (rc) return rc;
-    c->wpr = (g.frame_w + 63) / 64;
-    for (int k = 0; k < 2; ++k) c->bits2[k] = dalloc<uint64_t>(c, (size_t)NM * g.frame_h * c->wpr, false);
-    c->sums = dalloc<unsigned long long>(c, (size_t)NM * 3);      // cleared by pack_detections in front of every mask tail
-    if (!c->bits2[0] || !c->bits2[1]) return fail(c, APSE_E_NOMEM, "mask bit planes alloc");
-    // ---- association head: roi_pool(p2) -> FC (RxR valid conv) -> L2 normalise
-    const int R = g.assoc_roi;
-    Tens ap = make_t(c, "assoc_pooled", NM, R, R, 256);
-    Tens er;
-    {
-        ConvSpec sp{"assoc_fc", {"association.fc"}, R, R, 1, 0, 0, R, R};
-        c->emb_raw = dalloc<float>(c, (size_t)NM * g.embed_dim);
-        rc = add_conv(c, c->embedfc, sp, ap, KD, &er, "assoc_fc", nullptr, 0, 0, 2, c->emb_raw);
+    return finish_plan(c, 256);
+}
+
+// ------------------------------------------------------------------------------------------------ C4 plan (arch 1)
+// detectron2 Base-RCNN-C4: ResNet stem + res2..res4 on the UNPADDED image (size_divisibility 0), StandardRPNHead on res4 (15
+// anchors per cell), Res5ROIHeads: ROIAlignV2 14x14 on res4 -> res5 (first block stride 2 in its 1x1) -> 7x7 mean -> predictor;
+// mask branch: ROIAlignV2 14x14 of the detections -> res5 -> deconv 2x2 + ReLU -> 1x1 predictor (14x14 logits).  f32 only.
+static int add_res5(apse_ctx* c, std::vector<Step>& plan, const Tens& in, int items, int count_kind, const std::string& tag, Tens* out) {
+    Tens cur = in;
+    for (int bi = 0; bi < c->cfg.blocks[3]; ++bi) {
+        const std::string P = "roi_heads.res5." + std::to_string(bi);
+        const std::string T = tag + "." + std::to_string(bi);
+        const int stride = bi == 0 ? 2 : 1;
+        Tens a, b2, sc, o;
+        const Tens* resp = &cur;
+        int rc;
+        if (getw(c, P + ".shortcut.weight")) {
+            rc = add_conv(c, plan, ConvSpec{T + ".shortcut", {P + ".shortcut"}, 1, 1, stride, 0, 0}, cur, items, &sc, T + ".shortcut",
+                          nullptr, 0, 0, count_kind);
+            if (rc) return rc;
+            resp = &sc;
+        }
+        rc = add_conv(c, plan, ConvSpec{T + ".conv1", {P + ".conv1"}, 1, 1, stride, 0, 1}, cur, items, &a, T + ".conv1", nullptr, 0, 0,
+                      count_kind);
         if (rc) return rc;
-        const ConvParams& fp = c->embedfc[0].c.p;
-        // the same filters through the K-sliced form when the shape allows (K = 25600, N = 128 in the reference); APSE_NO_ASSOC_FC
-        // (read when the context is built) keeps the split-K convolution + normalise kernels
-        if (fp.w && fp.KWCp == R * 256 && apse_assoc_fc_ok(fp.KH * fp.KWCp, g.embed_dim) && !getenv("APSE_NO_ASSOC_FC")) {
-            c->ws_assoc = dalloc<float>(c, (size_t)(fp.KH * fp.KWCp / 128) * NM * g.embed_dim, false);
-            if (!c->ws_assoc) return fail(c, APSE_E_NOMEM, "association FC workspace");
+        rc = add_conv(c, plan, ConvSpec{T + ".conv2", {P + ".conv2"}, 3, 3, 1, 1, 1}, a, items, &b2, T + ".conv2", nullptr, 0, 0,
+                      count_kind);
+        if (rc) return rc;
+        rc = add_conv(c, plan, ConvSpec{T + ".conv3", {P + ".conv3"}, 1, 1, 1, 0, 1}, b2, items, &o, T + ".out" + std::to_string(bi), resp,
+                      1, 0, count_kind);
+        if (rc) return rc;
+        cur = o;
+    }
+    *out = cur;
+    return APSE_OK;
+}
+
+static int build_plan_c4(apse_ctx* c) {
+    const apse_config& g = c->cfg;
+    const int B = g.max_batch;
+    c->PH = g.image_h;                    // size_divisibility 0: no padding
+    c->PW = g.image_w;
+    layout_results(c);
+    c->res = dalloc<uint8_t>(c, c->lay.bytes);
+    if (!c->res) return fail(c, APSE_E_NOMEM, "results alloc");
+    int rc;
+    // ---- backbone: stem + max-pool + res2..res4 (keys backbone.stem.*, backbone.res{2,3,4}.N.*)
+    Tens cur;
+    Tens x0 = make_t(c, "input", B, c->PH, c->PW, 4);
+    rc = add_conv(c, c->backbone, ConvSpec{"stem.conv1", {"backbone.stem.conv1"}, 7, 7, 2, 3, 1}, x0, 1, &cur, "stem.conv1", nullptr, 0,
+                  0, 0);
+    if (rc) return rc;
+    {
+        Step st; st.kind = S_MAXPOOL; st.x = cur.p; st.H = cur.H; st.W = cur.W; st.C = cur.C;
+        Tens o = make_t(c, "stem", B, (cur.H + 2 - 3) / 2 + 1, (cur.W + 2 - 3) / 2 + 1, cur.C);
+        st.y = o.p; st.c.name = "stem.pool"; st.st = 0;
+        c->backbone.push_back(st);
+        cur = o;
+    }
+    for (int si = 0; si < 3; ++si) {
+        const std::string stage = "res" + std::to_string(si + 2);
+        for (int bi = 0; bi < g.blocks[si]; ++bi) {
+            const std::string P = "backbone." + stage + "." + std::to_string(bi);
+            const int stride = (bi == 0 && si > 0) ? 2 : 1;
+            Tens a, b2, sc, out;
+            const Tens* resp = &cur;
+            if (getw(c, P + ".shortcut.weight")) {
+                rc = add_conv(c, c->backbone, ConvSpec{P + ".shortcut", {P + ".shortcut"}, 1, 1, stride, 0, 0}, cur, 1, &sc, P + ".shortcut",
+                              nullptr, 0, 0, 0);
+                if (rc) return rc;
+                resp = &sc;
+            }
+            rc = add_conv(c, c->backbone, ConvSpec{P + ".conv1", {P + ".conv1"}, 1, 1, stride, 0, 1}, cur, 1, &a, P + ".conv1", nullptr, 0,
+                          0, 0);
+            if (rc) return rc;
+            rc = add_conv(c, c->backbone, ConvSpec{P + ".conv2", {P + ".conv2"}, 3, 3, 1, 1, 1}, a, 1, &b2, P + ".conv2", nullptr, 0, 0, 0);
+            if (rc) return rc;
+            const bool last = bi == g.blocks[si] - 1;
+            rc = add_conv(c, c->backbone, ConvSpec{P + ".conv3", {P + ".conv3"}, 1, 1, 1, 0, 1}, b2, 1, &out, last ? stage : P + ".out",
+                          resp, 1, 0, 0);
+            if (rc) return rc;
+            cur = out;
         }
     }
-    if (c->ws_floats) {
-        c->ws = dalloc<float>(c, c->ws_floats, false);
-        if (!c->ws) return fail(c, APSE_E_NOMEM, "split-K workspace alloc");
+    const Tens res4 = c->t["res4"];
+    if (res4.C < 256 || (res4.C & 255)) return fail(c, APSE_E_INVALID, "C4: res4 needs a multiple of 256 channels");
+    // ---- RPN head on res4: conv 3x3 + ReLU, then objectness (15) and deltas (60) fused into one 1x1 with an 80-wide row
+    {
+        Tens t, h;
+        rc = add_conv(c, c->rpnhead, ConvSpec{"rpn_conv", {"proposal_generator.rpn_head.conv"}, 3, 3, 1, 1, 1}, res4, 1, &t, "rpn_conv",
+                      nullptr, 0, 0, 0);
+        if (rc) return rc;
+        rc = add_conv(c, c->rpnhead,
+                      ConvSpec{"rpn_head", {"proposal_generator.rpn_head.objectness_logits", "proposal_generator.rpn_head.anchor_deltas"},
+                               1, 1, 1, 0, 0},
+                      t, 1, &h, "rpn_head", nullptr, 0, 80, 0);
+        if (rc) return rc;
+        if (c->rpnhead.back().c.p.Cout != 75) return fail(c, APSE_E_INVALID, "C4 RPN head: expected 15 objectness + 60 delta channels");
+        C4Rpn& R = c->c4r;
+        memset(&R, 0, sizeof R);
+        R.head = h.p; R.H = h.H; R.W = h.W; R.ld = 80; R.stride = 16;
+        R.n = h.H * h.W * 15;
+        R.k = R.n < g.rpn_pre_topk ? R.n : g.rpn_pre_topk;
+        static const int sizes[5] = {32, 64, 128, 256, 512};
+        static const double ratios[3] = {0.5, 1.0, 2.0};
+        for (int si = 0; si < 5; ++si)
+            for (int a = 0; a < 3; ++a) {          // DefaultAnchorGenerator: sizes outer, ratios inner
+                const double area = (double)sizes[si] * sizes[si];
+                const double w = sqrt(area / ratios[a]), hh = ratios[a] * w;
+                float* bb = R.base[3 * si + a];
+                bb[0] = (float)(-w / 2.0); bb[1] = (float)(-hh / 2.0); bb[2] = (float)(w / 2.0); bb[3] = (float)(hh / 2.0);
+            }
     }
-    c->tile_cnt = dalloc<int>(c, 65536);        // zero-initialised; every launch leaves it zero
-    c->rs_pitch = (g.image_w * 3 + 15) & ~15;            // row pitch of the intermediate image: dword loads in the vertical pass
-    c->rs_tmp = dalloc<uint8_t>(c, (size_t)B * g.frame_h * c->rs_pitch, false);
-    hipError_t e = hipDeviceSynchronize();
-    if (e != hipSuccess) return fail(c, APSE_E_HIP, std::string("plan build: ") + hipGetErrorString(e));
-    return APSE_OK;
+    const int PRE = g.rpn_pre_topk, POST = g.rpn_post_topk, K = g.num_classes, KD = g.dets_per_image;
+    c->dec_boxes = dalloc<float>(c, (size_t)B * PRE * 4);
+    c->dec_scores = dalloc<float>(c, (size_t)B * PRE);
+    c->dec_valid = dalloc<int>(c, (size_t)B * PRE);
+    c->maxc = dalloc<uint32_t>(c, (size_t)2 * B);
+    c->c4_nms = dalloc<uint8_t>(c, apse_c4_nms_scratch_bytes(B), false);
+    const int ncat = K > 8 ? K : 8;
+    c->keep_idx = dalloc<int>(c, (size_t)B * ncat * NMS_SLOT);
+    c->keep_cnt = dalloc<int>(c, (size_t)B * ncat);
+    c->nms_scratch = dalloc<uint8_t>(c, apse_nms_scratch_bytes(ncat * B));
+    c->props = dalloc<float>(c, (size_t)B * POST * 4);
+    c->prop_scores = dalloc<float>(c, (size_t)B * POST);
+    c->prop_entry = dalloc<int>(c, (size_t)B * POST);
+    if (!c->dec_boxes || !c->c4_nms || !c->props) return fail(c, APSE_E_NOMEM, "C4 proposal buffers");
+    // ---- box branch: ROIAlign 14x14 of res4 -> res5 -> mean over 7x7 (box_mean) -> fused predictor
+    Tens pooled = make_t(c, "box_pooled", B * POST, 14, 14, res4.C);
+    if (!pooled.p) return fail(c, APSE_E_NOMEM, "C4 box features");
+    Tens r5;
+    rc = add_res5(c, c->c4_res5box, pooled, POST, 1, "box_res5", &r5);
+    if (rc) return rc;
+    c->t["box_res5"] = r5;
+    Tens mean = make_t(c, "box_mean", B * POST, 1, 1, r5.C);
+    Tens pr;
+    rc = add_conv(c, c->boxhead,
+                  ConvSpec{"box_pred", {"roi_heads.box_predictor.cls_score", "roi_heads.box_predictor.bbox_pred"}, 1, 1, 1, 0, 0}, mean,
+                  POST, &pr, "box_pred", nullptr, 0, apse_roundup(5 * K + 1, 32), 1);
+    if (rc) return rc;
+    c->pred_ld = apse_roundup(5 * K + 1, 32);
+    if (pr.C != c->pred_ld) return fail(c, APSE_E_INVALID, "fused box predictor layout");
+    alloc_box_inference(c);
+    // ---- mask branch on the packed detection list: ROIAlign 14x14 -> res5 -> deconv + ReLU -> predictor (14 x 14 logits)
+    const int NM = B * KD;
+    Tens mp = make_t(c, "mask_pooled", NM, 14, 14, res4.C);
+    Tens m5, md, ml;
+    rc = add_res5(c, c->maskhead, mp, KD, 2, "mask_res5", &m5);
+    if (rc) return rc;
+    {
+        ConvSpec sp{"mask_deconv", {"roi_heads.mask_head.deconv"}, 1, 1, 1, 0, 1};
+        sp.deconv = 1;
+        rc = add_conv(c, c->maskhead, sp, m5, KD, &md, "mask_deconv", nullptr, 0, 0, 2);
+        if (rc) return rc;
+    }
+    rc = add_conv(c, c->maskhead, ConvSpec{"mask_logits", {"roi_heads.mask_head.predictor"}, 1, 1, 1, 0, 0}, md, KD, &ml, "mask_logits",
+                  nullptr, 0, 0, 2);
+    if (rc) return rc;
+    if (ml.H != 14 || ml.W != 14) return fail(c, APSE_E_INVALID, "C4 mask logits must be 14 x 14");
+    return finish_plan(c, res4.C);
 }
 
 // ================================================================================================ C ABI
@@ -871,8 +1058,31 @@ const char* apse_version(void) { return "apse_hip 0.6 (gfx950, f32 / bf16 / f16 
 
 int apse_create(const apse_config* cfg, apse_ctx** out) {
     if (!cfg || !out) return fail(nullptr, APSE_E_INVALID, "null argument");
-    if (cfg->struct_size != (int)sizeof(apse_config)) return fail(nullptr, APSE_E_INVALID, "apse_config size mismatch");
-    if (cfg->max_batch < 1 || cfg->max_batch > 64 || cfg->rpn_pre_topk > 1000 || cfg->rpn_post_topk > 1000 ||
+    // callers built against the header before `arch` was appended pass the shorter size: FPN
+    const int old_size = (int)offsetof(apse_config, arch);
+    if (cfg->struct_size != (int)sizeof(apse_config) && cfg->struct_size != old_size)
+        return fail(nullptr, APSE_E_INVALID, "apse_config size mismatch");
+    apse_config cf;
+    memset(&cf, 0, sizeof cf);
+    memcpy(&cf, cfg, (size_t)cfg->struct_size);
+    cf.struct_size = (int)sizeof(apse_config);
+    cfg = &cf;
+    if (cfg->arch != 0 && cfg->arch != 1) return fail(nullptr, APSE_E_INVALID, "arch must be 0 (FPN) or 1 (C4)");
+    if (cfg->arch == 1) {
+        // C4 limits: the single-level RPN keeps up to 6000 pre-NMS proposals (detectron2's C4 default); f32 only; the res5 stage
+        // runs on every box ROI (1000 x 14 x 14 x 1024 f32 = 0.8 GB of pooled features per frame), so the batch is capped where
+        // every activation tensor stays below 2^31 bytes
+        if (cfg->rpn_pre_topk < 1 || cfg->rpn_pre_topk > APSE_C4_MAX_PRE_TOPK)
+            return fail(nullptr, APSE_E_INVALID, "C4 (arch 1): rpn_pre_topk " + std::to_string(cfg->rpn_pre_topk) + " outside 1.." +
+                                                 std::to_string(APSE_C4_MAX_PRE_TOPK));
+        if (cfg->compute_dtype != 0)
+            return fail(nullptr, APSE_E_INVALID, "C4 (arch 1): compute_dtype must be 0 (f32); the 16-bit modes are FPN only");
+        if (cfg->max_batch > APSE_C4_MAX_BATCH)
+            return fail(nullptr, APSE_E_INVALID, "C4 (arch 1): max_batch " + std::to_string(cfg->max_batch) + " above the limit " +
+                                                 std::to_string(APSE_C4_MAX_BATCH));
+    }
+    const int pre_cap = cfg->arch == 1 ? APSE_C4_MAX_PRE_TOPK : 1000;
+    if (cfg->max_batch < 1 || cfg->max_batch > 64 || cfg->rpn_pre_topk > pre_cap || cfg->rpn_post_topk > 1000 ||
         cfg->dets_per_image > 100 || cfg->num_classes < 1 || cfg->num_classes > APSE_MAX_CLASSES || cfg->embed_dim > 256 ||
         cfg->max_batch * cfg->dets_per_image > 1024)
         return fail(nullptr, APSE_E_INVALID, "config out of supported range");
@@ -900,6 +1110,7 @@ int apse_create(const apse_config* cfg, apse_ctx** out) {
     if (hipSetDevice(cfg->device) != hipSuccess) return fail(nullptr, APSE_E_HIP, "hipSetDevice failed");
     apse_ctx* c = new apse_ctx();
     c->cfg = *cfg;
+    c->c4 = cfg->arch == 1;
     {
         const char* e = getenv("APSE_F32_WINOGRAD");
         c->f32_winograd = !(e && atoi(e) == 0);
@@ -938,7 +1149,7 @@ int apse_finalize_weights(apse_ctx* c) {
     if (!c) return APSE_E_INVALID;
     if (c->finalized) return fail(c, APSE_E_STATE, "already finalized");
     hipSetDevice(c->cfg.device);
-    int rc = build_plan(c);
+    int rc = c->c4 ? build_plan_c4(c) : build_plan(c);
     if (rc) return rc;
     c->hw.clear();
     c->finalized = true;
@@ -1001,8 +1212,17 @@ int apse_rpn_levels(apse_ctx* c, int batch, int level_mask, void* stream) {
     while (!((level_mask >> first_level) & 1)) ++first_level;
     hipStream_t s = (hipStream_t)stream;
     const apse_config& g = c->cfg;
+    if (c->c4 && level_mask != 31) return fail(c, APSE_E_INVALID, "C4 (arch 1) has one RPN level: level_mask must be 31");
     int rc = run_plan(c, c->rpnhead, batch, s);
     if (rc) return rc;
+    if (c->c4) {
+        int* propcnt = reinterpret_cast<int*>(c->res + c->lay.prop_count);
+        rc = apse_k_c4_rpn(&c->c4r, g.rpn_pre_topk, g.rpn_post_topk, (float)g.image_h, (float)g.image_w, (float)log(1000.0 / 16.0),
+                           g.rpn_nms, c->dec_boxes, c->dec_scores, c->dec_valid, c->c4_nms, c->props, c->prop_scores, c->prop_entry,
+                           propcnt, batch, s);
+        c->box_maxc_clean = false;
+        return rc ? fail(c, rc, "C4 rpn selection launch failed") : APSE_OK;
+    }
     for (size_t i = 0; i < c->stages.size(); ++i) {
         rc = apse_k_rpn_topk_stage(c->rl_dev, c->stage_dev[i], (int)c->stages[i].size(), c->lists, c->nslots, batch,
                                    i == 0 ? c->maxc : nullptr, s);
@@ -1040,9 +1260,22 @@ int apse_box_head(apse_ctx* c, int batch, void* stream) {
     const apse_config& g = c->cfg;
     int* propcnt = reinterpret_cast<int*>(c->res + c->lay.prop_count);
     const int P = g.rpn_post_topk, K = g.num_classes;
-    int rc = apse_k_roi_align(&c->fm, c->props, nullptr, propcnt, nullptr, P, batch * P, 7, c->t["box_pooled"].p,
+    int rc;
+    if (c->c4) {
+        const Tens& f = c->t["res4"];
+        rc = apse_k_roi_align_c4(f.p, f.H, f.W, f.C, 1.0f / 16.0f, c->props, nullptr, propcnt, nullptr, P, batch * P, 14,
+                                 c->t["box_pooled"].p, s);
+        if (rc) return fail(c, rc, "C4 roi_align(14) launch failed");
+        rc = run_plan(c, c->c4_res5box, batch, s);
+        if (rc) return rc;
+        const Tens& r5 = c->t["box_res5"];
+        rc = apse_k_mean_cells(r5.p, batch * P, r5.H * r5.W, r5.C, c->t["box_mean"].p, s);
+        if (rc) return fail(c, rc, "C4 mean launch failed");
+    } else {
+        rc = apse_k_roi_align(&c->fm, c->props, nullptr, propcnt, nullptr, P, batch * P, 7, c->t["box_pooled"].p,
                               c->t["box_pooled"].st, s);
-    if (rc) return fail(c, rc, "roi_align(7) launch failed");
+        if (rc) return fail(c, rc, "roi_align(7) launch failed");
+    }
     rc = run_plan(c, c->boxhead, batch, s);
     if (rc) return rc;
     const float wts[4] = {10.f, 10.f, 5.f, 5.f};
@@ -1127,14 +1360,21 @@ int apse_mask_tail(apse_ctx* c, int batch, void* stream) {
     uint8_t* r = c->res;
     const int NM = batch * g.dets_per_image;
     int* total = (int*)(r + c->lay.total);
-    int rc = apse_k_roi_align(&c->fm, (float*)(r + c->lay.box_resized), (int*)(r + c->lay.img), nullptr, total, 0, NM, 14,
+    int rc;
+    if (c->c4) {
+        const Tens& f = c->t["res4"];
+        rc = apse_k_roi_align_c4(f.p, f.H, f.W, f.C, 1.0f / 16.0f, (float*)(r + c->lay.box_resized), (int*)(r + c->lay.img), nullptr,
+                                 total, 0, NM, 14, c->t["mask_pooled"].p, s);
+    } else {
+        rc = apse_k_roi_align(&c->fm, (float*)(r + c->lay.box_resized), (int*)(r + c->lay.img), nullptr, total, 0, NM, 14,
                               c->t["mask_pooled"].p, c->t["mask_pooled"].st, s);
+    }
     if (rc) return fail(c, rc, "roi_align(14) launch failed");
     rc = run_plan(c, c->maskhead, batch, s);
     if (rc) return rc;
     PasteParams p;
     p.boxes = (float*)(r + c->lay.box_resized); p.cls = (int*)(r + c->lay.cls); p.total = total;
-    p.logits = c->t["mask_logits"].p; p.M = 28; p.ldc = c->t["mask_logits"].C;
+    p.logits = c->t["mask_logits"].p; p.M = c->t["mask_logits"].H; p.ldc = c->t["mask_logits"].C;
     p.sx = (float)((double)g.frame_w / (double)g.image_w); p.sy = (float)((double)g.frame_h / (double)g.image_h);
     p.out_h = g.frame_h; p.out_w = g.frame_w; p.words_per_row = c->wpr; p.thresh = g.mask_thresh;
     p.boxes_out = (float*)(r + c->lay.box); p.valid = (int*)(r + c->lay.valid); p.rect = (int*)(r + c->lay.rect);
@@ -1165,9 +1405,16 @@ int apse_embed(apse_ctx* c, int batch, void* stream) {
     uint8_t* r = c->res;
     const int NM = batch * g.dets_per_image;
     int* total = (int*)(r + c->lay.total);
-    const Tens& p2 = c->t["p2"];
-    int rc = apse_k_roi_pool(p2.p, p2.st, p2.H, p2.W, (float*)(r + c->lay.box), (int*)(r + c->lay.img), total, NM, g.assoc_roi,
+    int rc;
+    if (c->c4) {
+        const Tens& f = c->t["res4"];
+        rc = apse_k_roi_pool_c4(f.p, f.H, f.W, f.C, (float*)(r + c->lay.box), (int*)(r + c->lay.img), total, NM, g.assoc_roi,
+                                g.assoc_scale, (float*)c->t["assoc_pooled"].p, s);
+    } else {
+        const Tens& p2 = c->t["p2"];
+        rc = apse_k_roi_pool(p2.p, p2.st, p2.H, p2.W, (float*)(r + c->lay.box), (int*)(r + c->lay.img), total, NM, g.assoc_roi,
                              g.assoc_scale, (float*)c->t["assoc_pooled"].p, 0, 0, s);
+    }
     if (rc) return fail(c, rc, "roi_pool launch failed");
     if (c->ws_assoc) {
         // K-sliced FC + ordered reduction + normalise (roi.hip): the filters of the plan's convolution step, its own two kernels
@@ -1341,6 +1588,7 @@ int apse_roi_features(apse_ctx* c, int image, const float* rois, const uint8_t* 
     const apse_config& g = c->cfg;
     if (image < 0 || image >= g.max_batch || n < 0 || roi_size < 1 || roi_size > 32 || (n > 0 && (!rois || !out)))
         return fail(c, APSE_E_INVALID, "bad roi_features arguments");
+    if (c->c4) return fail(c, APSE_E_INVALID, "apse_roi_features reads p2: not available under C4 (arch 1)");
     if (n == 0) return APSE_OK;
     hipStream_t s = (hipStream_t)stream;
     const Tens& p2 = c->t["p2"];
@@ -1375,9 +1623,9 @@ int apse_debug_tensor(apse_ctx* c, const char* name, void* dst, size_t max_bytes
     if (nm == "proposals") { src = c->props; n = (size_t)B * g.rpn_post_topk * 16; }
     else if (nm == "proposal_scores") { src = c->prop_scores; n = (size_t)B * g.rpn_post_topk * 4; }
     else if (nm == "proposal_entry") { src = c->prop_entry; n = (size_t)B * g.rpn_post_topk * 4; }
-    else if (nm == "rpn_decoded") { src = c->dec_boxes; n = (size_t)B * 5 * g.rpn_pre_topk * 16; }
-    else if (nm == "rpn_decoded_scores") { src = c->dec_scores; n = (size_t)B * 5 * g.rpn_pre_topk * 4; }
-    else if (nm == "rpn_decoded_valid") { src = c->dec_valid; n = (size_t)B * 5 * g.rpn_pre_topk * 4; }
+    else if (nm == "rpn_decoded") { src = c->dec_boxes; n = (size_t)B * (c->c4 ? 1 : 5) * g.rpn_pre_topk * 16; }
+    else if (nm == "rpn_decoded_scores") { src = c->dec_scores; n = (size_t)B * (c->c4 ? 1 : 5) * g.rpn_pre_topk * 4; }
+    else if (nm == "rpn_decoded_valid") { src = c->dec_valid; n = (size_t)B * (c->c4 ? 1 : 5) * g.rpn_pre_topk * 4; }
     else if (nm == "box_probs") { src = c->probs; n = (size_t)B * g.rpn_post_topk * (g.num_classes + 1) * 4; }
     else if (nm == "cand_boxes") { src = c->cand_boxes; n = (size_t)B * g.rpn_post_topk * g.num_classes * 16; }
     else if (nm == "det_boxes") { src = c->det_boxes; n = (size_t)B * g.dets_per_image * 16; }
@@ -1390,7 +1638,8 @@ int apse_debug_tensor(apse_ctx* c, const char* name, void* dst, size_t max_bytes
         if (it == c->t.end()) return fail(c, APSE_E_MISSING, "no tensor " + nm);
         const Tens& t = it->second;
         int items = B;
-        if (nm == "box_pooled" || nm == "box_fc1" || nm == "box_fc2" || nm == "box_pred") items = B * g.rpn_post_topk;
+        if (nm == "box_pooled" || nm == "box_fc1" || nm == "box_fc2" || nm == "box_pred" || nm == "box_mean" || nm == "box_res5")
+            items = B * g.rpn_post_topk;
         else if (nm.rfind("mask_", 0) == 0 || nm.rfind("assoc_", 0) == 0) items = B * g.dets_per_image;
         src = t.p; n = (size_t)items * t.H * t.W * t.C * (t.st ? 2 : 4);
     }
@@ -1406,6 +1655,7 @@ double apse_flops(apse_ctx* c, int batch, double proposals, double detections) {
     double f = 0;
     for (auto& s : c->backbone) if (s.kind == S_CONV || s.kind == S_BNECK) f += s.c.flops_per_item * batch;
     for (auto& s : c->rpnhead) f += s.c.flops_per_item * batch;
+    for (auto& s : c->c4_res5box) f += s.c.flops_per_item * proposals;
     for (auto& s : c->boxhead) f += s.c.flops_per_item * proposals;
     for (auto& s : c->maskhead) f += s.c.flops_per_item * detections;
     for (auto& s : c->embedfc) f += s.c.flops_per_item * detections;

@@ -67,8 +67,9 @@ __device__ __forceinline__ RaAxis ra_axis(float s0, int pi, float bsz, int g, in
 }
 
 // the per-sample form (any window size); also the statement the separable form is derived from
+// f: element index of the lane's first channel in this image's map; C: channels per map cell (the cell stride)
 __device__ __forceinline__ f32x4 ra_bin_direct(const void* fmap, int st, size_t f, int H, int W, float sh, float sw, float bh,
-                                                float bw, int gh, int gw, int ph, int pw) {
+                                                float bw, int gh, int gw, int ph, int pw, int C = 256) {
     f32x4 acc = {0.f, 0.f, 0.f, 0.f};
     for (int iy = 0; iy < gh; ++iy) {
         float y = sh + (float)ph * bh + ((float)iy + 0.5f) * bh / (float)gh;
@@ -85,10 +86,10 @@ __device__ __forceinline__ f32x4 ra_bin_direct(const void* fmap, int st, size_t 
             if (xl >= W - 1) { xh = xl = W - 1; x = (float)xl; } else { xh = xl + 1; }
             const float lx = x - (float)xl, hx = 1.f - lx;
             const float w1 = hy * hx, w2 = hy * lx, w3 = ly * hx, w4 = ly * lx;
-            const f32x4 v1 = apse_ld4(fmap, f + ((size_t)yl * W + xl) * 256, st);
-            const f32x4 v2 = apse_ld4(fmap, f + ((size_t)yl * W + xh) * 256, st);
-            const f32x4 v3 = apse_ld4(fmap, f + ((size_t)yh * W + xl) * 256, st);
-            const f32x4 v4 = apse_ld4(fmap, f + ((size_t)yh * W + xh) * 256, st);
+            const f32x4 v1 = apse_ld4(fmap, f + ((size_t)yl * W + xl) * C, st);
+            const f32x4 v2 = apse_ld4(fmap, f + ((size_t)yl * W + xh) * C, st);
+            const f32x4 v3 = apse_ld4(fmap, f + ((size_t)yh * W + xl) * C, st);
+            const f32x4 v4 = apse_ld4(fmap, f + ((size_t)yh * W + xh) * C, st);
             acc += w1 * v1 + w2 * v2 + w3 * v3 + w4 * v4;
         }
     }
@@ -261,6 +262,20 @@ __global__ __launch_bounds__(256, RA_MINBLK) void roi_align_nhwc(const FpnMaps F
     }
 }
 
+// torchvision roi_pool: map rows [hs, he) and columns [ws, we) of bin (ph, pw) of one roi (x1, y1, x2, y2, frame pixels)
+__device__ __forceinline__ void rp_bin_window(const float* roi, float scale, int R, int ph, int pw, int H, int W, int& hs, int& he,
+                                              int& ws, int& we) {
+    const int sw = (int)roundf(roi[0] * scale), sh = (int)roundf(roi[1] * scale);
+    const int ew = (int)roundf(roi[2] * scale), eh = (int)roundf(roi[3] * scale);
+    const int rw = (ew - sw + 1) > 1 ? (ew - sw + 1) : 1;
+    const int rh = (eh - sh + 1) > 1 ? (eh - sh + 1) : 1;
+    const float bh = (float)rh / (float)R, bw = (float)rw / (float)R;
+    hs = (int)floorf((float)ph * bh); he = (int)ceilf((float)(ph + 1) * bh);
+    ws = (int)floorf((float)pw * bw); we = (int)ceilf((float)(pw + 1) * bw);
+    hs = min(max(hs + sh, 0), H); he = min(max(he + sh, 0), H);
+    ws = min(max(ws + sw, 0), W); we = min(max(we + sw, 0), W);
+}
+
 // torchvision roi_pool forward on one NHWC map; rois in original-frame pixels, packed list.
 // One BLOCK per output bin: the four waves take the bin's rows round-robin (a bin of a frame-sized box covers hundreds
 // of cells), two cells per iteration in flight, and meet in LDS for the final max.  roi_img == nullptr: every roi
@@ -280,15 +295,8 @@ __global__ __launch_bounds__(256) void roi_pool_nhwc(const void* __restrict__ fe
         const int pb = bin - r * rr;
         const int ph = pb / R, pw = pb - ph * R;
         const size_t f = (size_t)(roi_img ? roi_img[r] : img0) * H * W * 256 + lane * 4;
-        const int sw = (int)roundf(rois[r * 4 + 0] * scale), sh = (int)roundf(rois[r * 4 + 1] * scale);
-        const int ew = (int)roundf(rois[r * 4 + 2] * scale), eh = (int)roundf(rois[r * 4 + 3] * scale);
-        const int rw = (ew - sw + 1) > 1 ? (ew - sw + 1) : 1;
-        const int rh = (eh - sh + 1) > 1 ? (eh - sh + 1) : 1;
-        const float bh = (float)rh / (float)R, bw = (float)rw / (float)R;
-        int hs = (int)floorf((float)ph * bh), he = (int)ceilf((float)(ph + 1) * bh);
-        int ws = (int)floorf((float)pw * bw), we = (int)ceilf((float)(pw + 1) * bw);
-        hs = min(max(hs + sh, 0), H); he = min(max(he + sh, 0), H);
-        ws = min(max(ws + sw, 0), W); we = min(max(we + sw, 0), W);
+        int hs, he, ws, we;
+        rp_bin_window(rois + r * 4, scale, R, ph, pw, H, W, hs, he, ws, we);
         const bool empty = (he <= hs) || (we <= ws);
         f32x4 m = {-FLT_MAX, -FLT_MAX, -FLT_MAX, -FLT_MAX};
         auto mx = [&](const f32x4 v) {
@@ -323,6 +331,123 @@ __global__ __launch_bounds__(256) void roi_pool_nhwc(const void* __restrict__ fe
         }
         __syncthreads();
     }
+}
+
+// ---- C4 (Res5ROIHeads): one stride-16 map with C = 256 * nchunk channels --------------------------------------------------
+// ROIAlignV2 (aligned, sampling ratio 0, scale 1/16) of every roi on res4, written [roi][ph][pw][C]: the NHWC layout the first
+// res5 GEMMs read.  Grid (roi blocks, C / 256): a block builds the tap tables of its roi like roi_align_nhwc and its four waves
+// take the bins of one 256-channel chunk.  f32 maps only; sums in the same (Y, X) row-major window order.
+__global__ __launch_bounds__(256) void roi_align_c4(const float* __restrict__ fmap, int H, int W, int C, float sc,
+                                                    const float* __restrict__ rois, const int* __restrict__ roi_img,
+                                                    const int* __restrict__ cnt, const int* __restrict__ total, int per_img,
+                                                    int n_max, int R, float* __restrict__ out) {
+    __shared__ float wtab[2][RA_MAXR][RA_CAP];
+    __shared__ int btab[2][RA_MAXR][2];
+    __shared__ int all_ok;
+    const int lane = threadIdx.x & 63;
+    const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    const int rr = R * R;
+    const int coff = blockIdx.y * 256 + lane * 4;
+    const int nlive = roi_img ? (*total < n_max ? *total : n_max) : n_max;
+    for (int r = blockIdx.x; r < nlive; r += gridDim.x) {
+        int img;
+        bool live;
+        if (roi_img) {
+            live = r < *total;
+            img = live ? roi_img[r] : 0;
+        } else {
+            img = r / per_img;
+            live = (r - img * per_img) < cnt[img];
+        }
+        if (!live) {
+            for (int pb = wave; pb < rr; pb += 4) *reinterpret_cast<f32x4*>(out + ((size_t)r * rr + pb) * C + coff) = f32x4{0.f, 0.f, 0.f, 0.f};
+            continue;
+        }
+        const float x1 = rois[r * 4 + 0], y1 = rois[r * 4 + 1], x2 = rois[r * 4 + 2], y2 = rois[r * 4 + 3];
+        const size_t fimg = (size_t)img * H * W * C;
+        const float sw = x1 * sc - 0.5f, sh = y1 * sc - 0.5f;
+        const float ew = x2 * sc - 0.5f, eh = y2 * sc - 0.5f;
+        const float rw = ew - sw, rh = eh - sh;
+        const float bw = rw / (float)R, bh = rh / (float)R;
+        const int gh = (int)ceilf(rh / (float)R), gw = (int)ceilf(rw / (float)R);
+        const float cntf = (float)((gh * gw) > 1 ? gh * gw : 1);
+        __syncthreads();
+        if (threadIdx.x == 0) all_ok = 1;
+        __syncthreads();
+        for (int e = threadIdx.x; e < 2 * R * RA_CAP; e += blockDim.x) {
+            const int axis = e / (R * RA_CAP), bb = (e / RA_CAP) % R, c = e & (RA_CAP - 1);
+            const RaAxis a = axis == 0 ? ra_axis(sh, bb, bh, gh, H, c) : ra_axis(sw, bb, bw, gw, W, c);
+            wtab[axis][bb][c] = a.w;
+            if (c == 0) { btab[axis][bb][0] = a.base; btab[axis][bb][1] = a.n; if (!a.ok) all_ok = 0; }
+        }
+        __syncthreads();
+        const bool sep = all_ok != 0;
+        for (int pb = wave; pb < rr; pb += 4) {
+            const int ph = pb / R, pw = pb - ph * R;
+            f32x4 acc = {0.f, 0.f, 0.f, 0.f};
+            if (!sep) {
+                acc = ra_bin_direct(fmap, 0, fimg + coff, H, W, sh, sw, bh, bw, gh, gw, ph, pw, C);
+            } else {
+                const int ybase = btab[0][ph][0], ny = btab[0][ph][1], xbase = btab[1][pw][0], nx = btab[1][pw][1];
+                const float* f0 = fmap + fimg + ((size_t)ybase * W + xbase) * C + coff;
+                for (int yy = 0; yy < ny; ++yy)
+                    for (int xx = 0; xx < nx; ++xx) acc += (wtab[0][ph][yy] * wtab[1][pw][xx]) * ld4(f0 + ((size_t)yy * W + xx) * C);
+            }
+            *reinterpret_cast<f32x4*>(out + ((size_t)r * rr + pb) * C + coff) = acc / cntf;
+        }
+    }
+}
+
+// torchvision roi_pool of roi_pool_nhwc on a map of C = 256 * gridDim.y channels (the C4 association features on res4):
+// grid (bins, C / 256), the same per-bin walk and max order per 256-channel chunk; out [roi][R][R][C].
+__global__ __launch_bounds__(256) void roi_pool_c4(const float* __restrict__ feat, int H, int W, int C,
+                                                   const float* __restrict__ rois, const int* __restrict__ roi_img,
+                                                   const int* __restrict__ total, int n_max, int R, float scale,
+                                                   float* __restrict__ out) {
+    __shared__ f32x4 part[4][64];
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int rr = R * R;
+    const int nl = *total < n_max ? *total : n_max;
+    const int live = nl * rr;
+    const int coff = blockIdx.y * 256 + lane * 4;
+    for (int bin = blockIdx.x; bin < live; bin += gridDim.x) {
+        const int r = bin / rr;
+        const int pb = bin - r * rr;
+        const int ph = pb / R, pw = pb - ph * R;
+        const float* f = feat + (size_t)roi_img[r] * H * W * C + coff;
+        int hs, he, ws, we;
+        rp_bin_window(rois + r * 4, scale, R, ph, pw, H, W, hs, he, ws, we);
+        const bool empty = (he <= hs) || (we <= ws);
+        f32x4 m = {-FLT_MAX, -FLT_MAX, -FLT_MAX, -FLT_MAX};
+        auto mx = [&](const f32x4 v) {
+            m[0] = v[0] > m[0] ? v[0] : m[0];
+            m[1] = v[1] > m[1] ? v[1] : m[1];
+            m[2] = v[2] > m[2] ? v[2] : m[2];
+            m[3] = v[3] > m[3] ? v[3] : m[3];
+        };
+        for (int y = hs + wave; y < he; y += 4)
+            for (int x = ws; x < we; ++x) mx(ld4(f + ((size_t)y * W + x) * C));
+        part[wave][lane] = m;
+        __syncthreads();
+        if (wave == 0) {
+            mx(part[1][lane]); mx(part[2][lane]); mx(part[3][lane]);
+            if (empty) m = f32x4{0.f, 0.f, 0.f, 0.f};
+            *reinterpret_cast<f32x4*>(out + ((size_t)r * rr + pb) * C + coff) = m;
+        }
+        __syncthreads();
+    }
+}
+
+// Res5ROIHeads' box_features.mean(dim=[2, 3]): [n][cells][C] -> [n][C], the cells summed in ascending order, then / cells.
+__global__ __launch_bounds__(256) void mean_cells(const float* __restrict__ x, int n, int cells, int C, float* __restrict__ y) {
+    const size_t i = (size_t)blockIdx.x * 256 + threadIdx.x;           // one float4 of one row
+    const int c4 = C >> 2;
+    if (i >= (size_t)n * c4) return;
+    const size_t r = i / c4, c = (i - r * c4) * 4;
+    const float* p = x + r * cells * C + c;
+    f32x4 acc = {0.f, 0.f, 0.f, 0.f};
+    for (int k = 0; k < cells; ++k) acc += ld4(p + (size_t)k * C);
+    *reinterpret_cast<f32x4*>(y + r * C + c) = acc / (float)cells;
 }
 
 // F.interpolate(mask.float(), size=(OH, OW), mode='bilinear') with align_corners=False
@@ -529,6 +654,31 @@ int apse_k_roi_pool(const void* feat, int st, int H, int W, const float* rois, c
     if (blocks > 2048) blocks = 2048;
     hipLaunchKernelGGL(roi_pool_nhwc, dim3(blocks), dim3(256), 0, s, feat, st, H, W, rois, roi_img, total, n_max, R, scale,
                        out, img0, nchw);
+    return hipGetLastError() == hipSuccess ? APSE_OK : APSE_E_HIP;
+}
+int apse_k_roi_align_c4(const float* fmap, int H, int W, int C, float scale, const float* rois, const int* roi_img, const int* cnt,
+                        const int* total, int per_img, int n_max, int R, float* out, hipStream_t s) {
+    if (n_max <= 0) return APSE_OK;
+    if (C < 256 || (C & 255) || R < 1 || R > RA_MAXR) return APSE_E_INVALID;
+    const int blocks = n_max < 4096 ? n_max : 4096;
+    hipLaunchKernelGGL(roi_align_c4, dim3(blocks, C / 256), dim3(256), 0, s, fmap, H, W, C, scale, rois, roi_img, cnt, total, per_img,
+                       n_max, R, out);
+    return hipGetLastError() == hipSuccess ? APSE_OK : APSE_E_HIP;
+}
+int apse_k_roi_pool_c4(const float* feat, int H, int W, int C, const float* rois, const int* roi_img, const int* total, int n_max,
+                       int R, float scale, float* out, hipStream_t s) {
+    if (n_max <= 0) return APSE_OK;
+    if (C < 256 || (C & 255)) return APSE_E_INVALID;
+    const int bins = n_max * R * R;
+    hipLaunchKernelGGL(roi_pool_c4, dim3(bins < 8192 ? bins : 8192, C / 256), dim3(256), 0, s, feat, H, W, C, rois, roi_img, total,
+                       n_max, R, scale, out);
+    return hipGetLastError() == hipSuccess ? APSE_OK : APSE_E_HIP;
+}
+int apse_k_mean_cells(const float* x, int n, int cells, int C, float* y, hipStream_t s) {
+    if (n <= 0) return APSE_OK;
+    if (C & 3) return APSE_E_INVALID;
+    const size_t work = (size_t)n * (C >> 2);
+    hipLaunchKernelGGL(mean_cells, dim3((unsigned)((work + 255) / 256)), dim3(256), 0, s, x, n, cells, C, y);
     return hipGetLastError() == hipSuccess ? APSE_OK : APSE_E_HIP;
 }
 int apse_k_mask_resize(const uint8_t* masks, int n, int H, int W, int OH, int OW, float* out, hipStream_t s) {

@@ -638,6 +638,241 @@ __global__ __launch_bounds__(1024) void rank_sort_wide(const float* __restrict__
     if (tid == 0) out_count[b] = nout;
 }
 
+// ---------------------------------------------------------------- C4: single-level RPN selection and long-list NMS
+// detectron2's C4 RPN (Res5ROIHeads models) runs on one stride-16 map with 15 anchors per cell and keeps the top
+// PRE_NMS_TOPK_TEST = 6000 logits of up to H * W * 15 (59220 at 47 x 84) before an NMS over that one list.  The FPN
+// tournament (4096-key chunks, 1024-slot lists) and the 1024-box NMS slots do not reach that far, so this path has its own:
+//   c4_rpn_select : one block per image.  Radix select of the k-th smallest composite key (comp_key: score descending,
+//                   anchor index ascending -- distinct keys, so "key <= kth" is exactly k elements), compaction of those
+//                   k into LDS, one bitonic sort of <= 8192 keys, then Box2BoxTransform decode + clip + nonempty flag.
+//   c4_nms_prepare: ordered compaction of the valid decoded boxes (they arrive sorted) into the long NMS slot.
+//   c4_nms_matrix : 64 x 64 tiles of the suppression bit matrix (the same IoU arithmetic as nms_matrix).
+//   c4_nms_scan   : greedy scan, 64 rows per step, the bit matrix read from HBM; stops once post_topk boxes are kept
+//                   (keep[:post_topk] of the full scan), then writes the proposals.
+#define C4_SORT_N 8192      // keys sorted in LDS per image (>= rpn_pre_topk <= 6000)
+#define C4_NMS_MAX 6144     // boxes of the long NMS slot (>= 6000)
+#define C4_NMS_WORDS (C4_NMS_MAX / 64)
+
+
+__global__ __launch_bounds__(1024) void c4_rpn_select(const C4Rpn R, float img_h, float img_w, float scale_clamp,
+                                                     float* __restrict__ boxes, float* __restrict__ scores,
+                                                     int* __restrict__ valid, int pre) {
+    extern __shared__ __attribute__((aligned(16))) char smem[];
+    uint64_t* a = reinterpret_cast<uint64_t*>(smem);                    // [C4_SORT_N]
+    unsigned* hist = reinterpret_cast<unsigned*>(smem + C4_SORT_N * 8);  // [16 waves][256]
+    __shared__ uint64_t prefix_s;
+    __shared__ unsigned rank_s, fill_s;
+    const int b = blockIdx.x, tid = threadIdx.x, wave = tid >> 6;
+    const float* head = R.head + (size_t)b * R.H * R.W * R.ld;
+    const int n = R.n, k = R.k;
+    auto key_of = [&](int e) -> uint64_t {
+        const int pix = e / 15, an = e - pix * 15;
+        return comp_key(head[(size_t)pix * R.ld + an], (uint32_t)e);
+    };
+    // radix select, 8 bits per pass from the top: after pass p the top 8 (p + 1) bits of the k-th smallest key are known
+    if (tid == 0) { prefix_s = 0; rank_s = (unsigned)(k - 1); }
+    for (int pass = 0; pass < 8; ++pass) {
+        const int shift = 56 - 8 * pass;
+        for (int i = tid; i < 16 * 256; i += 1024) hist[i] = 0u;
+        __syncthreads();
+        const uint64_t prefix = prefix_s;
+        for (int e = tid; e < n; e += 1024) {
+            const uint64_t key = key_of(e);
+            if (pass == 0 || (key >> (shift + 8)) == (prefix >> (shift + 8))) atomicAdd(&hist[wave * 256 + (int)((key >> shift) & 255u)], 1u);
+        }
+        __syncthreads();
+        if (tid < 256) {
+            unsigned t = 0;
+            for (int w = 0; w < 16; ++w) t += hist[w * 256 + tid];
+            hist[tid] = t;                                                 // wave 0's row now holds the totals
+        }
+        __syncthreads();
+        if (tid == 0) {
+            unsigned r = rank_s;
+            int d = 0;
+            for (; d < 255 && r >= hist[d]; ++d) r -= hist[d];
+            rank_s = r;
+            prefix_s = prefix | ((uint64_t)d << shift);
+            fill_s = 0u;
+        }
+        __syncthreads();
+    }
+    const uint64_t kth = prefix_s;
+    for (int i = tid; i < C4_SORT_N; i += 1024) a[i] = ~0ull;
+    __syncthreads();
+    for (int e = tid; e < n; e += 1024) {
+        const uint64_t key = key_of(e);
+        if (key <= kth) a[atomicAdd(&fill_s, 1u)] = key;                   // exactly k keys (distinct keys)
+    }
+    __syncthreads();
+    block_bitonic_sort<C4_SORT_N / 1024>(a, tid);
+    for (int i = tid; i < pre; i += 1024) {
+        const size_t o = (size_t)b * pre + i;
+        if (i >= k) { valid[o] = 0; scores[o] = 0.f; continue; }
+        const uint64_t key = a[i];
+        const uint32_t e = (uint32_t)key;
+        const int pix = e / 15, an = e - pix * 15;
+        const int y = pix / R.W, x = pix - y * R.W;
+        const float sx = (float)(x * R.stride), sy = (float)(y * R.stride);
+        const float ax0 = sx + R.base[an][0], ay0 = sy + R.base[an][1];
+        const float ax1 = sx + R.base[an][2], ay1 = sy + R.base[an][3];
+        const float* d = head + (size_t)pix * R.ld + 15 + an * 4;
+        const float w = ax1 - ax0, h = ay1 - ay0;
+        const float cx = ax0 + 0.5f * w, cy = ay0 + 0.5f * h;
+        float dx = d[0] / 1.0f, dy = d[1] / 1.0f, dw = d[2] / 1.0f, dh = d[3] / 1.0f;
+        dw = dw > scale_clamp ? scale_clamp : dw;
+        dh = dh > scale_clamp ? scale_clamp : dh;
+        const float pcx = dx * w + cx, pcy = dy * h + cy;
+        const float pw = expf(dw) * w, ph = expf(dh) * h;
+        float x0 = pcx - 0.5f * pw, y0 = pcy - 0.5f * ph, x1 = pcx + 0.5f * pw, y1 = pcy + 0.5f * ph;
+        x0 = fminf(fmaxf(x0, 0.f), img_w);
+        y0 = fminf(fmaxf(y0, 0.f), img_h);
+        x1 = fminf(fmaxf(x1, 0.f), img_w);
+        y1 = fminf(fmaxf(y1, 0.f), img_h);
+        boxes[o * 4 + 0] = x0; boxes[o * 4 + 1] = y0; boxes[o * 4 + 2] = x1; boxes[o * 4 + 3] = y1;
+        scores[o] = comp_score(key);
+        valid[o] = ((x1 - x0) > 0.f) && ((y1 - y0) > 0.f);
+    }
+}
+
+// One long NMS slot per image: box [4][C4_NMS_MAX], area, entry, n; mask [C4_NMS_MAX][C4_NMS_WORDS] u64.
+struct C4Nms { float* box; float* area; int* entry; int* n; uint64_t* mask; };
+
+// The decoded list is in (score desc, anchor asc) order already; the valid boxes keep that order (a single category: the
+// batched_nms offset is 0 * (max + 1) = 0, so the boxes go in unshifted).
+__global__ __launch_bounds__(1024) void c4_nms_prepare(const float* __restrict__ boxes, const int* __restrict__ valid, int pre,
+                                                      C4Nms S) {
+    __shared__ int wsum[17];
+    const int b = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    boxes += (size_t)b * pre * 4;
+    valid += (size_t)b * pre;
+    float* bx = S.box + (size_t)b * 4 * C4_NMS_MAX;
+    if (tid == 0) wsum[16] = 0;
+    __syncthreads();
+    for (int base = 0; base < pre; base += 1024) {
+        const int e = base + tid;
+        const bool f = e < pre && valid[e];
+        const uint64_t bal = __ballot(f);
+        if (lane == 0) wsum[wave] = __popcll(bal);
+        __syncthreads();
+        int off = wsum[16];
+        for (int w = 0; w < wave; ++w) off += wsum[w];
+        const int pos = off + __popcll(bal & ((1ull << lane) - 1ull));
+        if (f && pos < C4_NMS_MAX) {
+            const float x0 = boxes[e * 4 + 0], y0 = boxes[e * 4 + 1], x1 = boxes[e * 4 + 2], y1 = boxes[e * 4 + 3];
+            bx[pos] = x0; bx[C4_NMS_MAX + pos] = y0; bx[2 * C4_NMS_MAX + pos] = x1; bx[3 * C4_NMS_MAX + pos] = y1;
+            S.area[(size_t)b * C4_NMS_MAX + pos] = (x1 - x0) * (y1 - y0);
+            S.entry[(size_t)b * C4_NMS_MAX + pos] = e;
+        }
+        __syncthreads();
+        if (tid == 0) { int t = wsum[16]; for (int w = 0; w < 16; ++w) t += wsum[w]; wsum[16] = t; }
+        __syncthreads();
+    }
+    if (tid == 0) S.n[b] = wsum[16] < C4_NMS_MAX ? wsum[16] : C4_NMS_MAX;
+}
+
+// grid (C4_NMS_WORDS column chunks, C4_NMS_WORDS row chunks, B), 64 threads: thread t owns row 64 * ic + t.
+__global__ __launch_bounds__(64) void c4_nms_matrix(C4Nms S, float thr) {
+    __shared__ float cb[5][64];
+    const int jc = blockIdx.x, ic = blockIdx.y, b = blockIdx.z;
+    const int n = S.n[b];
+    if (jc < ic || 64 * ic >= n || 64 * jc >= n) return;
+    const int t = threadIdx.x;
+    const float* bx = S.box + (size_t)b * 4 * C4_NMS_MAX;
+    const float* ar = S.area + (size_t)b * C4_NMS_MAX;
+    const int j = 64 * jc + t;
+    if (j < n) {
+        cb[0][t] = bx[j]; cb[1][t] = bx[C4_NMS_MAX + j]; cb[2][t] = bx[2 * C4_NMS_MAX + j]; cb[3][t] = bx[3 * C4_NMS_MAX + j];
+        cb[4][t] = ar[j];
+    }
+    __syncthreads();
+    const int i = 64 * ic + t;
+    if (i >= n) return;
+    uint64_t bits = 0;
+    const float ix0 = bx[i], iy0 = bx[C4_NMS_MAX + i], ix1 = bx[2 * C4_NMS_MAX + i], iy1 = bx[3 * C4_NMS_MAX + i];
+    const float ia = ar[i];
+    const int jend = (n - 64 * jc) < 64 ? (n - 64 * jc) : 64;
+    for (int jj = 0; jj < jend; ++jj) {
+        if (64 * jc + jj <= i) continue;
+        const float xx0 = fmaxf(ix0, cb[0][jj]), yy0 = fmaxf(iy0, cb[1][jj]);
+        const float xx1 = fminf(ix1, cb[2][jj]), yy1 = fminf(iy1, cb[3][jj]);
+        const float ww = fmaxf(0.f, xx1 - xx0), hh = fmaxf(0.f, yy1 - yy0);
+        const float inter = ww * hh;
+        const float ovr = inter / (ia + cb[4][jj] - inter);
+        if (ovr > thr) bits |= (1ull << jj);
+    }
+    S.mask[((size_t)b * C4_NMS_MAX + i) * C4_NMS_WORDS + jc] = bits;
+}
+
+// Greedy scan, one block per image.  Wave 0 resolves the 64 rows of a chunk on the diagonal word; then the waves OR the kept
+// rows' words right of the diagonal into the removed bitmap.  The scan ends as soon as `post` rows are kept: the kept list is in
+// processing order, so that is keep[:post] of the full scan.  Output: proposals [B][post] (boxes, scores, entry = rank in the
+// decoded list; zeros and -1 past the count) and the per-image count.
+__global__ __launch_bounds__(1024) void c4_nms_scan(C4Nms S, const float* __restrict__ dboxes, const float* __restrict__ dscores,
+                                                   int pre, int post, float* __restrict__ out_boxes, float* __restrict__ out_scores,
+                                                   int* __restrict__ out_entry, int* __restrict__ out_count) {
+    __shared__ uint64_t removed[C4_NMS_WORDS];
+    __shared__ uint64_t keepbits_s;
+    __shared__ int kept_s;
+    __shared__ int keep[1024];
+    const int b = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int n = S.n[b];
+    const int nw = (n + 63) >> 6;
+    const uint64_t* gm = S.mask + (size_t)b * C4_NMS_MAX * C4_NMS_WORDS;
+    const int* entry = S.entry + (size_t)b * C4_NMS_MAX;
+    for (int i = tid; i < C4_NMS_WORDS; i += 1024) removed[i] = 0ull;
+    if (tid == 0) kept_s = 0;
+    __syncthreads();
+    int kept = 0;                                   // wave 0's running count
+    for (int ch = 0; ch < nw; ++ch) {
+        const int rows_here = (n - 64 * ch) < 64 ? (n - 64 * ch) : 64;
+        if (wave == 0) {
+            const int row = 64 * ch + lane;
+            const uint64_t diag = row < n ? gm[(size_t)row * C4_NMS_WORDS + ch] : 0ull;
+            uint64_t rem = removed[ch];
+            uint64_t keepbits = 0;
+            uint64_t alive = ~rem & (rows_here == 64 ? ~0ull : ((1ull << rows_here) - 1ull));
+            while (alive) {
+                const int r = __builtin_ctzll(alive);
+                keepbits |= (1ull << r);
+                rem |= readlane64(diag, r) | (1ull << r);
+                alive &= ~rem;
+            }
+            const int pos = kept + __popcll(keepbits & ((1ull << lane) - 1ull));
+            if (((keepbits >> lane) & 1ull) && pos < post) keep[pos] = entry[row];
+            kept += __popcll(keepbits);
+            if (lane == 0) { keepbits_s = keepbits; kept_s = kept; }
+        }
+        __syncthreads();
+        if (kept_s >= post) break;                  // block-uniform
+        const uint64_t kb = keepbits_s;
+        for (int w = ch + 1 + wave; w < nw; w += 16) {
+            uint64_t v = 0;
+            if (lane < rows_here && ((kb >> lane) & 1ull)) v = gm[(size_t)(64 * ch + lane) * C4_NMS_WORDS + w];
+            v = wave_or64(v);
+            if (lane == 0) removed[w] |= v;
+        }
+        __syncthreads();
+    }
+    const int cnt = kept_s < post ? kept_s : post;
+    dboxes += (size_t)b * pre * 4;
+    dscores += (size_t)b * pre;
+    for (int i = tid; i < post; i += 1024) {
+        float* ob = out_boxes + ((size_t)b * post + i) * 4;
+        if (i < cnt) {
+            const int e = keep[i];
+            ob[0] = dboxes[e * 4 + 0]; ob[1] = dboxes[e * 4 + 1]; ob[2] = dboxes[e * 4 + 2]; ob[3] = dboxes[e * 4 + 3];
+            out_scores[(size_t)b * post + i] = dscores[e];
+            out_entry[(size_t)b * post + i] = e;
+        } else {
+            ob[0] = ob[1] = ob[2] = ob[3] = 0.f;
+            out_scores[(size_t)b * post + i] = 0.f;
+            out_entry[(size_t)b * post + i] = -1;
+        }
+    }
+    if (tid == 0) out_count[b] = cnt;
+}
+
 // Pack per-image detections into one dense list (image id kept per entry) so the mask tail's
 // GEMMs see a contiguous M.  det_* are [B][Kd]; packed_* are [B*Kd].
 __global__ void pack_detections(const float* __restrict__ det_boxes, const float* __restrict__ det_scores,
@@ -771,6 +1006,38 @@ int apse_k_nms_lists(const float* boxes, const float* scores, int n_total, const
                        ncat);
     hipLaunchKernelGGL(nms_matrix, dim3(16, 16, ncat * B), dim3(64), 0, s, S, thr);
     hipLaunchKernelGGL(nms_scan, dim3(ncat, B), dim3(1024), NMS_MAX * 16 * 8, s, S, keep_idx, keep_cnt);
+    return hipGetLastError() == hipSuccess ? APSE_OK : APSE_E_HIP;
+}
+size_t apse_c4_nms_scratch_bytes(int B) {
+    return (size_t)B * ((size_t)C4_NMS_MAX * C4_NMS_WORDS * 8 + (size_t)C4_NMS_MAX * 4 * 4 + (size_t)C4_NMS_MAX * 4 * 2 + 16);
+}
+static C4Nms c4_carve(void* scratch, int B) {
+    C4Nms S;
+    char* p = reinterpret_cast<char*>(scratch);
+    S.mask = reinterpret_cast<uint64_t*>(p); p += (size_t)B * C4_NMS_MAX * C4_NMS_WORDS * 8;
+    S.box = reinterpret_cast<float*>(p); p += (size_t)B * 4 * C4_NMS_MAX * 4;
+    S.area = reinterpret_cast<float*>(p); p += (size_t)B * C4_NMS_MAX * 4;
+    S.entry = reinterpret_cast<int*>(p); p += (size_t)B * C4_NMS_MAX * 4;
+    S.n = reinterpret_cast<int*>(p);
+    return S;
+}
+// C4 proposals: select + decode (dec_* [B][pre]), long NMS, keep[:post] -> props [B][post], counts.  pre <= 6000, post <= 1000.
+int apse_k_c4_rpn(const C4Rpn* R, int pre, int post, float img_h, float img_w, float scale_clamp, float thr, float* dec_boxes,
+                  float* dec_scores, int* dec_valid, void* scratch, float* props, float* prop_scores, int* prop_entry,
+                  int* prop_count, int B, hipStream_t s) {
+    if (pre < 1 || pre > 6000 || R->k > pre || post < 1 || post > 1000) return APSE_E_INVALID;
+    static bool done = false;
+    const size_t lds = (size_t)C4_SORT_N * 8 + 16 * 256 * 4;
+    if (!done) {
+        hipFuncSetAttribute(reinterpret_cast<const void*>(&c4_rpn_select), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+        done = true;
+    }
+    hipLaunchKernelGGL(c4_rpn_select, dim3(B), dim3(1024), lds, s, *R, img_h, img_w, scale_clamp, dec_boxes, dec_scores, dec_valid, pre);
+    C4Nms S = c4_carve(scratch, B);
+    hipLaunchKernelGGL(c4_nms_prepare, dim3(B), dim3(1024), 0, s, dec_boxes, dec_valid, pre, S);
+    hipLaunchKernelGGL(c4_nms_matrix, dim3(C4_NMS_WORDS, C4_NMS_WORDS, B), dim3(64), 0, s, S, thr);
+    hipLaunchKernelGGL(c4_nms_scan, dim3(B), dim3(1024), 0, s, S, dec_boxes, dec_scores, pre, post, props, prop_scores, prop_entry,
+                       prop_count);
     return hipGetLastError() == hipSuccess ? APSE_OK : APSE_E_HIP;
 }
 int apse_k_pack_detections(const float* det_boxes, const float* det_scores, const int* det_entry, const int* det_cnt, int B,

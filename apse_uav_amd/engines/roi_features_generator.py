@@ -19,6 +19,7 @@ import numpy as np
 import torch
 
 from .. import _lib
+from ..config import is_c4
 from ..networks.track_rcnn import TrackRCNN
 from ..utils import rle
 from ..weights import load_detector_file, synthetic_detector_state, blocks_from_state
@@ -26,6 +27,8 @@ from ..weights import load_detector_file, synthetic_detector_state, blocks_from_
 
 class RoiFeaturesGenerator:
     def __init__(self, config, roi_size=8, state_dict=None):
+        if is_c4(config):
+            raise NotImplementedError("RoiFeaturesGenerator reads the FPN level p2: not available for C4 (Res5ROIHeads) models")
         self.device = torch.device(config.MODEL.DEVICE)
         self.roi_size = roi_size
         self.in_features = config.MODEL.ROI_HEADS.IN_FEATURES

@@ -15,7 +15,8 @@ from .. import _lib
 from ..structures.instances import Boxes, Instances
 from ..structures.window_mask import MaskList, WindowMask
 from ..utils import resample
-from ..weights import blocks_from_state
+from ..config import check_c4_supported, is_c4
+from ..weights import blocks_from_state, is_c4_state
 
 
 class _Shape:
@@ -24,27 +25,44 @@ class _Shape:
 
 
 class _Backbone:
-    """``model.backbone.output_shape()`` as read by rcnn_tracker.py:53."""
-    size_divisibility = 32
+    """``model.backbone.output_shape()`` as read by rcnn_tracker.py:53.  FPN: p2..p6, padded to /32; C4 (Res5ROIHeads):
+    res4 only, unpadded (detectron2's ResNet backbone has size_divisibility 0)."""
+
+    def __init__(self, c4=False):
+        self.c4 = c4
+        self.size_divisibility = 0 if c4 else 32
 
     def output_shape(self):
+        if self.c4:
+            return {"res4": _Shape(1024, 16)}
         return {"p%d" % l: _Shape(256, 2 ** l) for l in range(2, 7)}
 
 
+def c4_res4_size(image_h, image_w):
+    """res4 of the unpadded C4 trunk: the stem (7x7 / 2, pad 3), the max-pool (3x3 / 2, pad 1) and the stride-2 1x1 of res3
+    and res4 each map n -> (n - 1) // 2 + 1."""
+    h, w = image_h, image_w
+    for _ in range(4):
+        h, w = (h - 1) // 2 + 1, (w - 1) // 2 + 1
+    return h, w
+
+
 class LazyFeatures(dict):
-    """{"p2".."p6": NCHW f32 CUDA tensor}, exported from the context on first access."""
+    """{"p2".."p6"} (C4: {"res4"}): NCHW f32 CUDA tensors, exported from the context on first access."""
 
     def __init__(self, model, batch):
         super().__init__()
         self._model, self._batch = model, batch
 
     def __missing__(self, key):
+        if self._model.backbone.c4 and key not in self.keys():
+            raise KeyError(key)                # C4 exports res4 only (FPN models still export res2..res5 / stem on demand)
         t = self._model.export_feature(key, self._batch)
         self[key] = t
         return t
 
     def keys(self):
-        return ["p2", "p3", "p4", "p5", "p6"]
+        return ["res4"] if self._model.backbone.c4 else ["p2", "p3", "p4", "p5", "p6"]
 
 
 class FrameResults:
@@ -93,7 +111,10 @@ class TrackRCNN:
     def __init__(self, cfg):
         self.cfg = cfg
         self.device = torch.device(cfg.MODEL.DEVICE)
-        self.backbone = _Backbone()
+        self.c4 = is_c4(cfg)
+        if self.c4:
+            check_c4_supported(cfg)
+        self.backbone = _Backbone(self.c4)
         self.training = False
         self._state = None
         self._assoc = None
@@ -165,10 +186,14 @@ class TrackRCNN:
             raise _lib.ApseError("the apse_uav hot path needs a ROCm GPU (cfg.MODEL.DEVICE=%s): no CPU fallback" % self.device)
         if self._state is None:
             raise _lib.ApseError("no detector weights loaded")
+        if is_c4_state(self._state) != self.c4:
+            raise _lib.ApseError("the detector weights are a %s checkpoint but the config is %s (MODEL.ROI_HEADS.NAME = %s)"
+                                 % ("C4" if is_c4_state(self._state) else "FPN", "C4" if self.c4 else "FPN",
+                                    self.cfg.MODEL.ROI_HEADS.NAME))
         lib = _lib.load()
         cfg = self.cfg
-        c = _lib.Config()
-        c.struct_size = C.sizeof(_lib.Config)
+        c = _lib.ConfigArch()
+        c.struct_size = C.sizeof(_lib.ConfigArch)
         c.device = self.device.index if self.device.index is not None else torch.cuda.current_device()
         c.max_batch = int(cfg.APSE.MAX_BATCH)
         c.frame_h, c.frame_w = int(frame_hw[0]), int(frame_hw[1])
@@ -192,6 +217,12 @@ class TrackRCNN:
         ph = (c.image_h + 31) // 32 * 32
         pw = (c.image_w + 31) // 32 * 32
         c.assoc_scale = (pw // 4) / float(c.frame_w)          # features.size()[3] / image_size[1]  (rcnn_tracker.py:165)
+        depth = 256
+        c.arch = 0
+        if self.c4:
+            c.arch = 1
+            depth = 1024
+            c.assoc_scale = c4_res4_size(c.image_h, c.image_w)[1] / float(c.frame_w)
         c.compute_dtype = {"f32": 0, "bf16": 1, "f16": 2, "fp16": 2}[str(cfg.APSE.DTYPE)]
         c.storage16 = int(bool(cfg.APSE.get("STORAGE16", True))) if c.compute_dtype else 0
         ctx = C.c_void_p()
@@ -202,7 +233,7 @@ class TrackRCNN:
                 sd["association.fc.weight"] = self._assoc.fc.weight
                 sd["association.fc.bias"] = self._assoc.fc.bias
             else:
-                sd["association.fc.weight"] = torch.zeros(c.embed_dim, 256 * roi * roi)
+                sd["association.fc.weight"] = torch.zeros(c.embed_dim, depth * roi * roi)
                 sd["association.fc.bias"] = torch.zeros(c.embed_dim)
             for name, t in sd.items():
                 if name.startswith("proposal_generator.anchor_generator") or name in ("pixel_mean", "pixel_std"):

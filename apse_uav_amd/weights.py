@@ -91,6 +91,56 @@ def synthetic_detector_state(seed=0, blocks=R101_BLOCKS, num_classes=4, bg_bias=
     return sd
 
 
+R50_C4_BLOCKS = (3, 4, 6, 3)
+R101_C4_BLOCKS = (3, 4, 23, 3)
+
+
+def synthetic_c4_state(seed=0, blocks=R101_C4_BLOCKS, num_classes=4, bg_bias=0.0, cls_gain=1.0, cls_bias=None):
+    """Seeded random weights with detectron2's C4 Mask R-CNN key names and shapes (Base-RCNN-C4: ``backbone.stem``,
+    ``backbone.res{2,3,4}.N``, ``roi_heads.res5.N``, a 1024-channel RPN with 15 anchors, ``roi_heads.mask_head.deconv`` /
+    ``predictor`` and no mask convolutions).  ``blocks`` = (res2, res3, res4, res5).  Same calibration idea as
+    ``synthetic_detector_state``: small gamma on each block's last norm keeps activations O(1) through the residual stages,
+    and ``cls_bias`` / ``bg_bias`` move the class logits so a handful of ROIs pass the score threshold."""
+    g = torch.Generator().manual_seed(seed)
+    sd = {}
+    _conv(sd, "backbone.stem.conv1", 64, 3, 7, g)
+    sd["backbone.stem.conv1.weight"] *= 1.0 / 60.0
+    _bn(sd, "backbone.stem.conv1.norm", 64, g)
+    cin = 64
+    for si, nblk in enumerate(blocks):
+        mid = 64 * (2 ** si)
+        cout = 4 * mid
+        for bi in range(nblk):
+            p = ("backbone.res%d.%d" % (si + 2, bi)) if si < 3 else ("roi_heads.res5.%d" % bi)
+            if bi == 0:
+                _conv(sd, p + ".shortcut", cout, cin, 1, g, gain=1.0)
+                _bn(sd, p + ".shortcut.norm", cout, g, 0.7, 1.0)
+            _conv(sd, p + ".conv1", mid, cin, 1, g)
+            _bn(sd, p + ".conv1.norm", mid, g)
+            _conv(sd, p + ".conv2", mid, mid, 3, g)
+            _bn(sd, p + ".conv2.norm", mid, g)
+            _conv(sd, p + ".conv3", cout, mid, 1, g)
+            _bn(sd, p + ".conv3.norm", cout, g, 0.1, 0.3)
+            cin = cout
+    _conv(sd, "proposal_generator.rpn_head.conv", 1024, 1024, 3, g, bias=True)
+    _conv(sd, "proposal_generator.rpn_head.objectness_logits", 15, 1024, 1, g, gain=1.0, bias=True)
+    _conv(sd, "proposal_generator.rpn_head.anchor_deltas", 60, 1024, 1, g, gain=0.05, bias=True)
+    _fc(sd, "roi_heads.box_predictor.cls_score", num_classes + 1, 2048, g, gain=cls_gain)
+    sd["roi_heads.box_predictor.cls_score.bias"][num_classes] += bg_bias
+    if cls_bias is not None:
+        sd["roi_heads.box_predictor.cls_score.bias"] += torch.tensor(cls_bias, dtype=torch.float32)
+    _fc(sd, "roi_heads.box_predictor.bbox_pred", num_classes * 4, 2048, g, gain=0.5)
+    sd["roi_heads.mask_head.deconv.weight"] = torch.randn(2048, 256, 2, 2, generator=g) * math.sqrt(2.0 / 2048)
+    sd["roi_heads.mask_head.deconv.bias"] = torch.randn(256, generator=g) * 0.01
+    _conv(sd, "roi_heads.mask_head.predictor", num_classes, 256, 1, g, gain=4.0, bias=True)
+    return sd
+
+
+def is_c4_state(sd):
+    """A C4 checkpoint: the trunk under ``backbone.res*`` (no ``bottom_up``) and res5 under ``roi_heads.res5``."""
+    return "backbone.stem.conv1.weight" in sd and "backbone.bottom_up.stem.conv1.weight" not in sd
+
+
 def synthetic_association_state(seed=1, roi_size=10, depth=256, dim=128):
     g = torch.Generator().manual_seed(seed)
     n = depth * roi_size * roi_size
@@ -99,10 +149,14 @@ def synthetic_association_state(seed=1, roi_size=10, depth=256, dim=128):
 
 
 def blocks_from_state(sd):
+    """Bottlenecks per stage (res2..res5).  C4 checkpoints: res2..res4 under ``backbone.``, res5 under ``roi_heads.res5``."""
+    c4 = is_c4_state(sd)
     blocks = []
     for s in (2, 3, 4, 5):
+        fmt = ("roi_heads.res5.%d.conv1.weight" if s == 5 else "backbone.res%d.%%d.conv1.weight" % s) if c4 else \
+            "backbone.bottom_up.res%d.%%d.conv1.weight" % s
         n = 0
-        while ("backbone.bottom_up.res%d.%d.conv1.weight" % (s, n)) in sd:
+        while (fmt % n) in sd:
             n += 1
         blocks.append(n)
     return tuple(blocks)

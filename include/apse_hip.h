@@ -49,8 +49,18 @@ typedef struct apse_ctx apse_ctx;
  *   rpn_post_topk * min(num_classes, ceil(1 / score_thresh) - 1) < 40000: fewer than 1 / score_thresh classes of a ROI can score
  *       above score_thresh, so this bounds the box candidates of an image below the count at which detectron2 0.1.2's
  *       batched_nms switches to a method without the category offset (COCO's 1000 x 19 = 19000 passes; 0.01 at 80 classes does not);
- *   rpn_pre_topk, rpn_post_topk <= 1000; embed_dim <= 256; compute_dtype 1 / 2 needs storage16 = 1. */
+ *   rpn_pre_topk, rpn_post_topk <= 1000; embed_dim <= 256; compute_dtype 1 / 2 needs storage16 = 1.
+ * C4 (arch = 1, detectron2 Base-RCNN-C4 / Res5ROIHeads) instead:
+ *   rpn_pre_topk <= APSE_C4_MAX_PRE_TOPK (6000, detectron2's C4 PRE_NMS_TOPK_TEST; one single-level list per image);
+ *   compute_dtype 0 (exact f32 only);
+ *   max_batch <= APSE_C4_MAX_BATCH (2): the res5 stage runs on every box ROI, and its pooled input alone is
+ *       rpn_post_topk x 14 x 14 x 1024 f32 = 0.8 GB per frame (about 2.5 GB of activations per frame in all); two frames
+ *       keep every activation tensor below 2^31 bytes, the byte range the implicit-GEMM kernels address;
+ *   the image is not padded (size_divisibility 0), blocks[3] = the roi_heads.res5 block count, and assoc_scale is the
+ *       res4 width over the frame width. */
 #define APSE_MAX_CLASSES 80
+#define APSE_C4_MAX_PRE_TOPK 6000
+#define APSE_C4_MAX_BATCH 2
 #define APSE_MAX_FRAME_W 49152
 #define APSE_MAX_FRAME_H 32768
 typedef struct apse_config {
@@ -59,7 +69,7 @@ typedef struct apse_config {
     int max_batch;                /* frames per forward (reference: 1), 1..64 */
     int frame_h, frame_w;         /* original frame, e.g. 2160 x 3840 or 375 x 1242; any size within the limits above */
     int image_h, image_w;         /* after ResizeShortestEdge, e.g. 750 x 1333 */
-    int blocks[4];                /* bottlenecks per stage, R-101 = 3,4,23,3 */
+    int blocks[4];                /* bottlenecks per stage, R-101 = 3,4,23,3 (C4: blocks[3] = roi_heads.res5 blocks) */
     int num_classes;              /* 4 (1..APSE_MAX_CLASSES = 80) */
     float score_thresh;           /* 0.5 */
     float box_nms;                /* 0.5 */
@@ -71,12 +81,16 @@ typedef struct apse_config {
     float pixel_mean[3];          /* BGR means */
     int assoc_roi;                /* 10 */
     int embed_dim;                /* 128 */
-    float assoc_scale;            /* roi_pool spatial scale = p2 width / frame width (rcnn_tracker.py:165) */
+    float assoc_scale;            /* roi_pool spatial scale = p2 width / frame width (rcnn_tracker.py:165); C4: res4 width */
     int compute_dtype;            /* 0 = exact f32 MFMA everywhere (reference numerics); 1 = bf16, 2 = f16 matrix cores with
                                      f32 accumulate for the trunk / head GEMMs (decision layers stay f32) */
     int storage16;                /* with compute_dtype 1/2: must be 1 = activations live in HBM in the 16-bit operand type (half
                                      the traffic, no conversion on the way to the matrix cores).  The f32-storage variant of
                                      the 16-bit modes was removed in round 4 (apse_create refuses it); ignored for f32 */
+    int arch;                     /* 0 = FPN + StandardROIHeads (Base-RCNN-FPN); 1 = C4 + Res5ROIHeads (Base-RCNN-C4): stem and
+                                     res2..res4 (keys backbone.stem.*, backbone.res{2,3,4}.N.*), the RPN on res4 with 15 anchors,
+                                     roi_heads.res5 on 14 x 14 ROIAlign crops of res4, 14 x 14 masks, association on res4.  A
+                                     caller passing the struct_size of the layout without this field gets 0 */
 } apse_config;
 
 /* Byte offsets of the per-forward results block (one D2H copy, apse_read_results). n = max_batch*dets_per_image. */
@@ -133,7 +147,7 @@ int apse_set_camera(apse_ctx* ctx, const double* m9, const double* dist, int ndi
 int apse_preprocess_frames(apse_ctx* ctx, const uint8_t* frames_dev, int batch, void* stream);
 /* Same from already-resized f32 CHW images [B][3][image_h][image_w] (the reference's model input). */
 int apse_preprocess_images(apse_ctx* ctx, const float* images_dev, int batch, void* stream);
-/* ResNet-101 + FPN (track_rcnn.py:42). */
+/* ResNet-101 + FPN (track_rcnn.py:42); C4: stem + res2..res4. */
 int apse_backbone(apse_ctx* ctx, int batch, void* stream);
 /* RPN head + proposal selection (track_rcnn.py:46). */
 int apse_rpn(apse_ctx* ctx, int batch, void* stream);
@@ -153,7 +167,7 @@ int apse_set_detections(apse_ctx* ctx, const float* boxes_host, const int* class
 int apse_mask_tail(apse_ctx* ctx, int batch, void* stream);
 /* roi_pool(p2) + AssociationHead (rcnn_tracker.py:156-189, association_head.py:16-27). */
 int apse_embed(apse_ctx* ctx, int batch, void* stream);
-/* RoiFeaturesGenerator.get_rois_features (dcnn/engines/roi_features_generator.py:68-117), to be called after
+/* RoiFeaturesGenerator.get_rois_features (dcnn/engines/roi_features_generator.py:68-117; FPN only), to be called after
  * apse_backbone: RoI features of image `image` of the batch on p2 for the association-head training batches.
  * rois_dev: [n][4] x1,y1,x2,y2 in ORIGINAL-frame pixels.  masks_dev == NULL: torchvision roi_pool (:113);
  * else [n][frame_h][frame_w] u8 (non-zero = inside): p2 * bilinear-resized mask, then roi_align(aligned=False,
@@ -183,7 +197,7 @@ int apse_copy_mask_window(apse_ctx* ctx, int det, int x0, int y0, int x1, int y1
  * (y1 - y0) rows of ((x1 + 63) >> 6) - (x0 >> 6) words at dst_dev + dst_word_offsets[k].  Host arrays, read before the call returns. */
 int apse_copy_mask_windows(apse_ctx* ctx, int n, const int* dets_host, const int* rects_host, uint64_t* dst_dev,
                            const long long* dst_word_offsets_host, void* stream);
-/* Named internal tensor -> caller buffer as NCHW f32 (p2..p6, res2..res5, stem): the feature dict
+/* Named internal tensor -> caller buffer as NCHW f32 (p2..p6, res2..res5, stem; C4: res2..res4, stem): the feature dict
  * TrackRCNN.inference returns (track_rcnn.py:57-58).  dims (B,C,H,W) via apse_feature_shape. */
 int apse_feature_shape(apse_ctx* ctx, const char* name, int* chw3);
 int apse_export_feature(apse_ctx* ctx, const char* name, float* dst_nchw_dev, int batch, void* stream);
