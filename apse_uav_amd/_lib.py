@@ -54,6 +54,16 @@ class RenderItem(C.Structure):
                 ("box", C.c_float * 4), ("rgb", C.c_uint8 * 4), ("label_off", C.c_int), ("label_len", C.c_int)]
 
 
+class MotsWindow(C.Structure):
+    """apse_mots_window (include/apse_hip.h)."""
+    _fields_ = [("rect", C.c_int * 4), ("words_per_row", C.c_int), ("area", C.c_int), ("bits", C.c_void_p)]
+
+
+class MotsObject(C.Structure):
+    """apse_mots_object (include/apse_hip.h)."""
+    _fields_ = [("rect", C.c_int * 4), ("words_per_row", C.c_int), ("score", C.c_float), ("bits", C.c_void_p)]
+
+
 class ConvDesc(C.Structure):
     _fields_ = [(k, C.c_int) for k in ("B", "H", "W", "Cin", "Cout", "KH", "KW", "stride", "pad", "relu", "res_mode",
                                        "cfg", "splitk", "prec", "fuse_reduce", "x_st", "res_st", "y_st")]
@@ -134,6 +144,11 @@ def load():
         "apse_render_instances": ([vp, vp, i, i, i, i, vp, i, vp, sz, vp, i, vp, sz, vp], i),
         "apse_render_pack_mask": ([vp, i, i, vp, vp], i),
         "apse_render_font_host": ([vp, sz], sz),
+        "apse_mots_split_workspace_bytes": ([], sz),
+        "apse_mots_split_idmap": ([vp, i, i, i, vp, sz, vp, vp, vp, vp, sz, vp], i),
+        "apse_mots_rle_to_bits": ([vp, vp, i, i, i, vp, vp], i),
+        "apse_mots_overlaps": ([vp, i, vp, i, vp, i, vp, vp], i),
+        "apse_mots_render_idmap": ([vp, vp, i, i, i, vp, vp], i),
         "apse_resize_normalize": ([vp, vp, vp, vp, vp, vp, i, vp, vp, i, i, i, i, i, i, i, i, C.POINTER(f * 3), vp], i),
     }
     for name, (args, ret) in sig.items():
@@ -152,7 +167,8 @@ EXPORTS = ["apse_create", "apse_destroy", "apse_last_error", "apse_version", "ap
            "apse_maxpool3x3s2_typed", "apse_roi_align", "apse_roi_align_typed", "apse_roi_pool", "apse_roi_features", "apse_nms_rank", "apse_mask_centroid_dense", "apse_mask_closest_dense",
            "apse_l2_normalize", "apse_sqdist", "apse_undistort_gamma", "apse_lab_tables_host", "apse_resize_normalize", "apse_replay_create", "apse_replay_destroy",
            "apse_replay_step", "apse_replay_packed", "apse_replay_max_id", "apse_replay_next_id", "apse_render_workspace_bytes",
-           "apse_render_instances", "apse_render_pack_mask", "apse_render_font_host"]
+           "apse_render_instances", "apse_render_pack_mask", "apse_render_font_host", "apse_mots_split_workspace_bytes",
+           "apse_mots_split_idmap", "apse_mots_rle_to_bits", "apse_mots_overlaps", "apse_mots_render_idmap"]
 
 
 def stream_ptr():

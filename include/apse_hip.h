@@ -331,6 +331,55 @@ int apse_render_pack_mask(const uint8_t* mask_dev, int H, int W, uint64_t* words
  * (665); writes it to `out` when cap is large enough. */
 size_t apse_render_font_host(uint8_t* out, size_t cap);
 
+/* ---- MOTS evaluation (csrc/mots.hip): the mask arithmetic of mots_tools/mots_eval (pycocotools area / iou / merge over the
+ * KITTI MOTS id maps and RLE files) on bit windows, and the id map of utils/mots_evaluation.py (crop_overlapping_masks +
+ * result_image_from_objects) straight from the tracker's masks.  Stateless: no context, enqueues on `stream` only, no allocation,
+ * no synchronisation.  Every count is an exact integer (integer atomics only), so results are bit-reproducible.
+ * A window is the WindowMask layout: rect x0, y0, x1, y1 (frame pixels, half-open), (y1 - y0) rows of words_per_row 64-bit words,
+ * word 0 holds pixels (x0 >> 6) << 6 .. +63, bit i = pixel + i.  Bits outside the rect are ignored on input and 0 on output, so
+ * two windows of one frame are aligned on absolute 64-pixel columns.
+ * Limits (APSE_E_INVALID outside them): frames 1 <= H <= APSE_MAX_FRAME_H, 1 <= W <= APSE_MAX_FRAME_W; id maps u16; at most
+ * APSE_MOTS_MAX_OBJECTS values per split and objects per render or RLE call; at most APSE_MOTS_MAX_PAIRS pairs and
+ * APSE_MOTS_MAX_UNION union members per overlaps call.  KITTI MOTS frames hold tens of objects. */
+#define APSE_MOTS_MAX_OBJECTS 1024
+#define APSE_MOTS_MAX_PAIRS 65536
+#define APSE_MOTS_MAX_UNION 1024
+typedef struct apse_mots_window {
+    int rect[4];                  /* x0, y0, x1, y1; x0 >= x1 or y0 >= y1: empty */
+    int words_per_row;            /* (((x1 + 63) >> 6) - (x0 >> 6)) for the windows this file writes */
+    int area;                     /* set pixels (written by apse_mots_split_idmap; informational elsewhere) */
+    uint64_t* bits;               /* device, (y1 - y0) * words_per_row words */
+} apse_mots_window;
+typedef struct apse_mots_object {
+    int rect[4];                  /* mask window, as apse_mots_window */
+    int words_per_row;
+    float score;                  /* owner rule: highest score, ties to the highest index */
+    const uint64_t* bits;         /* device; NULL: no pixels */
+} apse_mots_object;
+/* Workspace bytes of apse_mots_split_idmap. */
+size_t apse_mots_split_workspace_bytes(void);
+/* u16 id map [H][W] (device) -> its distinct non-zero values in ascending order (np.unique order) in values[k], each with its
+ * bounding-box window in windows[k] (rect, words_per_row, area, bits = pool + a packed offset) for k < min(n, max_values).
+ * info[0] = n, info[1] = pool words the windows need, info[2] = 1 when the bits were written (n <= max_values and info[1] <=
+ * pool_words), 0 otherwise: the caller reads info after the stream and retries with more room.  1 <= max_values <=
+ * APSE_MOTS_MAX_OBJECTS.  ws [ws_bytes >= apse_mots_split_workspace_bytes()] is scratch. */
+int apse_mots_split_idmap(const uint16_t* idmap, int H, int W, int max_values, uint64_t* pool, size_t pool_words, int* values,
+                          apse_mots_window* windows, int* info, void* ws, size_t ws_bytes, void* stream);
+/* COCO RLE -> window bits.  Object k's runs are ends[ends_off[k] .. ends_off[k + 1]), the running sums of its counts (column-major
+ * over an h x w image, first run = zeros); windows[k] (device: rect, words_per_row, bits) is its window, which must contain every
+ * set pixel (the host takes the bounding box from the runs).  Every word of each window is written. */
+int apse_mots_rle_to_bits(const int* ends, const int* ends_off, int n, int h, int w, const apse_mots_window* windows,
+                          void* stream);
+/* out[p] = {|a & b|, |a|, |b|} for pairs[p] = {a, b} over windows[0 .. n_windows).  b = -1: b is the union of the windows
+ * union_idx[0 .. n_union) (an empty list is the empty region), and out[p][2] = -1. */
+int apse_mots_overlaps(const apse_mots_window* windows, int n_windows, const int* pairs, int npairs, const int* union_idx,
+                       int n_union, int* out, void* stream);
+/* Tracked objects -> u16 id map [H][W] (device): every pixel belongs to the object of highest score among those whose mask holds
+ * it (ties: highest index) and takes values_host[owner] (0: a class MOTS does not score), 0 where no mask is set.  Equal to
+ * result_image_from_objects(crop_overlapping_masks(objects)).  objects: device [n]; values_host: host [n], 0..65535. */
+int apse_mots_render_idmap(const apse_mots_object* objects, const int* values_host, int n, int H, int W, uint16_t* idmap,
+                           void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -1,0 +1,87 @@
+#!/usr/bin/env python3
+"""Track the sequences of a KITTI MOTS seqmap and write or score the results: the --mots_evaluation mode of the reference's
+standard_rcnn_tracker_test.py.
+
+    python tools/track_mots.py SEQMAP --images IMAGE_DIR [--output DIR] [--eval GT_DIR] [--no-write]
+                               [--detector-state FILE] [--association-state FILE]
+
+IMAGE_DIR holds one folder of PNG / JPEG / BMP frames per sequence (datasets/data_tracking_image_2/training/image_02 in the
+reference); frames are read with Pillow.  For every frame the tracker's objects become the u16 id map of
+result_image_from_objects(crop_overlapping_masks(objects)), rendered on the device, written as DIR/SEQ/000000.png, ...
+(default output/evaluation_results, as the reference).  --eval GT_DIR scores the tracker online against the ground truth
+(utils/mots_eval.MotsEvaluator) and prints eval.py's tables; --no-write skips the PNGs.  Without state files the tracker runs
+on the seeded synthetic weights (apse_uav_amd.weights), which exercises the pipeline but detects nothing meaningful.
+"""
+import argparse
+import os
+import sys
+
+import numpy as np
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+
+EXTENSIONS = ("jpg", "jpeg", "png", "bmp")
+
+
+def image_files(path):
+    return [f for f in sorted(os.listdir(path)) if f.split(".")[-1].lower() in EXTENSIONS]
+
+
+def main(argv=None):
+    ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
+    ap.add_argument("seqmap")
+    ap.add_argument("--images", required=True, help="folder of per-sequence image folders")
+    ap.add_argument("--output", default="output/evaluation_results")
+    ap.add_argument("--eval", default="", help="ground-truth folder: score online")
+    ap.add_argument("--no-write", action="store_true")
+    ap.add_argument("--detector-state", default="", help="torch.load-able detector state dict")
+    ap.add_argument("--association-state", default="", help="torch.load-able association head state dict")
+    args = ap.parse_args(argv)
+    import torch
+    from PIL import Image
+    if not torch.cuda.is_available():
+        sys.exit("track_mots.py: no GPU visible (the tracker has no CPU fallback)")
+    from apse_uav_amd.config import setup_cfg
+    from apse_uav_amd.engines.rcnn_tracker import RcnnTracker
+    from apse_uav_amd.utils.mots_eval import MotsEvaluator, render_idmap
+    from apse_uav_amd.utils.mots_evaluation import parse_mots_seqmap
+    from apse_uav_amd.weights import synthetic_association_state, synthetic_detector_state
+    det = torch.load(args.detector_state) if args.detector_state else synthetic_detector_state(0)
+    assoc = torch.load(args.association_state) if args.association_state else synthetic_association_state(1)
+    sequences, _ = parse_mots_seqmap(args.seqmap)
+    print("Running evaluation for sequences:")
+    for s in sequences:
+        print(s)
+    evaluator = MotsEvaluator(args.eval, args.seqmap) if args.eval else None
+    for seq in sequences:
+        seq_path = os.path.join(args.images, seq)
+        names = image_files(seq_path)
+        first = np.asarray(Image.open(os.path.join(seq_path, names[0])).convert("RGB"))
+        size = first.shape[:2]
+        tracker = RcnnTracker(setup_cfg(), size, assoc, detector_state=det)
+        out_dir = os.path.join(args.output, seq)
+        if not args.no_write:
+            os.makedirs(out_dir, exist_ok=True)
+        if evaluator is not None:
+            evaluator.begin_sequence(seq)
+        print("\nEvaluating sequence: ", seq)
+        for name in names:
+            print(name, end="\r")
+            frame = np.ascontiguousarray(np.asarray(Image.open(os.path.join(seq_path, name)).convert("RGB"))[:, :, ::-1])
+            objects = tracker.next_frame(frame)                  # BGR, as cv2.imread gives the reference
+            frame_idx = tracker.frame_count - 1
+            if evaluator is not None:
+                evaluator.add_frame(frame_idx, objects, size)
+            if not args.no_write:
+                img = render_idmap(objects, size).cpu().numpy()
+                Image.fromarray(img).save(os.path.join(out_dir, "%06d.png" % frame_idx))
+        if evaluator is not None:
+            evaluator.end_sequence()
+    if evaluator is not None:
+        print()
+        evaluator.finish(out=print)
+
+
+if __name__ == "__main__":
+    main()
