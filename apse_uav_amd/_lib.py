@@ -150,6 +150,15 @@ def load():
         "apse_mots_overlaps": ([vp, i, vp, i, vp, i, vp, vp], i),
         "apse_mots_render_idmap": ([vp, vp, i, i, i, vp, vp], i),
         "apse_resize_normalize": ([vp, vp, vp, vp, vp, vp, i, vp, vp, i, i, i, i, i, i, i, i, C.POINTER(f * 3), vp], i),
+        "apse_assoc_fc_workspace_bytes": ([i, i, i], sz),
+        "apse_assoc_fc_forward": ([vp, vp, vp, i, i, i, vp, vp, vp, sz, vp], i),
+        "apse_assoc_fc_backward": ([vp, vp, vp, vp, i, i, i, vp, vp, vp, sz, vp], i),
+        "apse_triplet_workspace_bytes": ([i], sz),
+        "apse_triplet_hard_forward": ([vp, vp, i, i, f, i, vp, vp, sz, vp], i),
+        "apse_triplet_all_forward": ([vp, vp, i, i, f, i, vp, vp, sz, vp], i),
+        "apse_triplet_hard_backward": ([vp, i, i, i, vp, vp, vp, vp], i),
+        "apse_triplet_all_backward": ([vp, i, i, i, vp, vp, vp, vp], i),
+        "apse_sgd_step": ([vp, vp, vp, C.c_longlong, f, f, f, f, i, i, vp], i),
     }
     for name, (args, ret) in sig.items():
         fn = getattr(lib, name)            # AttributeError here = ABI drift between header and library
@@ -168,7 +177,10 @@ EXPORTS = ["apse_create", "apse_destroy", "apse_last_error", "apse_version", "ap
            "apse_l2_normalize", "apse_sqdist", "apse_undistort_gamma", "apse_lab_tables_host", "apse_resize_normalize", "apse_replay_create", "apse_replay_destroy",
            "apse_replay_step", "apse_replay_packed", "apse_replay_max_id", "apse_replay_next_id", "apse_render_workspace_bytes",
            "apse_render_instances", "apse_render_pack_mask", "apse_render_font_host", "apse_mots_split_workspace_bytes",
-           "apse_mots_split_idmap", "apse_mots_rle_to_bits", "apse_mots_overlaps", "apse_mots_render_idmap"]
+           "apse_mots_split_idmap", "apse_mots_rle_to_bits", "apse_mots_overlaps", "apse_mots_render_idmap",
+           "apse_assoc_fc_workspace_bytes", "apse_assoc_fc_forward", "apse_assoc_fc_backward", "apse_triplet_workspace_bytes",
+           "apse_triplet_hard_forward", "apse_triplet_all_forward", "apse_triplet_hard_backward", "apse_triplet_all_backward",
+           "apse_sgd_step"]
 
 
 def stream_ptr():

@@ -17,6 +17,9 @@
 // LDS of one workgroup on gfx950 (160 KiB per CU)
 #define APSE_LDS_BYTES 163840
 
+// Sets the message apse_last_error(NULL) returns (stateless entry points; defined in detector.hip) and returns `code`.
+int apse_fail_global(int code, const char* msg);
+
 typedef __attribute__((ext_vector_type(16))) float f32x16;
 typedef __attribute__((ext_vector_type(4))) float f32x4;
 

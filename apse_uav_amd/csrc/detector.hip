@@ -166,6 +166,7 @@ static int fail(apse_ctx* c, int code, const std::string& msg) {
     if (c) c->err = msg; else g_create_error = msg;
     return code;
 }
+int apse_fail_global(int code, const char* msg) { return fail(nullptr, code, msg); }
 #define HIPCHK(c, call)                                                                        \
     do {                                                                                       \
         hipError_t e_ = (call);                                                                \

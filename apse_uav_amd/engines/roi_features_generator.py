@@ -7,7 +7,7 @@ backbone (stem + res2..res5 + FPN) on one frame, then on ``p2`` (``in_features[0
 
     gen = RoiFeaturesGenerator(config, roi_size=8)
     ids, rois = gen.get_rois_features(original_image, objects, objects_masks=None)
-    # objects rows: <frame>, <id>, <bb_left>, <bb_top>, <bb_width>, <bb_height>, <conf>;  rois: [N, C, roi_size, roi_size]
+    # objects rows: <frame>, <id>, <bb_left>, <bb_top>, <bb_width>, <bb_height>[, <conf>, ...];  rois: [N, C, roi_size, roi_size]
 
 The frame goes through the same HIP path as the tracker (PIL-exact resize + normalise + pad, implicit-GEMM
 backbone); the RoI stage is ``apse_roi_features`` (include/apse_hip.h).  ``objects_masks`` may be COCO RLE dicts
@@ -23,6 +23,18 @@ from ..config import is_c4
 from ..networks.track_rcnn import TrackRCNN
 from ..utils import rle
 from ..weights import load_detector_file, synthetic_detector_state, blocks_from_state
+
+
+def _object_rows(objects):
+    """Object rows as a float64 [N, W] array.  A 2-D array of 6 or more columns is taken as it is (the reference reads
+    columns 1..5 only; its MOTSloader passes 6-column rows, MOTloader 7-column ones); anything else is read as flat
+    7-column rows, as before."""
+    if not len(objects):
+        return np.zeros((0, 7))
+    a = np.asarray(objects, dtype=np.float64)
+    if a.ndim == 2 and a.shape[1] >= 6:
+        return a
+    return a.reshape(-1, 7)
 
 
 class RoiFeaturesGenerator:
@@ -72,7 +84,7 @@ class RoiFeaturesGenerator:
 
     def get_rois_features(self, original_image, objects, objects_masks=None):
         """original_image: HxWx3 uint8 (BGR, as read by cv2); returns (ids tensor [N], rois tensor [N, C, S, S]) on the device."""
-        objects = np.asarray(objects, dtype=np.float64).reshape(-1, 7) if len(objects) else np.zeros((0, 7))
+        objects = _object_rows(objects)
         height, width = original_image.shape[:2]
         n = objects.shape[0]
         C = 256

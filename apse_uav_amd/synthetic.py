@@ -73,3 +73,50 @@ class SyntheticSequence:
             inside = (np.abs(u) <= v["L"] / 2) & (np.abs(w_) <= v["Wd"] / 2)
             img[y0:y1, x0:x1][inside] = np.asarray(v["color"], np.uint8)
         return img
+
+
+def write_synthetic_mots(root, seqs=("0000", "0001"), frames=14, height=160, width=288):
+    """A tiny KITTI MOTS-layout dataset under ``root`` for dry runs of association-head training (tools/
+    train_association_head.py --synthetic, the loader tests): <root>/instances_txt/<seq>.txt (one RLE row per visible vehicle,
+    ids 1001.. for class 1 and 2001.. for class 2, plus one ignore region, id 10000), <root>/training/image_02/<seq>/%06d.png
+    (PIL, RGB) and <root>/train.seqmap.  Frame 1 of every sequence has no objects.  Returns the seqmap path."""
+    import os
+    from PIL import Image
+    from .utils import rle
+    os.makedirs(os.path.join(root, "instances_txt"), exist_ok=True)
+    lines_map = []
+    jit = np.random.default_rng(5)          # per-object box jitter: the same id is seen with different crops
+    for s, seq in enumerate(seqs):
+        ss = SyntheticSequence("dynamic", height, width, n_vehicles=6, seed=77 + s)
+        img_dir = os.path.join(root, "training", "image_02", seq)
+        os.makedirs(img_dir, exist_ok=True)
+        rows = []
+        for t in range(frames):
+            Image.fromarray(ss.frame(t)[:, :, ::-1].copy()).save(os.path.join(img_dir, "%06d.png" % t))
+            if t == 1:
+                continue
+            for i, v in enumerate(ss.veh):
+                cx, cy, vis = ss.pose(v, t, i)
+                if not vis:
+                    continue
+                sc = jit.uniform(0.5, 1.6, 2)
+                cx, cy = cx + jit.uniform(-0.3, 0.3) * v["L"], cy + jit.uniform(-0.3, 0.3) * v["Wd"]
+                hw, hh = 0.35 * v["L"] * sc[0], 0.45 * v["Wd"] * sc[1]
+                x0, x1 = int(max(cx - hw, 0)), int(min(cx + hw, width))
+                y0, y1 = int(max(cy - hh, 0)), int(min(cy + hh, height))
+                if x1 - x0 < 2 or y1 - y0 < 2:
+                    continue
+                m = np.zeros((height, width), np.uint8)
+                m[y0:y1, x0:x1] = 1
+                cls = 1 if i % 2 == 0 else 2
+                rows.append("%d %d %d %d %d %s" % (t, cls * 1000 + 1 + i, cls, height, width, rle.encode(m)["counts"].decode()))
+            ign = np.zeros((height, width), np.uint8)
+            ign[:8, :16] = 1
+            rows.append("%d 10000 10 %d %d %s" % (t, height, width, rle.encode(ign)["counts"].decode()))
+        with open(os.path.join(root, "instances_txt", seq + ".txt"), "w") as f:
+            f.write("\n".join(rows) + "\n")
+        lines_map.append("%s empty %06d %06d" % (seq, 0, frames - 1))
+    seqmap = os.path.join(root, "train.seqmap")
+    with open(seqmap, "w") as f:
+        f.write("\n".join(lines_map) + "\n")
+    return seqmap

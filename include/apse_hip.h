@@ -380,6 +380,47 @@ int apse_mots_overlaps(const apse_mots_window* windows, int n_windows, const int
 int apse_mots_render_idmap(const apse_mots_object* objects, const int* values_host, int n, int H, int W, uint16_t* idmap,
                            void* stream);
 
+/* ---- Association-head training (csrc/assoc_train.hip): the f32 steps of dcnn/scripts/train/train_association_head.py --
+ * AssociationHead's fc + F.normalize (dcnn/networks/association_head.py:16-31) forward and backward, batch_hard_triplet_loss and
+ * batch_all_triplet_loss (dcnn/online_triplet_loss/losses.py:7-197) with their dE, and torch.optim.SGD's step.  Stateless,
+ * enqueue on `stream` only, no allocation; the caller passes the workspace.  Deterministic: no float atomics, fixed reduction
+ * orders, ties of max / min to the lowest index -- two runs of a step give bit-identical losses, gradients and weights.
+ * Errors: APSE_E_INVALID outside the limits below, with the text in apse_last_error(NULL).
+ * Limits: 1 <= n <= APSE_ASSOC_MAX_N rows (embeddings), 1 <= D <= APSE_ASSOC_MAX_D, 1 <= K <= APSE_ASSOC_MAX_K (256 x 32 x 32,
+ * the roi_size bound of apse_roi_features).  The triplet entry points also accept n = 0 and then enqueue nothing (the loss of an
+ * empty batch is the caller's: NaN for batch-hard's mean, 0 for batch-all). */
+#define APSE_ASSOC_MAX_N 2048
+#define APSE_ASSOC_MAX_D 256
+#define APSE_ASSOC_MAX_K (256 * 32 * 32)
+/* Workspace bytes of apse_assoc_fc_forward / _backward (0 outside the limits). */
+size_t apse_assoc_fc_workspace_bytes(int n, int K, int D);
+/* x [n][K] (the NCHW RoIs flattened in (C, H, W) order), w [D][K] (fc.weight), b [D] -> e [n][D] = Z / max(|Z|, 1e-12) with
+ * Z = x w^T + b, and inv_norm [n] = 1 / max(|Z|, 1e-12) for the backward pass. */
+int apse_assoc_fc_forward(const float* x, const float* w, const float* b, int n, int K, int D, float* e, float* inv_norm,
+                          float* ws, size_t ws_bytes, void* stream);
+/* dE [n][D] -> dZ = (dE - e (e . dE)) inv_norm (F.normalize above its eps), dw [D][K] = dZ^T x, db [D] = sum_i dZ.  Overwrites
+ * dw and db (no dx: the RoIs do not require grad). */
+int apse_assoc_fc_backward(const float* x, const float* e, const float* inv_norm, const float* de, int n, int K, int D, float* dw,
+                           float* db, float* ws, size_t ws_bytes, void* stream);
+/* Workspace bytes of the triplet entry points (0 outside the limits).  The forward call leaves the distances and the per-row
+ * coefficients there; the backward call of the same loss reads them. */
+size_t apse_triplet_workspace_bytes(int n);
+/* labels [n] (compared as values), e [n][D] -> loss [1] = batch_hard_triplet_loss(labels, e, margin, squared). */
+int apse_triplet_hard_forward(const double* labels, const float* e, int n, int D, float margin, int squared, float* loss,
+                              void* ws, size_t ws_bytes, void* stream);
+/* -> loss_frac [2] = (loss, fraction_positive_triplets) of batch_all_triplet_loss. */
+int apse_triplet_all_forward(const double* labels, const float* e, int n, int D, float margin, int squared, float* loss_frac,
+                             void* ws, size_t ws_bytes, void* stream);
+/* de [n][D] = grad_loss[0] (device scalar; NULL: 1) x d loss / d e, from the workspace of the forward call. */
+int apse_triplet_hard_backward(const float* e, int n, int D, int squared, const void* ws, const float* grad_loss, float* de,
+                               void* stream);
+int apse_triplet_all_backward(const float* e, int n, int D, int squared, const void* ws, const float* grad_loss, float* de,
+                              void* stream);
+/* One torch.optim.SGD step on n elements of p with grad g and momentum buffer buf (unused when momentum == 0): first_step != 0
+ * sets buf = d_p, as torch does when the buffer does not exist yet.  nesterov needs momentum > 0 and dampening == 0. */
+int apse_sgd_step(float* p, const float* g, float* buf, long long n, float lr, float momentum, float dampening,
+                  float weight_decay, int nesterov, int first_step, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
