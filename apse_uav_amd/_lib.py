@@ -159,6 +159,13 @@ def load():
         "apse_triplet_hard_backward": ([vp, i, i, i, vp, vp, vp, vp], i),
         "apse_triplet_all_backward": ([vp, i, i, i, vp, vp, vp, vp], i),
         "apse_sgd_step": ([vp, vp, vp, C.c_longlong, f, f, f, f, i, i, vp], i),
+        "apse_coco_box_iou": ([vp, vp, vp, i, i, i, vp, vp, vp, vp, vp], i),
+        "apse_coco_poly_to_bits": ([vp, vp, i, vp, i, vp, vp, vp, i, vp, vp, vp, vp], i),
+        "apse_coco_match": ([vp, vp, vp, i, i, i, vp, vp, vp, i, vp, vp, vp, i, vp, i, vp, i, vp, vp, vp, vp, vp], i),
+        "apse_coco_accumulate_workspace_bytes": ([C.c_longlong], sz),
+        "apse_coco_sort_lists": ([vp, vp, i, vp, C.c_longlong, i, vp, vp, sz, vp], i),
+        "apse_coco_accumulate": ([vp, vp, vp, i, vp, i, vp, vp, vp, C.c_longlong, i, vp, i, i, i, i, i, vp, vp, vp, vp, sz,
+                                  vp], i),
     }
     for name, (args, ret) in sig.items():
         fn = getattr(lib, name)            # AttributeError here = ABI drift between header and library
@@ -180,7 +187,8 @@ EXPORTS = ["apse_create", "apse_destroy", "apse_last_error", "apse_version", "ap
            "apse_mots_split_idmap", "apse_mots_rle_to_bits", "apse_mots_overlaps", "apse_mots_render_idmap",
            "apse_assoc_fc_workspace_bytes", "apse_assoc_fc_forward", "apse_assoc_fc_backward", "apse_triplet_workspace_bytes",
            "apse_triplet_hard_forward", "apse_triplet_all_forward", "apse_triplet_hard_backward", "apse_triplet_all_backward",
-           "apse_sgd_step"]
+           "apse_sgd_step", "apse_coco_box_iou", "apse_coco_poly_to_bits", "apse_coco_match",
+           "apse_coco_accumulate_workspace_bytes", "apse_coco_sort_lists", "apse_coco_accumulate"]
 
 
 def stream_ptr():

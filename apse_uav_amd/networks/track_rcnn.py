@@ -120,6 +120,7 @@ class TrackRCNN:
         self._assoc = None
         self._ctx = None
         self._ctx_key = None
+        self.contexts_built = 0               # apse_create calls so far (one per frame / image size change, weights, head)
         self._lay = None
         self._host = None
         self._camera = None                   # FramePreprocessor: undistort + gamma fused into preprocess_frames
@@ -252,6 +253,7 @@ class TrackRCNN:
             lib.apse_destroy(ctx)
             raise
         self._ctx, self._ctx_key, self._lay = ctx, key, lay
+        self.contexts_built += 1
         if self._camera is not None:
             self._push_camera()
         self._host = torch.empty(lay.bytes, dtype=torch.uint8).pin_memory()

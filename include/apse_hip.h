@@ -380,6 +380,82 @@ int apse_mots_overlaps(const apse_mots_window* windows, int n_windows, const int
 int apse_mots_render_idmap(const apse_mots_object* objects, const int* values_host, int n, int H, int W, uint16_t* idmap,
                            void* stream);
 
+/* ---- COCO evaluation (csrc/coco_eval.hip): the per-pair and per-group arithmetic of pycocotools 2.0 COCOeval for iouType
+ * 'bbox' and 'segm' (utils/coco_eval.py keeps the bookkeeping on the host).  Stateless: no context, enqueues on `stream` only, no
+ * allocation, no synchronisation.  Every floating-point value is f64 as pycocotools computes it; no float atomics, every reduction
+ * is an exact max or an integer sum, so two runs are bit-identical.  Errors: APSE_E_INVALID outside the limits below, with the
+ * text in apse_last_error(NULL).
+ * Groups: detections and ground truths of one (image, category) pair, as CSR offsets over flat arrays: group k holds detections
+ * dt_off[k] .. dt_off[k + 1] and ground truths gt_off[k] .. gt_off[k + 1] (device int [n_groups + 1]); its IoU block [D][G]
+ * starts at iou[iou_off[k]] (device int64 [n_groups]).
+ * Limits: at most APSE_COCO_MAX_GROUPS groups, APSE_COCO_MAX_GT ground truths and APSE_COCO_MAX_DET detections per group
+ * (max_gt / max_dt: the caller's largest group), APSE_COCO_MAX_T IoU thresholds, APSE_COCO_MAX_R recall thresholds,
+ * APSE_COCO_MAX_A area ranges, APSE_COCO_MAX_M maxDets values, APSE_COCO_MAX_CATS categories, APSE_COCO_MAX_KEYS detections
+ * in one (category, maxDet) list.  COCO val2017 with default Params needs 400k groups, tens of ground truths per group, 100
+ * detections per group, T = 10, R = 101, A = 4, M = 3, K = 80 and at most 500k detections per category. */
+#define APSE_COCO_MAX_GROUPS (1 << 24)
+#define APSE_COCO_MAX_GT 4096
+#define APSE_COCO_MAX_DET 4096
+#define APSE_COCO_MAX_T 64
+#define APSE_COCO_MAX_R 1024
+#define APSE_COCO_MAX_A 16
+#define APSE_COCO_MAX_M 16
+#define APSE_COCO_MAX_CATS 1024
+#define APSE_COCO_MAX_KEYS (1 << 24)
+#define APSE_COCO_MAX_POLY_OBJECTS (1 << 20)
+#define APSE_COCO_MAX_POLY_PARTS (1 << 22)
+#define APSE_COCO_MAX_POLY_VERTS (1 << 26)
+/* maskApi bbIou: iou[iou_off[k] + d * G + g] for every group k, from XYWH boxes dt_box [n_dt][4] and gt_box [n_gt][4] (f64) and
+ * gt_crowd [n_gt] (int, nonzero: crowd).  w = fmin(D0+D2, G0+G2) - fmax(D0, G0) (0 when <= 0), the same for h, i = w*h,
+ * u = crowd ? D2*D3 : (D2*D3 + G2*G3) - i, IoU = i / u.  A group without detections or without ground truths writes nothing. */
+int apse_coco_box_iou(const int* dt_off, const int* gt_off, const long long* iou_off, int n_groups, int max_dt, int max_gt,
+                      const double* dt_box, const double* gt_box, const int* gt_crowd, double* iou, void* stream);
+/* COCO polygons -> window bits, equal pixel for pixel to pycocotools rleFrPoly of every part followed by merge (union).  Object
+ * i (an h x w image: obj_hw [n_obj][2] = {h, w}, device, and the same values in obj_hw_host) owns parts obj_part_off[i] ..
+ * obj_part_off[i + 1]; part p owns vertices part_vert_off[p] .. part_vert_off[p + 1] of xy [n_verts][2] (f64, x then y), closed
+ * back to its first vertex.  Vertex coordinates must be finite with |5 v + .5| < 2^31.  edge_off [n_verts + 1] (device) is the
+ * exclusive scan of every edge's y-boundary point count: with lo / hi the smaller / larger scaled x (int)(5 x + .5) of the
+ * edge's two vertices, the number of columns c in [0, w - 1] with lo <= 5c + 2 and 5c + 3 <= hi (utils/coco.py poly_layout).
+ * An edge whose count the device finds different sets info[0] = 1 and writes nothing.  toggles [edge_off[n_verts]] (device int)
+ * is scratch.  windows[i] (device: rect, words_per_row, bits) must hold every set pixel; every word of it is written. */
+int apse_coco_poly_to_bits(const double* xy, const int* part_vert_off, int n_parts, const int* obj_part_off, int n_obj,
+                           const int* obj_hw, const int* obj_hw_host, const int* edge_off, int n_verts, int* toggles,
+                           const apse_mots_window* windows, int* info, void* stream);
+/* evaluateImg for every (group, area range a, IoU threshold t) at once.  Each group's detections are already in stable score
+ * order and cut to maxDets[-1]; dt_area / dt_id (int64) per detection, gt_area / gt_crowd / gt_id per ground truth (ground truths
+ * in file order), iou as apse_coco_box_iou writes it.  area_rng_host [A][2] and iou_thrs_host [T] are Params' f64 arrays (host).
+ * A ground truth is ignored in range a when crowd or area < lo or area > hi.  Greedy matching, detections in order: the
+ * threshold is min(t, 1 - 1e-10); a ground truth already matched (its match > 0) and not crowd is skipped; the pick is the
+ * not-ignored ground truth of highest IoU >= threshold (ties to the later one), else the ignored one by the same rule.
+ * Outputs (device): dt_match [A][T][n_dt] = the matched ground truth's id (0: none), dt_ignore [A][T][n_dt] = the matched ground
+ * truth's ignore flag, or 1 when unmatched (match == 0) with an area outside the range; gt_match [A][T][n_gt] = the matching
+ * detection's id (0: none), ground truths in file order; gt_ignore [A][n_gt] in file order. */
+int apse_coco_match(const int* dt_off, const int* gt_off, const long long* iou_off, int n_groups, int max_dt, int max_gt,
+                    const double* iou, const double* dt_area, const long long* dt_id, int n_dt, const double* gt_area,
+                    const int* gt_crowd, const long long* gt_id, int n_gt, const double* area_rng_host, int A,
+                    const double* iou_thrs_host, int T, long long* dt_match, unsigned char* dt_ignore, long long* gt_match,
+                    unsigned char* gt_ignore, void* stream);
+/* Workspace bytes of apse_coco_accumulate for n_keys detections over all (category, maxDet) lists (0 outside the limits). */
+size_t apse_coco_accumulate_workspace_bytes(long long n_keys);
+/* The sort of apse_coco_accumulate on its own: list s = seg_idx[seg_off[s] .. seg_off[s + 1]) (indices into score, device
+ * f64) -> sorted_idx[seg_off[s] ..] (device int [n_keys]) in the order of np.argsort(-score[list], kind='mergesort'): descending,
+ * -0 and +0 equal, NaN last, ties in list order.  At most APSE_COCO_MAX_CATS * APSE_COCO_MAX_M lists of at most max_seg <=
+ * APSE_COCO_MAX_KEYS keys; ws [ws_bytes >= apse_coco_accumulate_workspace_bytes(n_keys)] is scratch. */
+int apse_coco_sort_lists(const double* score, const int* seg_off, int n_seg, const int* seg_idx, long long n_keys, int max_seg,
+                         int* sorted_idx, void* ws, size_t ws_bytes, void* stream);
+/* COCOeval.accumulate.  The list of (maxDet index m, category k) is segment m * K + k: seg_idx[seg_off[s] .. seg_off[s + 1])
+ * holds the detection indices (into dt_score and the match outputs) of each image's first maxDets[m] detections of category k,
+ * concatenated in image order; max_seg is the longest list.  Each list is sorted stably by descending score (the order of
+ * np.argsort(-scores, kind='mergesort')).  npig (k, a) counts gt_ignore[a][g] == 0 over cat_gt_off[k] .. cat_gt_off[k + 1].
+ * tp = match != 0 and not ignored, fp = match == 0 and not ignored, rc = tp / npig, pr = tp / ((fp + tp) + 2^-52) and its suffix
+ * maximum; for each recall threshold rec_thrs[r] (device f64 [R]) the first i with rc[i] >= rec_thrs[r] gives precision and
+ * scores, 0 past the end.  Writes precision [T][R][K][A][M], scores [T][R][K][A][M] and recall [T][K][A][M] (device f64); a
+ * (k, a) with npig == 0 is -1 throughout. */
+int apse_coco_accumulate(const double* dt_score, const long long* dt_match, const unsigned char* dt_ignore, int n_dt,
+                         const unsigned char* gt_ignore, int n_gt, const int* cat_gt_off, const int* seg_off,
+                         const int* seg_idx, long long n_keys, int max_seg, const double* rec_thrs, int T, int R, int K, int A,
+                         int M, double* precision, double* recall, double* scores, void* ws, size_t ws_bytes, void* stream);
+
 /* ---- Association-head training (csrc/assoc_train.hip): the f32 steps of dcnn/scripts/train/train_association_head.py --
  * AssociationHead's fc + F.normalize (dcnn/networks/association_head.py:16-31) forward and backward, batch_hard_triplet_loss and
  * batch_all_triplet_loss (dcnn/online_triplet_loss/losses.py:7-197) with their dE, and torch.optim.SGD's step.  Stateless,
