@@ -166,6 +166,18 @@ def load():
         "apse_coco_sort_lists": ([vp, vp, i, vp, C.c_longlong, i, vp, vp, sz, vp], i),
         "apse_coco_accumulate": ([vp, vp, vp, i, vp, i, vp, vp, vp, C.c_longlong, i, vp, i, i, i, i, i, vp, vp, vp, vp, sz,
                                   vp], i),
+        "apse_mask_roi_features": ([vp, i, vp, i, vp, vp], i),
+        "apse_mask_train_workspace_bytes": ([i, i], sz),
+        "apse_mask_pack_elems": ([i, i, i, i], sz),
+        "apse_mask_pack_weight": ([vp, vp, i, i, i, i, i, vp, vp, vp], i),
+        "apse_mask_conv_forward": ([vp, vp, vp, i, i, i, i, i, i, i, i, i, i, i, vp, vp, sz, vp], i),
+        "apse_mask_conv3x3": ([vp, vp, vp, i, i, vp, vp], i),
+        "apse_mask_relu_grad": ([vp, vp, C.c_longlong, vp, vp], i),
+        "apse_mask_bias_grad": ([vp, C.c_longlong, vp, vp, sz, vp], i),
+        "apse_mask_wgrad": ([vp, vp, i, i, vp, vp, sz, vp], i),
+        "apse_mask_loss_forward": ([vp, i, vp, vp, i, vp, vp, sz, vp], i),
+        "apse_mask_loss_backward": ([vp, i, vp, vp, i, vp, vp, vp], i),
+        "apse_mask_predictor_backward": ([vp, vp, vp, vp, i, i, vp, vp, vp, vp, sz, vp], i),
     }
     for name, (args, ret) in sig.items():
         fn = getattr(lib, name)            # AttributeError here = ABI drift between header and library
@@ -188,7 +200,10 @@ EXPORTS = ["apse_create", "apse_destroy", "apse_last_error", "apse_version", "ap
            "apse_assoc_fc_workspace_bytes", "apse_assoc_fc_forward", "apse_assoc_fc_backward", "apse_triplet_workspace_bytes",
            "apse_triplet_hard_forward", "apse_triplet_all_forward", "apse_triplet_hard_backward", "apse_triplet_all_backward",
            "apse_sgd_step", "apse_coco_box_iou", "apse_coco_poly_to_bits", "apse_coco_match",
-           "apse_coco_accumulate_workspace_bytes", "apse_coco_sort_lists", "apse_coco_accumulate"]
+           "apse_coco_accumulate_workspace_bytes", "apse_coco_sort_lists", "apse_coco_accumulate",
+           "apse_mask_roi_features", "apse_mask_train_workspace_bytes", "apse_mask_pack_elems", "apse_mask_pack_weight",
+           "apse_mask_conv_forward", "apse_mask_conv3x3", "apse_mask_relu_grad", "apse_mask_bias_grad", "apse_mask_wgrad", "apse_mask_loss_forward",
+           "apse_mask_loss_backward", "apse_mask_predictor_backward"]
 
 
 def stream_ptr():

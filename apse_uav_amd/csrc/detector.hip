@@ -55,6 +55,7 @@ int apse_k_rank_wide(const float*, const float*, int, const int*, const int*, in
 int apse_k_pack_detections(const float*, const float*, const int*, const int*, int, int, int, float*, float*, int*, int*,
                            int*, int*, int*, unsigned long long*, hipStream_t);
 int apse_k_roi_align(const FpnMaps*, const float*, const int*, const int*, const int*, int, int, int, void*, int, hipStream_t);
+int apse_k_mask_roi_index(int*, int, hipStream_t);
 int apse_k_roi_pool(const void*, int, int, int, const float*, const int*, const int*, int, int, float, float*, int, int, hipStream_t);
 int apse_k_mask_resize(const uint8_t*, int, int, int, int, int, float*, hipStream_t);
 int apse_k_round16(const float*, uint16_t*, size_t, int, hipStream_t);
@@ -139,6 +140,7 @@ struct apse_ctx {
     float* emb_raw = nullptr;
     float* ws_assoc = nullptr;      // [K / 128][max detections][embed_dim]: K slices of the association FC (apse_k_assoc_fc), or nullptr
     float* rf_mask = nullptr; size_t rf_mask_floats = 0;      // apse_roi_features: masks at p2 resolution (grown on demand)
+    int* mrf_idx = nullptr; size_t mrf_cap = 0;               // apse_mask_roi_features: image index per RoI + live count (grown on demand)
     bool box_maxc_clean = false;
     UndistortParams cam; bool cam_on = false; LabTables* cam_lut = nullptr; void* cam_map = nullptr; bool cam_map_ok = false;     // apse_set_camera: fused undistort + gamma in apse_preprocess_frames
     int hint_total = 8;      // detections seen in the previous forward: sizes the GRID of the packed-list GEMMs, nothing else
@@ -1125,6 +1127,7 @@ void apse_destroy(apse_ctx* c) {
     hipSetDevice(c->cfg.device);
     for (void* p : c->allocs) hipFree(p);
     if (c->rf_mask) hipFree(c->rf_mask);
+    if (c->mrf_idx) hipFree(c->mrf_idx);
     if (c->read_ev) hipEventDestroy(c->read_ev);
     for (int k = 0; k < 2; ++k) {
         if (c->given_ev[k]) hipEventDestroy(c->given_ev[k]);
@@ -1612,6 +1615,32 @@ int apse_roi_features(apse_ctx* c, int image, const float* rois, const uint8_t* 
     if (rc) return fail(c, rc, "mask resize launch failed");
     rc = apse_k_roi_align_masked(p2.p, p2.st, p2.H, p2.W, image, rois, c->rf_mask, n, roi_size, 4, scale, out, s);
     return rc ? fail(c, rc, "masked roi_align launch failed") : APSE_OK;
+}
+
+int apse_mask_roi_features(apse_ctx* c, int image, const float* rois, int n, float* out, void* stream) {
+    if (!c || !c->finalized) return fail(c, APSE_E_STATE, "not finalized");
+    const apse_config& g = c->cfg;
+    if (image < 0 || image >= g.max_batch || n < 0 || n > (1 << 20) || (n > 0 && (!rois || !out)))
+        return fail(c, APSE_E_INVALID, "bad mask_roi_features arguments (image inside the batch, 0 <= n <= 2^20)");
+    if (c->c4) return fail(c, APSE_E_INVALID, "apse_mask_roi_features pools p2..p5: not available under C4 (arch 1)");
+    if (n == 0) return APSE_OK;
+    hipStream_t s = (hipStream_t)stream;
+    if ((size_t)n + 1 > c->mrf_cap) {
+        HIPCHK(c, hipStreamSynchronize(s));
+        if (c->mrf_idx) hipFree(c->mrf_idx);
+        c->mrf_idx = nullptr; c->mrf_cap = 0;
+        if (hipMalloc(reinterpret_cast<void**>(&c->mrf_idx), ((size_t)n + 1) * sizeof(int)) != hipSuccess) return fail(c, APSE_E_NOMEM, "mask_roi_features scratch");
+        c->mrf_cap = (size_t)n + 1;
+    }
+    // the mask branch's own launch (apse_mask_tail) on a list that lives in `image`: the maps are offset to that image, every RoI
+    // carries image index 0 and the live count is n.  The kernel strides its blocks over the RoIs, so n has no launch bound.
+    FpnMaps fm = c->fm;
+    for (int l = 0; l < 4; ++l)
+        fm.p[l] = reinterpret_cast<const char*>(fm.p[l]) + (size_t)image * fm.H[l] * fm.W[l] * 256 * (fm.st ? 2 : 4);
+    int rc = apse_k_mask_roi_index(c->mrf_idx, n, s);
+    if (rc) return fail(c, rc, "mask_roi_features index launch failed");
+    rc = apse_k_roi_align(&fm, rois, c->mrf_idx, nullptr, c->mrf_idx + n, 0, n, 14, out, 0, s);
+    return rc ? fail(c, rc, "roi_align(14) launch failed") : APSE_OK;
 }
 
 int apse_debug_tensor(apse_ctx* c, const char* name, void* dst, size_t max_bytes, size_t* bytes, void* stream) {

@@ -331,6 +331,25 @@ class TrackRCNN:
         self._call("apse_debug_tensor", name.encode(), _lib.ptr(out), n.value, C.byref(n), _lib.stream_ptr())
         return out
 
+    def backbone_frames(self, frames):
+        """Preprocess uint8 CUDA frames [B, H, W, 3] (BGR) and run the backbone only (stem .. FPN): what ``mask_roi_features``
+        and ``export_feature`` read afterwards."""
+        B = self.preprocess_frames(frames)
+        self._running_tag = None
+        self._call("apse_backbone", B, _lib.stream_ptr())
+        return B
+
+    def mask_roi_features(self, boxes, image=0):
+        """ROIAlign 14x14 of ``boxes`` ([n][4] x1,y1,x2,y2 in resized-image pixels, any n) over p2..p5 of image ``image`` of the last
+        ``apse_backbone`` run: f32 [n][14][14][256], the values the mask branch pools for the same boxes (apse_mask_roi_features;
+        FPN models only -- the mask-head training input, networks/mask_head.py)."""
+        if self.c4:
+            raise NotImplementedError("mask_roi_features pools p2..p5: not available for C4 (Res5ROIHeads) models")
+        b = torch.as_tensor(boxes, dtype=torch.float32).reshape(-1, 4).to(self.device).contiguous()
+        out = torch.empty((b.shape[0], 14, 14, 256), dtype=torch.float32, device=self.device)
+        self._call("apse_mask_roi_features", int(image), _lib.ptr(b), b.shape[0], _lib.ptr(out), _lib.stream_ptr())
+        return out
+
     def flops(self, batch, proposals, detections):
         return float(_lib.load().apse_flops(self._ctx, batch, proposals, detections))
 

@@ -70,3 +70,77 @@ class SGD:
     def state_dict(self):
         return {"state": {i: dict(self.state[p]) for i, p in enumerate(self.params) if p in self.state},
                 "param_groups": [{k: v for k, v in self.param_groups[0].items() if k != "params"}]}
+
+    def load_state_dict(self, sd):
+        """Restores what ``state_dict`` wrote (hyper-parameters and momentum buffers, matched to the parameters by position)."""
+        for k, v in sd["param_groups"][0].items():
+            if k != "params":
+                self.param_groups[0][k] = v
+        self.state = {}
+        for i, st in sd["state"].items():
+            p = self.params[int(i)]
+            self.state[p] = {k: (v.detach().to(device=p.device, dtype=p.dtype).clone() if torch.is_tensor(v) else v)
+                             for k, v in st.items()}
+
+
+class WarmupMultiStepLR:
+    """detectron2's ``build_lr_scheduler`` default (solver/lr_scheduler.py WarmupMultiStepLR), as
+    dcnn/scripts/train/finetune_segmentation.py steps it once per iteration:
+
+        lr(it) = base_lr * warmup(it) * gamma ** (number of milestones <= it)
+        warmup(it) = 1 for it >= warmup_iters, else warmup_factor * (1 - it / warmup_iters) + it / warmup_iters   ("linear")
+                     ("constant": warmup_factor)
+
+    Works on any optimizer with ``param_groups`` (``torch.optim.SGD``, ``apse_uav_amd.optim.SGD``).  Like torch's schedulers the
+    constructor sets the learning rate of iteration 0 and ``step()`` moves to the next iteration.
+    """
+
+    def __init__(self, optimizer, milestones, gamma=0.1, warmup_factor=0.001, warmup_iters=1000, warmup_method="linear",
+                 last_epoch=-1):
+        milestones = [int(m) for m in milestones]
+        if milestones != sorted(milestones):
+            raise ValueError("Milestones should be a list of increasing integers. Got {}".format(milestones))
+        if warmup_method not in ("linear", "constant"):
+            raise ValueError("Unknown warmup method: {}".format(warmup_method))
+        self.optimizer = optimizer
+        self.milestones = milestones
+        self.gamma = float(gamma)
+        self.warmup_factor = float(warmup_factor)
+        self.warmup_iters = int(warmup_iters)
+        self.warmup_method = warmup_method
+        for g in optimizer.param_groups:
+            g.setdefault("initial_lr", g["lr"])
+        self.base_lrs = [g["initial_lr"] for g in optimizer.param_groups]
+        self.last_epoch = int(last_epoch)
+        self.step()
+
+    def factor(self, it):
+        """lr(it) / base_lr."""
+        if it >= self.warmup_iters:
+            warm = 1.0
+        elif self.warmup_method == "constant":
+            warm = self.warmup_factor
+        else:
+            alpha = it / self.warmup_iters
+            warm = self.warmup_factor * (1 - alpha) + alpha
+        return warm * self.gamma ** sum(1 for m in self.milestones if m <= it)
+
+    def get_lr(self):
+        f = self.factor(self.last_epoch)
+        return [b * f for b in self.base_lrs]
+
+    def get_last_lr(self):
+        return [g["lr"] for g in self.optimizer.param_groups]
+
+    def step(self):
+        self.last_epoch += 1
+        for g, lr in zip(self.optimizer.param_groups, self.get_lr()):
+            g["lr"] = lr
+
+    def state_dict(self):
+        return {k: v for k, v in self.__dict__.items() if k != "optimizer"}
+
+    def load_state_dict(self, sd):
+        self.__dict__.update(sd)
+        for g, lr in zip(self.optimizer.param_groups, self.get_lr()):
+            g["lr"] = lr

@@ -1,0 +1,216 @@
+"""Dataset side of mask-head fine-tuning -- counterpart of dcnn/utils/COCO_utils.py and of the detectron2 pieces
+dcnn/scripts/train/finetune_segmentation.py leans on (dataset dictionaries, ``PolygonMasks.crop_and_resize``, the train loader).
+
+* ``generate_coco_dataset_dictionaries``: COCO json -> detectron2-style dataset dictionaries with the reference's filtering
+  (non-crowd annotations of the allowed class names, category ids mapped), ground-truth boxes as precomputed proposals.
+  The reference's line ``annotation_dict['segmentation'] = ann['segmentation'],`` wraps the polygon list in a 1-tuple by accident;
+  here the list itself is stored.  RLE (dict) segmentations are refused: the reference drops crowds, and non-crowd COCO
+  annotations are polygons.
+* ``detectron2_dataset_to_coco``: the dictionaries back to a COCO dataset (for ``utils.coco.COCO.from_dataset`` / ``COCOeval``).
+* ``mask_targets``: ``PolygonMasks.crop_and_resize`` (``rasterize_polygons_within_box``) at 28 x 28: the polygon transform on the
+  host in float64, the rasterisation by ``apse_coco_poly_to_bits`` (equal to pycocotools ``frPyObjects`` + ``merge``).
+* ``MaskTrainLoader``: batches of ``IMS_PER_BATCH`` images -> RoI features of the ground-truth boxes from the frozen backbone
+  (test-size resize; optional seeded horizontal flip), classes and 28 x 28 targets.  Ground truths appear once: detectron2 appends
+  the ground truth to proposals that already are the ground truth, and an exact duplicate of every RoI leaves a mean loss and its
+  gradient unchanged.
+"""
+import json
+import os
+
+import numpy as np
+import torch
+
+from . import coco as cocomod
+from . import resample
+
+MASK_SIZE = 28
+XYWH_ABS = 1          # detectron2 BoxMode.XYWH_ABS
+
+
+def generate_coco_dataset_dictionaries(json_file, imgfolder, allowed_classes=None, category_mapping=None,
+                                       precomputed_proposals=True):
+    """-> list of {file_name, image_id, height, width, annotations: [{bbox (XYWH), bbox_mode, category_id, segmentation, iscrowd}],
+    proposal_boxes (XYXY f32 [k, 4]), proposal_objectness_logits, proposal_bbox_mode}.  ``allowed_classes``: category NAMES to
+    keep (None: all); ``category_mapping``: {json category id: training class index} (None: the sorted kept ids -> 0..K-1).
+    Images left without annotations are dropped, as the reference does."""
+    with open(json_file) as fh:
+        data = json.load(fh)
+    names = {c["id"]: c["name"] for c in data["categories"]}
+    keep_ids = sorted(i for i, nm in names.items() if allowed_classes is None or nm in allowed_classes)
+    if category_mapping is None:
+        category_mapping = {cid: k for k, cid in enumerate(keep_ids)}
+    by_img = {}
+    for ann in data["annotations"]:
+        by_img.setdefault(ann["image_id"], []).append(ann)
+    out = []
+    for img in data["images"]:
+        anns = []
+        for ann in by_img.get(img["id"], []):
+            if ann.get("iscrowd", 0) or ann["category_id"] not in keep_ids or ann["category_id"] not in category_mapping:
+                continue
+            seg = ann.get("segmentation")
+            if isinstance(seg, dict):
+                raise ValueError("annotation %s: RLE segmentations are not supported for mask-head training (non-crowd COCO "
+                                 "annotations are polygons)" % ann.get("id"))
+            if not seg:
+                continue
+            anns.append({"bbox": [float(v) for v in ann["bbox"]], "bbox_mode": XYWH_ABS,
+                         "category_id": int(category_mapping[ann["category_id"]]),
+                         "segmentation": [list(map(float, p)) for p in seg],          # the list itself (not the reference's 1-tuple)
+                         "iscrowd": 0})
+        if not anns:
+            continue
+        d = {"file_name": os.path.join(imgfolder, img["file_name"]), "image_id": img["id"], "height": int(img["height"]),
+             "width": int(img["width"]), "annotations": anns}
+        if precomputed_proposals:
+            b = np.array([a["bbox"] for a in anns], np.float32).reshape(-1, 4)
+            d["proposal_boxes"] = np.stack([b[:, 0], b[:, 1], b[:, 0] + b[:, 2], b[:, 1] + b[:, 3]], 1)
+            d["proposal_objectness_logits"] = np.ones(len(anns), np.float32)
+            d["proposal_bbox_mode"] = 0                                              # XYXY_ABS
+        out.append(d)
+    return out
+
+
+def detectron2_dataset_to_coco(dicts, class_names=None):
+    """Dataset dictionaries -> COCO dataset dict (category ids = training class indices)."""
+    images, anns, cats = [], [], set()
+    for d in dicts:
+        images.append({"id": d["image_id"], "file_name": os.path.basename(d["file_name"]), "height": d["height"], "width": d["width"]})
+        for a in d["annotations"]:
+            x, y, w, h = a["bbox"]
+            area = float(w * h)
+            anns.append({"id": len(anns) + 1, "image_id": d["image_id"], "category_id": a["category_id"], "bbox": [x, y, w, h],
+                         "area": area, "iscrowd": a.get("iscrowd", 0), "segmentation": a["segmentation"]})
+            cats.add(a["category_id"])
+    K = (max(cats) + 1) if cats else 0
+    if class_names is not None:
+        K = max(K, len(class_names))
+    categories = [{"id": k, "name": class_names[k] if class_names is not None and k < len(class_names) else "class%d" % k}
+                  for k in range(K)]
+    return {"images": images, "annotations": anns, "categories": categories}
+
+
+def crop_and_resize_polygons(polygons, box, mask_size=MASK_SIZE):
+    """detectron2 ``rasterize_polygons_within_box`` up to the rasterisation: polygons (flat x, y lists) shifted by the box origin
+    and scaled by mask_size / max(extent, 0.1), in float64; one multiply of the whole array when the two ratios are equal."""
+    x0, y0, x1, y1 = (float(v) for v in box)
+    w, h = x1 - x0, y1 - y0
+    out = []
+    for p in polygons:
+        q = np.array(p, np.float64)
+        q = q[:2 * (len(q) // 2)].copy()
+        q[0::2] = q[0::2] - x0
+        q[1::2] = q[1::2] - y0
+        out.append(q)
+    rh, rw = mask_size / max(h, 0.1), mask_size / max(w, 0.1)
+    if rh == rw:
+        for q in out:
+            q *= rh
+    else:
+        for q in out:
+            q[0::2] *= rw
+            q[1::2] *= rh
+    return out
+
+
+def mask_targets(polygons_per_roi, boxes, device, mask_size=MASK_SIZE):
+    """``PolygonMasks.crop_and_resize(boxes, mask_size)``: uint8 [n][mask_size][mask_size] on the device (1 = inside)."""
+    n = len(polygons_per_roi)
+    if n == 0:
+        return torch.zeros((0, mask_size, mask_size), dtype=torch.uint8, device=device)
+    objs = []
+    for polys, box in zip(polygons_per_roi, np.asarray(boxes, np.float64).reshape(-1, 4)):
+        parts = [q.reshape(-1, 2) for q in crop_and_resize_polygons(polys, box, mask_size)]
+        objs.append((parts, mask_size, mask_size))
+    windows, keep = cocomod.polygons_to_windows(objs, device)
+    dense = cocomod.windows_to_dense(windows, mask_size, mask_size)
+    del keep
+    return torch.from_numpy(dense.astype(np.uint8)).to(device)
+
+
+def flip_annotations(boxes, polygons_per_roi, width):
+    """Horizontal flip of XYXY boxes and polygons (detectron2 HFlipTransform: x -> width - x)."""
+    b = np.asarray(boxes, np.float64).reshape(-1, 4).copy()
+    x0 = width - b[:, 2]
+    x1 = width - b[:, 0]
+    b[:, 0], b[:, 2] = x0, x1
+    polys = []
+    for ps in polygons_per_roi:
+        qs = []
+        for p in ps:
+            q = np.array(p, np.float64)
+            q[0::2] = width - q[0::2]
+            qs.append(q)
+        polys.append(qs)
+    return b, polys
+
+
+class MaskTrainLoader:
+    """Yields (roi_features [n][14][14][256], classes int64 [n] (host), targets uint8 [n][28][28]) per batch of ``ims_per_batch``
+    images, endlessly, in a seeded shuffled order.  ``model``: a TrackRCNN (FPN) with the frozen detector's weights.
+    ``cache_features=True`` keeps every image's RoI features and targets on the device after the first visit (196 KB per object
+    for the features); it is off when ``flip`` is on, where an image has two versions.  A batch with more than ``max_rois``
+    ground truths (APSE_MASK_TRAIN_MAX_N) keeps the first ``max_rois``."""
+
+    def __init__(self, dicts, model, ims_per_batch=2, seed=0, flip=False, cache_features=False, max_rois=1024):
+        if getattr(model, "c4", False):
+            raise NotImplementedError("mask-head training covers FPN models; C4 (Res5ROIHeads) shares res5 with the box branch")
+        self.dicts = list(dicts)
+        self.model = model
+        self.ims_per_batch = int(ims_per_batch)
+        self.flip = bool(flip)
+        self.cache = {} if (cache_features and not flip) else None
+        self.max_rois = int(max_rois)
+        self.rng = np.random.default_rng(seed)
+        self._order = []
+
+    def state_dict(self):
+        return {"rng": self.rng.bit_generator.state, "order": list(self._order)}
+
+    def load_state_dict(self, sd):
+        self.rng.bit_generator.state = sd["rng"]
+        self._order = list(sd["order"])
+
+    def image_item(self, d, flipped=False):
+        """One image through the frozen backbone: (features, classes, targets) of its ground-truth boxes."""
+        from PIL import Image
+        key = d["image_id"]
+        if self.cache is not None and key in self.cache:
+            return self.cache[key]
+        model = self.model
+        frame = np.asarray(Image.open(d["file_name"]).convert("RGB"))[:, :, ::-1].copy()
+        H, W = frame.shape[:2]
+        if (H, W) != (d["height"], d["width"]):
+            raise ValueError("%s is %dx%d, the annotations say %dx%d" % (d["file_name"], H, W, d["height"], d["width"]))
+        boxes = np.array([[a["bbox"][0], a["bbox"][1], a["bbox"][0] + a["bbox"][2], a["bbox"][1] + a["bbox"][3]]
+                          for a in d["annotations"]], np.float64).reshape(-1, 4)
+        polys = [a["segmentation"] for a in d["annotations"]]
+        classes = torch.tensor([a["category_id"] for a in d["annotations"]], dtype=torch.int64)
+        if flipped:
+            frame = frame[:, ::-1].copy()
+            boxes, polys = flip_annotations(boxes, polys, W)
+        ih, iw = resample.resize_shortest_edge(H, W, model.cfg.INPUT.MIN_SIZE_TEST, model.cfg.INPUT.MAX_SIZE_TEST)
+        sx, sy = iw / W, ih / H                                   # detectron2's ResizeTransform scales boxes and polygons alike
+        boxes = boxes * np.array([sx, sy, sx, sy])
+        polys = [[np.array(p, np.float64) * np.tile([sx, sy], len(p) // 2) for p in ps] for ps in polys]
+        model.backbone_frames(torch.from_numpy(frame[None]).to(model.device))
+        feats = model.mask_roi_features(boxes.astype(np.float32))
+        targets = mask_targets(polys, boxes, model.device)
+        item = (feats, classes, targets)
+        if self.cache is not None:
+            self.cache[key] = item
+        return item
+
+    def __iter__(self):
+        return self
+
+    def __next__(self):
+        items = []
+        for _ in range(self.ims_per_batch):
+            if not self._order:
+                self._order = [int(i) for i in self.rng.permutation(len(self.dicts))]
+            d = self.dicts[self._order.pop(0)]
+            flipped = bool(self.flip and self.rng.random() < 0.5)
+            items.append(self.image_item(d, flipped))
+        feats = torch.cat([i[0] for i in items])[:self.max_rois]
+        return feats, torch.cat([i[1] for i in items])[:self.max_rois], torch.cat([i[2] for i in items])[:self.max_rois]

@@ -497,6 +497,62 @@ int apse_triplet_all_backward(const float* e, int n, int D, int squared, const v
 int apse_sgd_step(float* p, const float* g, float* buf, long long n, float lr, float momentum, float dampening,
                   float weight_decay, int nesterov, int first_step, void* stream);
 
+/* ---- Mask-head training (csrc/mask_train.hip): the f32 steps of dcnn/scripts/train/finetune_segmentation.py for
+ * MaskRCNNConvUpsampleHead (FPN models: ROIAlign 14 -> 4 x (conv3x3 256 + ReLU) -> deconv 2x2 stride 2 + ReLU -> 1x1 predictor with
+ * K class channels) and mask_rcnn_loss.  NHWC f32 activations; the master weights stay in the checkpoint's layouts on the device.
+ * Stateless, enqueue on `stream` only, no allocation; the caller passes the workspace (apse_mask_train_workspace_bytes covers every
+ * entry below).  Deterministic: no float atomics, every sum has an order fixed by the shapes.  Errors: APSE_E_INVALID outside the
+ * limits, with the text in apse_last_error(NULL).  Limits: 1 <= n <= APSE_MASK_TRAIN_MAX_N RoIs per call (the loss entries also
+ * take n = 0 and then enqueue nothing), 1 <= K <= APSE_MAX_CLASSES. */
+#define APSE_MASK_TRAIN_MAX_N 1024
+/* ROIAlignV2 14x14 (aligned, sampling ratio 0) of `n` boxes over p2..p5 of image `image`, detectron2's level assignment: the
+ * launch apse_mask_tail runs on its detection list, so the values equal the `mask_pooled` tensor of apse_set_detections +
+ * apse_mask_tail for the same boxes.  To be called after apse_backbone (FPN only).  rois_dev [n][4] x1,y1,x2,y2 in RESIZED-image
+ * pixels; out_dev f32 [n][14][14][256].  0 <= n <= 2^20 (not bound by the detection list). */
+int apse_mask_roi_features(apse_ctx* ctx, int image, const float* rois_dev, int n, float* out_dev, void* stream);
+/* Workspace bytes for n RoIs and K classes (0 outside the limits). */
+size_t apse_mask_train_workspace_bytes(int n, int K);
+/* Elements of a packed filter (= apse_conv_packed_elems of the same shape). */
+size_t apse_mask_pack_elems(int Cout, int Cin, int KH, int KW);
+/* Device-side filter packing into the rows apse_conv2d reads.  kind 0: w = OIHW [Cout][Cin][KH][KW] -> the bytes
+ * apse_conv_pack_weight writes.  kind 1: w = OIHW [Cin][Cout][3][3] of a FORWARD 3x3 layer -> the filter of its data gradient
+ * (taps flipped, channels transposed; Cout here = the forward layer's Cin).  kind 2: w = ConvTranspose2d [Cin][Cout / 4][2][2] ->
+ * the 1x1 filter with rows (dy * 2 + dx) * Cout / 4 + co that the deconvolution runs as.  bias_packed (optional): bias (or zeros
+ * when bias == NULL) padded to a multiple of 128 entries. */
+int apse_mask_pack_weight(const float* w_dev, const float* bias_dev, int kind, int Cout, int Cin, int KH, int KW, float* packed_dev,
+                          float* bias_packed_dev, void* stream);
+/* y = conv(x) (+ bias, ReLU) on the inference kernel (conv_igemm_f32), tile shape and K split chosen as a max_batch = 1 context
+ * chooses them for its mask head: the result does not depend on n and equals that context's bits.  x [n][H][W][Cin]; deconv != 0:
+ * a 1x1 layer with Cout = 4 x channels whose output is scattered to [n][2H][2W][Cout / 4]. */
+int apse_mask_conv_forward(const float* x_dev, const float* w_packed_dev, const float* bias_packed_dev, int n, int H, int W, int Cin,
+                           int Cout, int KH, int KW, int stride, int pad, int relu, int deconv, float* y_dev, float* ws,
+                           size_t ws_bytes, void* stream);
+/* The 256 -> 256 3x3 layers (stride 1, pad 1) on [n][14][14][256]: y = conv(x) (+ bias, ReLU) from a kind 0 pack (forward of
+ * mask_fcnN) or a kind 1 pack (its data gradient), on the exact-f32 MFMA with the reduction summed as 36 chains of 64 (the
+ * inference kernel runs one long chain per K split; the forward error of training feeds the ReLU masks of the gradients). */
+int apse_mask_conv3x3(const float* x_dev, const float* w_packed_dev, const float* bias_packed_dev, int n, int relu, float* y_dev,
+                      void* stream);
+/* g = y > 0 ? dy : 0 over `elems` floats (a multiple of 4; g may alias dy). */
+int apse_mask_relu_grad(const float* y_dev, const float* dy_dev, long long elems, float* g_dev, void* stream);
+/* db [256] = column sums of g [rows][256]: rows in ascending order inside at most 512 slices, slices in ascending order. */
+int apse_mask_bias_grad(const float* g_dev, long long rows, float* db_dev, float* ws, size_t ws_bytes, void* stream);
+/* Weight gradient as an implicit GEMM on the exact-f32 MFMA, split over the RoI pixels, partial tiles added in chunk order.
+ * kind 0 (3x3, stride 1, pad 1): a = dY [n][14][14][256], b = X [n][14][14][256] -> dw [256][256][3][3] (OIHW).
+ * kind 1 (deconvolution 2x2, stride 2): a = X [n][14][14][256], b = dY [n][28][28][256] -> dw [256][256][2][2] ([Cin][Cout][2][2]). */
+int apse_mask_wgrad(const float* a_dev, const float* b_dev, int n, int kind, float* dw_dev, float* ws, size_t ws_bytes, void* stream);
+/* mask_rcnn_loss: logits [n][28][28][K], classes [n] (ignored when K == 1), targets [n][28][28] bytes (non-zero = inside) ->
+ * out4 = {loss_mask, accuracy, false_positive, false_negative}. */
+int apse_mask_loss_forward(const float* logits_dev, int K, const int* classes_dev, const uint8_t* targets_dev, int n, float* out4_dev,
+                           void* ws, size_t ws_bytes, void* stream);
+/* d [n][28][28] = grad_loss[0] (device scalar; NULL: 1) x (sigmoid(x) - t) / (n x 784) on the ground-truth class channel (the other
+ * channels' gradient is 0 and is not stored). */
+int apse_mask_loss_backward(const float* logits_dev, int K, const int* classes_dev, const uint8_t* targets_dev, int n,
+                            const float* grad_loss_dev, float* d_dev, void* stream);
+/* Predictor backward from d: g5 [n][28][28][256] = a5 > 0 ? d x w_pred[class] : 0 (the gradient at the deconvolution's
+ * pre-activation), dw [K][256] and db [K] (classes without a RoI: exactly 0).  a5 = the deconvolution's output. */
+int apse_mask_predictor_backward(const float* d_dev, const float* a5_dev, const int* classes_dev, const float* w_pred_dev, int n, int K,
+                                 float* g5_dev, float* dw_dev, float* db_dev, float* ws, size_t ws_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
