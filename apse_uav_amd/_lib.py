@@ -14,7 +14,10 @@ import numpy as np
 _HERE = os.path.dirname(os.path.abspath(__file__))
 # APSE_HIP_LIB: another build of the same sources (A/B measurements of a compile-time switch, tools/gpu_ab.sh); the
 # default is the in-tree library
-LIB_PATH = os.environ.get("APSE_HIP_LIB") or os.path.join(_HERE, "libapse_hip.so")
+_TREE_LIB = os.path.join(_HERE, "libapse_hip.so")
+LIB_PATH = os.environ.get("APSE_HIP_LIB") or _TREE_LIB
+# entries that only tools/ use: a build from before they existed may still be loaded through APSE_HIP_LIB (load())
+TOOL_ENTRIES = ("apse_winograd_pack_filter", "apse_winograd_conv2d")
 
 APSE_OK = 0
 
@@ -121,6 +124,8 @@ def load():
         "apse_conv_packed_elems": ([C.POINTER(ConvDesc)], sz),
         "apse_conv_pack_weight": ([C.POINTER(ConvDesc), vp, i, vp, vp], i),
         "apse_conv2d": ([C.POINTER(ConvDesc), vp, vp, vp, vp, vp, vp, sz, vp], i),
+        "apse_winograd_pack_filter": ([vp, i, i, vp], i),
+        "apse_winograd_conv2d": ([C.POINTER(ConvDesc), vp, vp, vp, vp, vp], i),
         "apse_maxpool3x3s2": ([vp, vp, i, i, i, i, vp], i),
         "apse_maxpool3x3s2_typed": ([vp, vp, i, i, i, i, i, vp], i),
         "apse_roi_align": ([C.POINTER(vp), C.POINTER(i), C.POINTER(i), vp, i, i, i, vp, vp], i),
@@ -180,6 +185,8 @@ def load():
         "apse_mask_predictor_backward": ([vp, vp, vp, vp, i, i, vp, vp, vp, vp, sz, vp], i),
     }
     for name, (args, ret) in sig.items():
+        if name in TOOL_ENTRIES and LIB_PATH != _TREE_LIB and not hasattr(lib, name):
+            continue                       # an older build loaded through APSE_HIP_LIB for an A/B run
         fn = getattr(lib, name)            # AttributeError here = ABI drift between header and library
         fn.argtypes = args
         fn.restype = ret
@@ -191,7 +198,7 @@ EXPORTS = ["apse_create", "apse_destroy", "apse_last_error", "apse_version", "ap
            "apse_set_resize_tables", "apse_set_camera", "apse_preprocess_frames", "apse_preprocess_images", "apse_backbone", "apse_rpn", "apse_rpn_levels",
            "apse_box_head", "apse_set_detections", "apse_mask_tail", "apse_embed", "apse_forward", "apse_results_describe",
            "apse_read_results", "apse_read_results_begin", "apse_read_results_end", "apse_copy_mask_window", "apse_copy_mask_windows", "apse_host_copy", "apse_feature_shape", "apse_export_feature", "apse_debug_tensor",
-           "apse_flops", "apse_profile", "apse_profile_read", "apse_conv_packed_elems", "apse_conv_pack_weight", "apse_conv2d", "apse_maxpool3x3s2",
+           "apse_flops", "apse_profile", "apse_profile_read", "apse_conv_packed_elems", "apse_conv_pack_weight", "apse_conv2d", "apse_winograd_pack_filter", "apse_winograd_conv2d", "apse_maxpool3x3s2",
            "apse_maxpool3x3s2_typed", "apse_roi_align", "apse_roi_align_typed", "apse_roi_pool", "apse_roi_features", "apse_nms_rank", "apse_mask_centroid_dense", "apse_mask_closest_dense",
            "apse_l2_normalize", "apse_sqdist", "apse_undistort_gamma", "apse_lab_tables_host", "apse_resize_normalize", "apse_replay_create", "apse_replay_destroy",
            "apse_replay_step", "apse_replay_packed", "apse_replay_max_id", "apse_replay_next_id", "apse_render_workspace_bytes",

@@ -18,6 +18,12 @@
 //   - the U slice [16][64 co][8] is one contiguous 2 KiB run per xi (global layout [Cin/8][16][Cout][8])
 //   - LDS rows are 8 floats (32 B): the 16-byte half a lane reads is XOR-swizzled with (row >> 3) & 1, so the ds_read_b128
 //     fragment reads (lane half h takes channels 4 h .. 4 h + 3 for the four k-steps) are bank-conflict-free
+// Schedule of the k loop (one basic block per slice; 256 VGPRs, no scratch, 2 waves per SIMD): slice s + 1 sits in one register set,
+// fetched a slice ahead; its U hand-over, row transform and column transform + V hand-over are pinned in front of MFMA groups
+// 1, 2 and 3 of slice s (sched_barrier), each followed by the fetch of slice s + 2 into the registers it freed.  The second
+// xi's fragments are read behind the first xi's MFMAs, and the slice's last MFMA group runs after the barrier, behind the
+// next slice's first fragment reads.  Every accumulator still takes its products channel-ascending, one k-step after the
+// other, and the transforms keep their operation order: the bits are those of the unscheduled loop.
 // Epilogue: per 32-channel half of the N tile the accumulators go to LDS as [16][64 t][32 co]; each thread then owns one
 // tile x 4 channels, applies A^T . A, bias, ReLU and stores the 2x2 pixels as dwordx4 (pixels past H / W are dropped).
 // No split-K, no atomics: a tile's result depends on nothing but its inputs (not on batch, grid or history).
@@ -29,6 +35,10 @@ constexpr int WT = WTR * WTC;
 constexpr int WN = 64;                    // output channels per block
 constexpr int KC = 8;                     // channels per k-slice
 constexpr int NTHR = 512;
+// MFMA group (0..6 of a slice's eight) in front of which each piece of the next slice's staging is issued: the U hand-over,
+// the row transform, the column transform + V hand-over.  Measured at out2 shape: 1/2/3 353.7 us, 0/1/2 361.4, 2/3/4 358.4,
+// 0/2/4 368.4 (HISTORY.md)
+constexpr int G_U = 1, G_ROWS = 2, G_V = 3;
 constexpr int SLICE_F = 16 * WT * KC;     // floats of V (and of U: WN == WT) per k-slice buffer
 constexpr size_t WINO_LDS = (size_t)2 * 2 * SLICE_F * sizeof(float);     // [2 buffers][V, U] = 128 KiB
 static_assert(WN == WT, "V and U slices share one size");
@@ -42,7 +52,7 @@ __global__ __launch_bounds__(NTHR) void conv_winograd_f32(const ConvParams p) {
     float* Cs = reinterpret_cast<float*>(smem);          // epilogue view [16][WT][32]
 
     const int tid = threadIdx.x;
-    const int lane = tid & 63, wave = tid >> 6;
+    const int lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int fr = lane & 31, fh = lane >> 5;
 
     // block -> (image, tile strip, N tile); blocks are dealt round-robin over 8 XCDs: give each XCD a contiguous range so
@@ -66,14 +76,19 @@ __global__ __launch_bounds__(NTHR) void conv_winograd_f32(const ConvParams p) {
     const int nsteps = C / KC;
 
     // ---- staging roles
-    // input: thread = (transform row i, tile t, channel group cg); rows ra / rb of the 4x4 tile give row i of B^T d
-    const int cg = tid & 1, t = (tid >> 1) & (WT - 1), ti = tid >> 7;
+    // input: thread = (transform row i, tile t, channel group cg); rows ra / rb of the 4x4 tile give row i of B^T d.  The row
+    // index i = wave >> 1 is wave-uniform: rows ra / rb combine as ra + sgn * rb with sgn = +-1 in an SGPR (the product is
+    // exact, so the fma rounds exactly like the add / subtract it stands for)
+    const int cg = tid & 1, t = (tid >> 1) & (WT - 1), ti = wave >> 1;
     const int ra = ti == 0 ? 0 : (ti == 2 ? 2 : 1);
     const int rb = ti == 0 ? 2 : (ti == 1 ? 2 : (ti == 2 ? 1 : 3));
+    const float sgn = ti == 1 ? 1.f : -1.f;
     const int iy_a = oy0 + 2 * (t / WTC) - 1 + ra, iy_b = oy0 + 2 * (t / WTC) - 1 + rb;
     const int ix0 = ox0 + 2 * (t % WTC) - 1;
     const __amdgpu_buffer_rsrc_t xrsrc =
         __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(p.x), 0, (int)((((unsigned)(p.B * p.H * p.W)) << p.cin_log2) * 4u), 0x00020000);
+    // an empty range for the fetches of slices past the last one, which the loop issues unconditionally: zeros, no memory access
+    const __amdgpu_buffer_rsrc_t xnone = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(p.x), 0, 0, 0x00020000);
     // byte offset of channel 0 of the thread's channel group at each of its 8 taps; a tap outside the image gets a base past
     // any range (the launcher keeps the activation tensor below 2 GiB), so every k-slice's load of it returns zeros
     unsigned xoff[2][4];
@@ -87,42 +102,54 @@ __global__ __launch_bounds__(NTHR) void conv_winograd_f32(const ConvParams p) {
             xoff[r][c] = in ? ((((unsigned)((b * p.H + iy) * p.W + ix)) << p.cin_log2) + (unsigned)(cg * 4)) * 4u : 0x80000000u;
         }
     }
-    // U: four 16-byte pieces per thread, piece q = tid + 512 k: xi = q >> 7, row co = (q >> 1) & 63, half q & 1
-    const float* ubase = p.wu + (size_t)n0 * KC;
-    const size_t ustep = (size_t)16 * p.Cout * KC;        // floats per k-slice of the global U
+    // U: four 16-byte pieces per thread, piece q = tid + 512 k: xi = q >> 7, row co = (q >> 1) & 63, half q & 1.  Read through
+    // a descriptor of the whole U (16 * Cout * Cin floats, slice-major): a slice past the last one is out of its range
+    const __amdgpu_buffer_rsrc_t ursrc =
+        __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(p.wu), 0, (int)((((unsigned)(16 * p.Cout)) << p.cin_log2) * 4u), 0x00020000);
+    const unsigned ustep = (unsigned)(16 * p.Cout * KC * 4);     // bytes per k-slice of the global U
+    unsigned uoff[4], ulds[4];
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+        const int q = tid + NTHR * k;
+        const int xi = q >> 7, co = (q >> 1) & 63, h = q & 1;
+        uoff[k] = (unsigned)(((xi * p.Cout + n0 + co) * KC + h * 4) * 4);
+        ulds[k] = (unsigned)((xi * WN + co) * KC + ((h ^ ((co >> 3) & 1)) * 4));
+    }
+    const int vlds = (4 * ti * WT + t) * KC + (cg ^ ((t >> 3) & 1)) * 4;
 
+    // one register set: a slice is fetched one slice ahead of the MFMAs that use it and handed to LDS inside the MFMA stream
+    // of the slice before (see the loop)
     f32x4 xr[2][4], ur[4];
-    auto fetch = [&](int s) {
+    auto fetch_u = [&](int s) {
+        const unsigned kb = (unsigned)s * ustep;
+#pragma unroll
+        for (int k = 0; k < 4; ++k) ur[k] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(ursrc, (int)(uoff[k] + kb), 0, 0));
+    };
+    auto fetch_x = [&](int s) {
         const unsigned kb = (unsigned)(s * KC * 4);
+        const __amdgpu_buffer_rsrc_t rs = s < nsteps ? xrsrc : xnone;
 #pragma unroll
         for (int r = 0; r < 2; ++r)
 #pragma unroll
             for (int c = 0; c < 4; ++c)
-                xr[r][c] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(xrsrc, (int)(xoff[r][c] + kb), 0, 0));
-        const float* us = ubase + (size_t)s * ustep;
-#pragma unroll
-        for (int k = 0; k < 4; ++k) {
-            const int q = tid + NTHR * k;
-            const int xi = q >> 7, co = (q >> 1) & 63, h = q & 1;
-            ur[k] = *reinterpret_cast<const f32x4*>(us + ((size_t)xi * p.Cout + co) * KC + h * 4);
-        }
+                xr[r][c] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(rs, (int)(xoff[r][c] + kb), 0, 0));
     };
-    auto stage = [&](int buf) {
-        // row i of B^T d (4 pixels x 4 channels), then the column combinations: V[4 i + j]
-        f32x4 x[4];
+    auto write_u = [&](int buf) {
 #pragma unroll
-        for (int c = 0; c < 4; ++c) x[c] = ti == 1 ? xr[0][c] + xr[1][c] : xr[0][c] - xr[1][c];
-        const f32x4 v[4] = {x[0] - x[2], x[1] + x[2], x[2] - x[1], x[1] - x[3]};
-        const int sw = (cg ^ ((t >> 3) & 1)) * 4;
+        for (int k = 0; k < 4; ++k) *reinterpret_cast<f32x4*>(Us + buf * SLICE_F + ulds[k]) = ur[k];
+    };
+    // row i of B^T d (4 pixels x 4 channels), in place in xr[0]
+    auto xform_rows = [&]() {
 #pragma unroll
-        for (int j = 0; j < 4; ++j)
-            *reinterpret_cast<f32x4*>(Vs + buf * SLICE_F + ((4 * ti + j) * WT + t) * KC + sw) = v[j];
+        for (int c = 0; c < 4; ++c)
 #pragma unroll
-        for (int k = 0; k < 4; ++k) {
-            const int q = tid + NTHR * k;
-            const int xi = q >> 7, co = (q >> 1) & 63, h = q & 1;
-            *reinterpret_cast<f32x4*>(Us + buf * SLICE_F + (xi * WN + co) * KC + ((h ^ ((co >> 3) & 1)) * 4)) = ur[k];
-        }
+            for (int e = 0; e < 4; ++e) xr[0][c][e] = __builtin_fmaf(xr[1][c][e], sgn, xr[0][c][e]);
+    };
+    // the column combinations: V[4 i + j]
+    auto write_v = [&](int buf) {
+        const f32x4 v[4] = {xr[0][0] - xr[0][2], xr[0][1] + xr[0][2], xr[0][2] - xr[0][1], xr[0][1] - xr[0][3]};
+#pragma unroll
+        for (int j = 0; j < 4; ++j) *reinterpret_cast<f32x4*>(Vs + buf * SLICE_F + vlds + j * WT * KC) = v[j];
     };
 
     f32x16 acc[2][2][2];
@@ -135,32 +162,55 @@ __global__ __launch_bounds__(NTHR) void conv_winograd_f32(const ConvParams p) {
 #pragma unroll
                 for (int v = 0; v < 16; ++v) acc[a][i][j][v] = 0.f;
 
-    fetch(0);
-    stage(0);
+    fetch_u(0);
+    fetch_x(0);
+    write_u(0);
+    xform_rows();
+    write_v(0);
+    __builtin_amdgcn_sched_barrier(0);                   // the loop counts on this order: U of a slice is requested before its taps
+    fetch_u(1);
+    __builtin_amdgcn_sched_barrier(0);
+    fetch_x(1);
     __syncthreads();
+    // The k loop.  Slice s is multiplied from LDS buffer s & 1 while slice s + 1, fetched during slice s - 1, goes through the
+    // transform into the other buffer and slice s + 2 is requested, each piece pinned into its own gap of the MFMA stream: the
+    // two waves of a SIMD and the eight waves of the block do not all stop multiplying at once, and the last MFMA group of a
+    // slice runs behind the barrier, over the next slice's first fragment reads.  One basic block per slice: the last two slices hand over
+    // and fetch past the end (zeros into a buffer nobody reads) rather than branch.
     const int fsw = (fh ^ ((fr >> 3) & 1)) * 4;          // swizzled half of the fragment rows (row & 15 == fr & 15)
+    const int frag = (2 * wave * WT + fr) * KC + fsw;
+    f32x4 af[2][2], bf[2][2];
+    auto read_frags = [&](int buf, int a) {
+#pragma unroll
+        for (int i = 0; i < 2; ++i) af[a][i] = *reinterpret_cast<const f32x4*>(Vs + buf * SLICE_F + frag + (a * WT + 32 * i) * KC);
+#pragma unroll
+        for (int j = 0; j < 2; ++j) bf[a][j] = *reinterpret_cast<const f32x4*>(Us + buf * SLICE_F + frag + (a * WN + 32 * j) * KC);
+    };
+    auto mfma_group = [&](int a, int k) {
+#pragma unroll
+        for (int i = 0; i < 2; ++i)
+#pragma unroll
+            for (int j = 0; j < 2; ++j)
+                acc[a][i][j] = __builtin_amdgcn_mfma_f32_32x32x2f32(af[a][i][k], bf[a][j][k], acc[a][i][j], 0, 0, 0);
+    };
+    read_frags(0, 0);
     for (int s = 0; s < nsteps; ++s) {
         const int buf = s & 1;
-        const bool more = s + 1 < nsteps;
-        if (more) fetch(s + 1);                          // in flight across this slice's MFMAs
+        read_frags(buf, 1);                              // lands behind the first xi's MFMAs
 #pragma unroll
-        for (int a = 0; a < 2; ++a) {
-            const int xi = 2 * wave + a;
-            f32x4 af[2], bf[2];
-#pragma unroll
-            for (int i = 0; i < 2; ++i) af[i] = *reinterpret_cast<const f32x4*>(Vs + buf * SLICE_F + (xi * WT + 32 * i + fr) * KC + fsw);
-#pragma unroll
-            for (int j = 0; j < 2; ++j) bf[j] = *reinterpret_cast<const f32x4*>(Us + buf * SLICE_F + (xi * WN + 32 * j + fr) * KC + fsw);
-#pragma unroll
-            for (int k = 0; k < 4; ++k)
-#pragma unroll
-                for (int i = 0; i < 2; ++i)
-#pragma unroll
-                    for (int j = 0; j < 2; ++j)
-                        acc[a][i][j] = __builtin_amdgcn_mfma_f32_32x32x2f32(af[i][k], bf[j][k], acc[a][i][j], 0, 0, 0);
+        for (int g = 0; g < 7; ++g) {                    // MFMA groups 0..6 of the slice: (xi, k-step) = (g >> 2, g & 3)
+            __builtin_amdgcn_sched_barrier(0);
+            if (g == G_U) { write_u(buf ^ 1); fetch_u(s + 2); }
+            if (g == G_ROWS) xform_rows();
+            if (g == G_V) { write_v(buf ^ 1); fetch_x(s + 2); }
+            __builtin_amdgcn_sched_barrier(0);
+            mfma_group(g >> 2, g & 3);
         }
-        if (more) stage(buf ^ 1);                        // buf ^ 1 was last read before the previous barrier
-        __syncthreads();
+        __builtin_amdgcn_sched_barrier(0);
+        __syncthreads();                                  // buf ^ 1 is complete; buf is in registers and may be rewritten
+        read_frags(buf ^ 1, 0);                          // the next slice's first fragments, behind this slice's last group
+        __builtin_amdgcn_sched_barrier(0);
+        mfma_group(1, 3);
     }
 
     // ---- epilogue, one 32-channel half of the N tile at a time

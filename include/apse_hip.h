@@ -237,6 +237,13 @@ size_t apse_conv_packed_elems(const apse_conv_desc* d);
 int apse_conv_pack_weight(const apse_conv_desc* d, const float* w_oihw, int cin_real, const float* scale, float* packed);
 int apse_conv2d(const apse_conv_desc* d, const float* x_dev, const float* w_packed_dev, const float* bias_dev,
                 const float* res_dev, float* y_dev, float* ws_dev, size_t ws_bytes, void* stream);
+/* One layer through the fused f32 Winograd F(2x2,3x3) kernel the f32 plan uses for its p2 / p3 3x3 layers (a test / tool helper,
+ * like apse_conv2d, which keeps the direct kernels).  apse_winograd_pack_filter: OIHW host filter [Cout][Cin][3][3], Cin a power of
+ * two >= 8 -> U = G g G^T, 16 * Cout * Cin floats on the host, the bytes a context uploads.  apse_winograd_conv2d: f32 NHWC in /
+ * out, 3x3 / stride 1 / pad 1, Cout a multiple of 64, no residual, every storage type 0; anything else is APSE_E_INVALID. */
+int apse_winograd_pack_filter(const float* w_oihw, int Cout, int Cin, float* packed);
+int apse_winograd_conv2d(const apse_conv_desc* d, const float* x_dev, const float* wu_dev, const float* bias_dev, float* y_dev,
+                         void* stream);
 int apse_maxpool3x3s2(const float* x_dev, float* y_dev, int B, int H, int W, int C, void* stream);
 /* Same on a storage type (0 f32, 1 bf16, 2 f16): the form the 16-bit modes run after the stem. */
 int apse_maxpool3x3s2_typed(const void* x_dev, void* y_dev, int B, int H, int W, int C, int storage, void* stream);
