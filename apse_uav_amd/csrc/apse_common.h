@@ -141,13 +141,6 @@ __device__ __forceinline__ void apse_st4(void* base, size_t idx, f32x4 v, int st
 // Values are discarded.
 struct ApseWarm { f32x4 v[4]; };
 
-// C4 (Res5ROIHeads) RPN on res4: the head rows and the 15 cell anchors (select_nms.hip c4_rpn_select; built by detector.hip)
-struct C4Rpn {
-    const float* head;     // [B][H*W][ld]: channels 0..14 objectness (anchor a), 15 + 4 a + j deltas
-    int H, W, ld, stride;
-    int n, k;              // H*W*15, min(pre_topk, n)
-    float base[15][4];     // cell anchors, a = 3 * size + ratio
-};
 __device__ __forceinline__ void apse_warm_issue(ApseWarm& wv, const void* w, unsigned bytes, unsigned blk, unsigned nblk, int tid) {
     const unsigned stride = (bytes / nblk + 1023u) & ~1023u;
     const unsigned len = stride > 16384u ? 16384u : stride;

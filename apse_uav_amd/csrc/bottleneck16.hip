@@ -26,7 +26,7 @@
 // stage is fetched global -> registers while the previous one computes and handed to LDS between two barriers.  (First form of
 // this kernel: 15 stages of 8 KB, double-buffered, one barrier each -- with 0.1-0.3 us of MFMA work per stage every stage waited
 // out an L2 round trip: 28 us per tile.)  The sequence is the same for every tile, so the stream runs across tile seams.
-#include "apse_common.h"
+#include "apse_kernels.h"
 #include <type_traits>
 
 #define BN_TH 8

@@ -1,449 +1,36 @@
-// libapse_hip.so context: weights, buffers, launch plan and the C ABI of include/apse_hip.h.
-// Host-side C++ only orchestrates; all arithmetic is in the HIP kernels of this directory.
+// libapse_hip.so context: run_plan (the per-forward launch sequence) and the context's C ABI of include/apse_hip.h.
+// The plan it runs is built in plan.hip; the stateless operators of the ABI are in ops.hip (detector_ctx.h says which file
+// holds what).  Host-side C++ only orchestrates; all arithmetic is in the HIP kernels of this directory.
 // One context per device/process rank; the caller's stream carries every launch (no hidden syncs
 // except apse_read_results).
-#include "apse_common.h"
-#include "../../include/apse_hip.h"
-#include "preproc_pixel.h"
+#include "detector_ctx.h"
 
 #include <math.h>
-#include <stdio.h>
 #include <string.h>
 
-#include <map>
-#include <mutex>
-#include <string>
-#include <vector>
-
-// ---- kernels' extern "C" launchers (defined in the other .hip files)
-struct RpnLevel { const float* head; int H, W, stride; int n; int k; float base[3][4]; };
-struct RpnLevels { RpnLevel lv[5]; int head_ld; int pre_topk; };
-struct TopkJob { int kind; int level; int begin, count; int nsrc; int src[4]; int src_count[4]; int dst; int dst_count; };
-struct FpnMaps { const void* p[4]; int H[4], W[4]; float scale[4]; int st; };
-struct PasteParams {
-    const float* boxes; const int* cls; const int* total; const float* logits; int M, ldc; float sx, sy; int out_h, out_w;
-    int words_per_row; float thresh; float* boxes_out; int* valid; int* rect; uint64_t* bits; unsigned long long* sums;
-};
-extern "C" {
-int apse_k_pil_resize(const uint8_t*, uint8_t*, void*, int, uint8_t*, const int*, const int*, int, const int*, const int*, int, int,
-                      int, int, int, int, int, int, const float*, const UndistortParams*, const LabTables*, const void*, const int*, int, hipStream_t);
-int apse_k_undistort_build_map_compact(const UndistortParams*, void*, int*, hipStream_t);
-int apse_k_chw_norm(const float*, void*, int, int, int, int, int, int, const float*, hipStream_t);
-int apse_k_maxpool3x3s2(const void*, void*, int, int, int, int, int, hipStream_t);
-bool apse_assoc_fc_ok(int K, int N);
-int apse_k_assoc_fc(const float*, const float*, const float*, float*, const int*, int, int, int, float*, float*, hipStream_t);
-int apse_k_stem_pool16(const void*, const uint16_t*, const float*, void*, int, int, int, int, hipStream_t, hipEvent_t, hipEvent_t);
-int apse_k_subsample2(const void*, void*, int, int, int, int, int, hipStream_t);
-int apse_k_bottleneck64_fused16(const void*, const void*, void*, const uint16_t*, const float*, const uint16_t*, const float*,
-                                const uint16_t*, const float*, int, int, int, int, int, hipStream_t, hipEvent_t, hipEvent_t);
-int apse_k_nhwc_to_nchw(const void*, float*, int, int, int, int, hipStream_t);
-int apse_k_rpn_topk_stage(const RpnLevels*, const TopkJob*, int, uint64_t*, int, int, uint32_t*, hipStream_t);
-int apse_k_rpn_decode(const RpnLevels*, int, const uint64_t*, int, const int*, float, float, float, float*, float*, int*,
-                      uint32_t*, int, int, hipStream_t);
-int apse_k_nms_percat(const float*, const float*, const int*, int, int, int, const uint32_t*, float, int*, int*, int,
-                      void*, int, int, int, hipStream_t);
-size_t apse_nms_scratch_bytes(int slots);
-int apse_k_rank_final(const float*, const float*, int, const int*, const int*, int, int, float*, float*, int*, int*, uint32_t*,
-                      int, hipStream_t);
-int apse_k_box_candidates(const float*, int, int, const float*, const int*, int, float, float, float, const float*, float,
-                          float*, float*, int*, uint32_t*, float*, int, hipStream_t);
-int apse_k_box_candidates_wide(const float*, int, int, const float*, const int*, int, float, float, float, const float*, float,
-                               float*, float*, int*, uint32_t*, float*, int*, int*, int, hipStream_t);
-int apse_k_nms_lists(const float*, const float*, int, const int*, int*, int, const uint32_t*, float, int*, int*, int, void*, int,
-                     hipStream_t);
-int apse_k_rank_wide(const float*, const float*, int, const int*, const int*, int, int, float*, float*, int*, int*, int, hipStream_t);
-int apse_k_pack_detections(const float*, const float*, const int*, const int*, int, int, int, float*, float*, int*, int*,
-                           int*, int*, int*, unsigned long long*, hipStream_t);
-int apse_k_roi_align(const FpnMaps*, const float*, const int*, const int*, const int*, int, int, int, void*, int, hipStream_t);
-int apse_k_mask_roi_index(int*, int, hipStream_t);
-int apse_k_roi_pool(const void*, int, int, int, const float*, const int*, const int*, int, int, float, float*, int, int, hipStream_t);
-int apse_k_mask_resize(const uint8_t*, int, int, int, int, int, float*, hipStream_t);
-int apse_k_round16(const float*, uint16_t*, size_t, int, hipStream_t);
-int apse_k_roi_align_masked(const void*, int, int, int, int, const float*, const float*, int, int, int, float, float*, hipStream_t);
-int apse_k_l2_normalize(const float*, float*, int, const int*, int, hipStream_t);
-int apse_k_sqdist(const float*, const float*, int, int, int, float*, hipStream_t);
-int apse_k_mask_paste(const PasteParams*, int, unsigned long long*, int, hipStream_t);
-int apse_k_closest_points(const uint64_t*, const int*, const int*, const unsigned long long*, const int*, const int*, const int*, int,
-                          int, int, int, int, int*, int*, unsigned long long*, int, hipStream_t);
-int apse_k_closest_single(const uint64_t*, int, int, int, float, float, unsigned long long*, hipStream_t);
-int apse_k_undistort_gamma(const UndistortParams*, const uint8_t*, uint8_t*, const LabTables*, int, hipStream_t);
-int apse_k_bits_to_dense(const uint64_t*, const int*, int, int, int, uint8_t*, hipStream_t);
-int apse_k_copy_mask_windows(const uint64_t*, uint64_t*, int, const long long*, const long long*, const int*, const int*, int, hipStream_t);
-int apse_k_dense_to_bits(const uint8_t*, int, int, int, uint64_t*, unsigned long long*, hipStream_t);
-size_t apse_c4_nms_scratch_bytes(int);
-int apse_k_c4_rpn(const C4Rpn*, int, int, float, float, float, float, float*, float*, int*, void*, float*, float*, int*, int*, int,
-                  hipStream_t);
-int apse_k_roi_align_c4(const float*, int, int, int, float, const float*, const int*, const int*, const int*, int, int, int, float*,
-                        hipStream_t);
-int apse_k_roi_pool_c4(const float*, int, int, int, const float*, const int*, const int*, int, int, float, float*, hipStream_t);
-int apse_k_mean_cells(const float*, int, int, int, float*, hipStream_t);
-}
-
 static std::string g_create_error;
-#define NMS_SLOT 1024
-#define APSE_NARROW_CLASSES 6     // up to this many classes: box_candidates / rank_merge (one thread per ROI, ncat <= 8)
-#define APSE_EV_HALF 1024    // HIP events per half of the profiling pool (one pair per timed launch)
-#define APSE_WINO_MIN_BLOCKS 128  // f32 Winograd layers: fewest blocks per image (see add_conv)
-#define APSE_EXPECTED_DETS 8      // list length the packed-list GEMMs are shaped for (static: see add_conv)
 
-struct HostW { std::vector<float> v; std::vector<int64_t> shape; };
-struct Tens { float* p = nullptr; int H = 0, W = 0, C = 0; int st = 0; };   // per-item NHWC dims; st: 0 f32, 1 bf16, 2 f16 storage
-
-struct ConvStep {
-    ConvParams p;          // B/M filled at launch
-    int b_mult = 1;        // items per image (1, post_topk, dets_per_image)
-    int fixed_items = 0;   // > 0: the launch always covers this many items (a tensor laid out for max_batch: merged RPN head)
-    int cfg = 0;
-    double flops_per_item = 0;   // algorithmic 2*MACs per item (one image / one roi / one detection)
-    int count_kind = 0;    // 0 none, 1 prop_cnt[0] (batch 1 only), 2 packed total
-    void* pool_y = nullptr;   // != nullptr: the stem of the 16-bit modes, run as stem_s2d_pool16 (conv + ReLU + 3x3/2 max-pool) into this map
-    std::string name;
-};
-enum StepKind { S_CONV, S_MAXPOOL, S_SUBSAMPLE, S_BNECK };
-// S_BNECK: a whole 64-channel bottleneck as one launch (bottleneck16.hip); c = its conv1 (name, flops of all three), c2 / c3 the others
-struct Step { StepKind kind; ConvStep c; const float* x; float* y; int H, W, C; int st = 0; ConvParams p2, p3; };
-
-struct apse_ctx {
-    apse_config cfg;
-    std::string err;
-    bool f32_winograd = true;    // APSE_F32_WINOGRAD=0 (read once, at apse_create): the named f32 3x3 layers keep the direct kernel
-    std::map<std::string, HostW> hw;
-    bool finalized = false;
-    int PH = 0, PW = 0;
-    std::vector<void*> allocs;
-    std::map<std::string, Tens> t;
-    std::vector<Step> backbone, rpnhead, boxhead, maskhead, embedfc;
-    float* ws = nullptr; size_t ws_floats = 0; int* tile_cnt = nullptr;
-    // resize tables
-    int *hb = nullptr, *hc = nullptr, *vb = nullptr, *vc = nullptr; int hk = 0, vk = 0; uint8_t* rs_tmp = nullptr;
-    int rs_pitch = 0;
-    int* hcT = nullptr;                                  // horizontal taps tap-major [8][image_w], zero past a pixel's count (hk <= 8)
-    // rpn
-    RpnLevels rl_host; RpnLevels* rl_dev = nullptr;
-    std::vector<std::vector<TopkJob>> stages; std::vector<TopkJob*> stage_dev; int nslots = 0; uint64_t* lists = nullptr;
-    int final_slot_host[5]; int* final_slot_dev = nullptr;
-    float *dec_boxes = nullptr, *dec_scores = nullptr; int* dec_valid = nullptr; uint32_t* maxc = nullptr;   // maxc[2*B]: rpn, box
-    int *keep_idx = nullptr, *keep_cnt = nullptr; void* nms_scratch = nullptr;
-    float *props = nullptr, *prop_scores = nullptr; int *prop_entry = nullptr;
-    // box head
-    FpnMaps fm;
-    float *cand_boxes = nullptr, *cand_scores = nullptr, *probs = nullptr; int* cand_valid = nullptr;
-    int pred_ld = 32;                                    // row length of the fused predictor output: round_up(5 K + 1, 32)
-    bool wide = false;                                   // num_classes > APSE_NARROW_CLASSES: the wide box-inference kernels
-    int *cls_list = nullptr, *cls_cnt = nullptr;         // wide: class-major candidate lists [B][K][P] and counts [B][K]
-    float *det_boxes = nullptr, *det_scores = nullptr; int *det_entry = nullptr, *det_cnt = nullptr;
-    // results block (device) and layout
-    apse_results_layout lay; uint8_t* res = nullptr;
-    // mask tail
-    uint64_t* bits2[2] = {nullptr, nullptr}; int bits_cur = 0, bits_read = 0;   // mask bit planes, alternating per forward (see apse_mask_tail)
-    unsigned long long* sums = nullptr; int wpr = 0; bool sums_dirty = false;
-    float* emb_raw = nullptr;
-    float* ws_assoc = nullptr;      // [K / 128][max detections][embed_dim]: K slices of the association FC (apse_k_assoc_fc), or nullptr
-    float* rf_mask = nullptr; size_t rf_mask_floats = 0;      // apse_roi_features: masks at p2 resolution (grown on demand)
-    int* mrf_idx = nullptr; size_t mrf_cap = 0;               // apse_mask_roi_features: image index per RoI + live count (grown on demand)
-    bool box_maxc_clean = false;
-    UndistortParams cam; bool cam_on = false; LabTables* cam_lut = nullptr; void* cam_map = nullptr; bool cam_map_ok = false;     // apse_set_camera: fused undistort + gamma in apse_preprocess_frames
-    int hint_total = 8;      // detections seen in the previous forward: sizes the GRID of the packed-list GEMMs, nothing else
-    hipEvent_t read_ev = nullptr; void* read_pending = nullptr;      // apse_read_results_begin / _end
-    // apse_set_detections: two pinned staging blocks, each guarded by the event behind its H2D copies, so the call only enqueues
-    // (a sequence driver puts the next given-boxes forward behind apse_read_results_begin like any other forward)
-    uint8_t* given_host[2] = {nullptr, nullptr}; hipEvent_t given_ev[2] = {nullptr, nullptr}; int given_k = 0;
-    // per-kernel profiling with HIP events on the caller's stream (bench.py roofline)
-    bool prof_on = false; std::vector<hipEvent_t> ev_pool; int ev_used = 0;
-    struct Pending { int cfg; double flops_per_item; int count_kind; int b_mult; int batch; int e0, e1; };
-    std::vector<Pending> pending; double prof[APSE_NCFG][3] = {{0}};
-    // the event pool has two halves: apse_read_results_begin hands the half (and the pending list) of the forward it reads to _end
-    // and switches recording to the other half, so a forward enqueued between the two halves of a read keeps its own events
-    int ev_base = 0, cal_read = -1; std::vector<Pending> pending_read;
-    // stateless-op scratch
-    uint64_t* op_bits = nullptr; unsigned long long* op_sums = nullptr; size_t op_bits_words = 0;
-    // C4 (cfg.arch 1, Res5ROIHeads): the RPN on res4, the res5 stage on the box ROIs (c4_res5box, then the 7x7 mean and the
-    // predictor in `boxhead`) and again on the detections (the front of `maskhead`)
-    bool c4 = false;
-    C4Rpn c4r; void* c4_nms = nullptr;
-    std::vector<Step> c4_res5box;
-};
-
-static int fail(apse_ctx* c, int code, const std::string& msg) {
+int fail(apse_ctx* c, int code, const std::string& msg) {
     if (c) c->err = msg; else g_create_error = msg;
     return code;
 }
 int apse_fail_global(int code, const char* msg) { return fail(nullptr, code, msg); }
-#define HIPCHK(c, call)                                                                        \
-    do {                                                                                       \
-        hipError_t e_ = (call);                                                                \
-        if (e_ != hipSuccess) return fail(c, APSE_E_HIP, std::string(#call) + ": " + hipGetErrorString(e_)); \
-    } while (0)
 
-template <typename T>
-static T* dalloc(apse_ctx* c, size_t n, bool zero = true) {
-    void* p = nullptr;
-    if (hipMalloc(&p, n * sizeof(T) > 0 ? n * sizeof(T) : 16) != hipSuccess) return nullptr;
-    if (zero) hipMemset(p, 0, n * sizeof(T));
-    c->allocs.push_back(p);
-    return reinterpret_cast<T*>(p);
-}
-template <typename T>
-static T* dupload(apse_ctx* c, const std::vector<T>& v) {
-    T* p = dalloc<T>(c, v.size(), false);
-    if (p && !v.empty()) hipMemcpy(p, v.data(), v.size() * sizeof(T), hipMemcpyHostToDevice);
-    return p;
-}
-
-// ------------------------------------------------------------------------------------------------
-// weight packing: OIHW (+ per-channel scale) -> [Cout_p][KH][KWCp], run = (kw, cin_p)
-static void pack_oihw(const float* w, int Cout, int Cin, int KH, int KW, int cin_p, const float* scale, float* out,
-                      int KWCp) {
-    for (int o = 0; o < Cout; ++o) {
-        const float sc = scale ? scale[o] : 1.0f;
-        for (int r = 0; r < KH; ++r)
-            for (int s = 0; s < KW; ++s)
-                for (int ci = 0; ci < Cin; ++ci)
-                    out[((size_t)o * KH + r) * KWCp + s * cin_p + ci] = w[(((size_t)o * Cin + ci) * KH + r) * KW + s] * sc;
+// Profiling: the index of a fresh event pair in this forward's half of the pool (the launch records ev_pool[e], ev_pool[e + 1]
+// around its kernel), or -1 when profiling is off or the half is used up.  The first pair a forward takes is preceded by the
+// calibration pair: two back-to-back records; their elapsed time (the marker overhead a timed kernel also pays) is subtracted
+// from every measurement of this forward.
+static int take_event_pair(apse_ctx* c, hipStream_t s) {
+    if (!c->prof_on) return -1;
+    if (c->ev_used == 0) {
+        hipEventRecord(c->ev_pool[c->ev_base], s);
+        hipEventRecord(c->ev_pool[c->ev_base + 1], s);
+        c->ev_used = 2;
     }
-}
-static int pow2_at_least(int v) { int p = 4; while (p < v) p <<= 1; return p; }
-
-static const HostW* getw(apse_ctx* c, const std::string& n) {
-    auto it = c->hw.find(n);
-    return it == c->hw.end() ? nullptr : &it->second;
-}
-
-static Tens make_t(apse_ctx* c, const std::string& name, int items, int H, int W, int C, int st = 0) {
-    Tens t;
-    t.H = H; t.W = W; t.C = C; t.st = st;
-    const size_t elems = (size_t)items * H * W * C;
-    t.p = dalloc<float>(c, st ? (elems + 1) / 2 : elems);          // 16-bit storage: half the bytes
-    c->t[name] = t;
-    return t;
-}
-
-// Build one convolution step from reference weights `wname` (OIHW) with optional FrozenBN `wname.norm.*`.
-// extra rows (fused heads) can be appended through `more`.
-struct ConvSpec {
-    std::string name; std::vector<std::string> wnames;   // one or more OIHW weights concatenated along Cout
-    int KH, KW, stride, pad, relu;
-    int fc_h = 0, fc_w = 0;   // >0: weight is [Cout][C*fc_h*fc_w] flattened (c,h,w): treat as fc_h x fc_w valid conv
-    int deconv = 0;
-    int s2d = 0;              // stem on the space-to-depth(2) input: the 7x7 / stride-2 filter is re-indexed as 4x4 / stride-1 over 12 channels
-};
-
-// 16-bit storage mode: every activation the bulk GEMMs produce lives in HBM in the operand type; the narrow
-// decision heads (Cout <= 32) and the association FC keep f32 outputs.
-// f32 -> bf16 (dtype 1) / f16 (dtype 2) bits, round-to-nearest-even like the in-kernel converts; a NaN stays a NaN
-static uint16_t round16(float v, int dtype) {
-    if (dtype == 2) {
-        const _Float16 hval = (_Float16)v;
-        uint16_t r;
-        memcpy(&r, &hval, 2);
-        return r;
-    }
-    uint32_t b;
-    memcpy(&b, &v, 4);
-    if ((b & 0x7fffffffu) > 0x7f800000u) return (uint16_t)((b >> 16) | 0x40);
-    return (uint16_t)((b + 0x7fffu + ((b >> 16) & 1u)) >> 16);
-}
-static int storage_type(const apse_ctx* c) { return (c->cfg.compute_dtype >= 1 && c->cfg.storage16) ? c->cfg.compute_dtype : 0; }
-
-// f32 layers that run as fused Winograd F(2x2,3x3) (conv_winograd.hip): the terminal 3x3 layers at p2 / p3 -- the FPN outputs and
-// the RPN conv, whose results feed no further 3x3 chain (conv_winograd_f32)
-static bool winograd_layer(const std::string& n) {
-    return n == "backbone.fpn_output2" || n == "backbone.fpn_output3" || n == "rpn_t2" || n == "rpn_t3";
-}
-// U = G g G^T per (cout, cin) in float64, rounded to f32 once, stored [cin_p / 8][16][Cout][8] (xi = 4 i + j): the B-operand
-// staging of conv_winograd_f32 reads one contiguous 2 KiB run per xi and k-slice.  Channels past Cin are zero.
-static std::vector<float> winograd_filters(const float* oihw, int Cout, int Cin, int cin_p) {
-    static const double G[4][3] = {{1, 0, 0}, {0.5, 0.5, 0.5}, {0.5, -0.5, 0.5}, {0, 0, 1}};
-    std::vector<float> u((size_t)16 * Cout * cin_p, 0.f);
-    for (int o = 0; o < Cout; ++o)
-        for (int ci = 0; ci < Cin; ++ci) {
-            const float* g = oihw + ((size_t)o * Cin + ci) * 9;
-            double t[4][3];                                  // G g
-            for (int i = 0; i < 4; ++i)
-                for (int s = 0; s < 3; ++s) t[i][s] = G[i][0] * g[s] + G[i][1] * g[3 + s] + G[i][2] * g[6 + s];
-            for (int i = 0; i < 4; ++i)
-                for (int j = 0; j < 4; ++j) {
-                    const double v = t[i][0] * G[j][0] + t[i][1] * G[j][1] + t[i][2] * G[j][2];      // (G g) G^T
-                    u[(((size_t)(ci / 8) * 16 + 4 * i + j) * Cout + o) * 8 + (ci & 7)] = (float)v;
-                }
-        }
-    return u;
-}
-
-static int add_conv(apse_ctx* c, std::vector<Step>& plan, const ConvSpec& sp, const Tens& in, int in_items_mult, Tens* out,
-                    const std::string& out_name, const Tens* res, int res_mode, int y_ld_override, int count_kind,
-                    float* out_ptr_override = nullptr, const Tens* out_view = nullptr) {
-    // gather rows
-    std::vector<float> rows;    // OIHW concatenated
-    std::vector<float> bias;
-    int Cout = 0, Cin = 0;
-    const int KH = sp.KH, KW = sp.KW;
-    for (const auto& wn : sp.wnames) {
-        const HostW* w = getw(c, wn + ".weight");
-        if (!w) return fail(c, APSE_E_MISSING, "missing weight " + wn + ".weight");
-        int co, ci;
-        std::vector<float> oihw;
-        if (sp.fc_h > 0) {
-            co = (int)w->shape[0];
-            const int flat = (int)w->shape[1];
-            ci = flat / (sp.fc_h * sp.fc_w);
-            oihw = w->v;                      // [co][c][h][w] already (c,h,w) flattened == OIHW
-        } else if (sp.deconv) {
-            // ConvTranspose2d weight [Cin][Cout][2][2] -> rows n = (dy*2+dx)*Cout + co, K = ci (1x1)
-            ci = (int)w->shape[0];
-            const int cc = (int)w->shape[1];
-            co = 4 * cc;
-            oihw.assign((size_t)co * ci, 0.f);
-            for (int i = 0; i < ci; ++i)
-                for (int o = 0; o < cc; ++o)
-                    for (int dy = 0; dy < 2; ++dy)
-                        for (int dx = 0; dx < 2; ++dx)
-                            oihw[((size_t)((dy * 2 + dx) * cc + o)) * ci + i] = w->v[(((size_t)i * cc + o) * 2 + dy) * 2 + dx];
-        } else if (w->shape.size() == 2) {
-            co = (int)w->shape[0]; ci = (int)w->shape[1]; oihw = w->v;
-        } else if (sp.s2d) {
-            // out(oy, ox) = sum w7[ky][kx][c] x[2 oy - 3 + ky][2 ox - 3 + kx][c]; with input row 2 Y + dy, Y = oy - 2 + r (r = 0..3):
-            // ky = 2 r + dy - 1, kx = 2 s + dx - 1 (taps outside 0..6 do not exist: zero), channel (2 dy + dx) 3 + c
-            if (w->shape.size() != 4 || w->shape[2] != 7 || w->shape[3] != 7 || w->shape[1] != 3 || KH != 4 || KW != 4)
-                return fail(c, APSE_E_INVALID, "space-to-depth stem needs a 7x7 filter over 3 channels: " + wn);
-            co = (int)w->shape[0]; ci = 12;
-            oihw.assign((size_t)co * 12 * 16, 0.f);
-            for (int o = 0; o < co; ++o)
-                for (int ch = 0; ch < 3; ++ch)
-                    for (int r = 0; r < 4; ++r)
-                        for (int sx = 0; sx < 4; ++sx)
-                            for (int dy = 0; dy < 2; ++dy)
-                                for (int dx = 0; dx < 2; ++dx) {
-                                    const int ky = 2 * r + dy - 1, kx = 2 * sx + dx - 1;
-                                    if (ky < 0 || ky > 6 || kx < 0 || kx > 6) continue;
-                                    oihw[(((size_t)o * 12 + (dy * 2 + dx) * 3 + ch) * 4 + r) * 4 + sx] = w->v[(((size_t)o * 3 + ch) * 7 + ky) * 7 + kx];
-                                }
-        } else {
-            co = (int)w->shape[0]; ci = (int)w->shape[1]; oihw = w->v;
-            if ((int)w->shape[2] != KH || (int)w->shape[3] != KW) return fail(c, APSE_E_INVALID, "kernel size mismatch " + wn);
-        }
-        if (Cin && ci != Cin) return fail(c, APSE_E_INVALID, "Cin mismatch in fused conv " + sp.name);
-        Cin = ci;
-        // FrozenBN fold (detectron2 FrozenBatchNorm2d, eps 1e-5): scale = g * rsqrt(var + eps), bias = b - mean*scale
-        const HostW* g = getw(c, wn + ".norm.weight");
-        std::vector<float> scale;
-        const int nb = sp.deconv ? co / 4 : co;
-        std::vector<float> b(nb, 0.f);
-        if (g) {
-            const HostW* be = getw(c, wn + ".norm.bias");
-            const HostW* mu = getw(c, wn + ".norm.running_mean");
-            const HostW* var = getw(c, wn + ".norm.running_var");
-            if (!be || !mu || !var) return fail(c, APSE_E_MISSING, "incomplete norm for " + wn);
-            scale.resize(co);
-            for (int o = 0; o < co; ++o) {
-                scale[o] = g->v[o] * (1.0f / sqrtf(var->v[o] + 1e-5f));
-                b[o] = be->v[o] - mu->v[o] * scale[o];
-            }
-            const size_t per = (size_t)ci * KH * KW;
-            for (int o = 0; o < co; ++o)
-                for (size_t k = 0; k < per; ++k) oihw[(size_t)o * per + k] *= scale[o];
-        } else {
-            const HostW* bw = getw(c, wn + ".bias");
-            if (bw) for (int o = 0; o < nb; ++o) b[o] = bw->v[o];
-        }
-        rows.insert(rows.end(), oihw.begin(), oihw.end());
-        bias.insert(bias.end(), b.begin(), b.end());
-        Cout += co;
-    }
-    const int cin_p = in.C;
-    if (pow2_at_least(Cin) != cin_p && Cin != cin_p) return fail(c, APSE_E_INVALID, "input channels mismatch at " + sp.name);
-    if (sp.s2d && (in.C != 16 || sp.stride != 1 || sp.pad != 2)) return fail(c, APSE_E_INVALID, "space-to-depth stem geometry");
-    const int KWC = KW * cin_p, KWCp = apse_roundup(KWC, 32);
-    const int Cout_p = apse_roundup(Cout, 128);
-    std::vector<float> packed((size_t)Cout_p * KH * KWCp, 0.f);
-    pack_oihw(rows.data(), Cout, Cin, KH, KW, cin_p, nullptr, packed.data(), KWCp);
-    std::vector<float> bias_p(Cout_p, 0.f);
-    for (size_t i = 0; i < bias.size(); ++i) bias_p[i] = bias[i];
-    // bf16 or f16 operands; the box and mask predictors are decision layers and stay f32 at any width (up to 6 classes they are
-    // narrow anyway: Cout <= 32)
-    const bool use_bf16 = (c->cfg.compute_dtype >= 1 && Cout > 32 && sp.name != "assoc_fc" && sp.name != "box_pred" &&
-                           sp.name != "mask_logits");
-    float* wd = nullptr;
-    uint16_t* wd16 = nullptr;
-    if (use_bf16) {
-        // filters pre-rounded to the 16-bit operand type (round-to-nearest-even, as the in-kernel converts do)
-        std::vector<uint16_t> p16(packed.size());
-        for (size_t i = 0; i < packed.size(); ++i) p16[i] = round16(packed[i], c->cfg.compute_dtype);
-        wd16 = dupload(c, p16);
-    } else {
-        wd = dupload(c, packed);
-    }
-    float* bd = dupload(c, bias_p);
-    if ((!wd && !wd16) || !bd) return fail(c, APSE_E_NOMEM, "weight upload failed at " + sp.name);
-
-    Step st;
-    st.kind = S_CONV;
-    ConvStep& cs = st.c;
-    memset(&cs.p, 0, sizeof(cs.p));
-    cs.name = sp.name;
-    cs.b_mult = in_items_mult;
-    cs.count_kind = count_kind;
-    ConvParams& p = cs.p;
-    p.x = in.p; p.w = wd; p.w16 = wd16; p.bias = bd; p.res = res ? res->p : nullptr; p.res_mode = res_mode;
-    p.x_st = in.st; p.res_st = res ? res->st : 0;
-    p.H = in.H; p.W = in.W; p.cin_log2 = apse_ilog2(cin_p);
-    p.KH = KH; p.KW = KW; p.stride = sp.stride; p.pad = sp.pad; p.KWCp = KWCp;
-    p.OH = (in.H + 2 * sp.pad - KH) / sp.stride + 1;
-    p.OW = (in.W + 2 * sp.pad - KW) / sp.stride + 1;
-    if (sp.s2d) { p.OH = in.H; p.OW = in.W; }       // pad 2 above / left, 1 below / right: taps past the map read zeros (range check)
-    p.Cout = Cout; p.relu = sp.relu;
-    p.steps_total = KH * (KWCp / 32);
-    p.splitk = 1;
-    p.out_mode = sp.deconv ? 1 : 0;
-    // bf16 matrix cores for the bulk GEMMs; decision layers (narrow heads) and the association FC stay exact f32
-    p.prec = use_bf16 ? c->cfg.compute_dtype : 0;
-    p.cdec = sp.deconv ? Cout / 4 : 0;
-    const int out_c = sp.deconv ? Cout / 4 : (y_ld_override > 0 ? y_ld_override : Cout);
-    const int oh = sp.deconv ? 2 * p.OH : p.OH, ow = sp.deconv ? 2 * p.OW : p.OW;
-    const int out_st = out_view ? out_view->st : ((use_bf16 && !out_ptr_override) ? storage_type(c) : 0);
-    if (out_st && (out_c & 7)) return fail(c, APSE_E_INVALID, "16-bit tensors need C % 8 == 0 at " + sp.name);
-    Tens o;
-    if (out_view) { o = *out_view; o.H = oh; o.W = ow; o.C = out_c; c->t[out_name] = o; }      // a slice of a larger allocation
-    else if (out_ptr_override) { o.p = out_ptr_override; o.H = oh; o.W = ow; o.C = out_c; }
-    else o = make_t(c, out_name, c->cfg.max_batch * in_items_mult, oh, ow, out_c, out_st);
-    p.y_st = o.st;
-    if (!o.p) return fail(c, APSE_E_NOMEM, "activation alloc failed at " + sp.name);
-    p.y = o.p; p.y_ld = out_c; p.y_coff = 0;
-    cs.flops_per_item = sp.s2d ? 2.0 * p.OH * p.OW * (double)Cout * 7 * 7 * 3        // algorithmic: the reference's 7x7x3 taps
-                               : 2.0 * p.OH * p.OW * (double)Cout * KH * KW * Cin;
-    // tile config / split-K chosen for the full batch; workspace sized for the worst case over 1..max_batch
-    const int Mfull = c->cfg.max_batch * in_items_mult * p.OH * p.OW;
-    int sk = 1;
-    cs.cfg = apse_conv_pick_cfg(Mfull, Cout, p.steps_total, &sk);
-    if (count_kind == 2) {
-        // GEMMs over the packed detection list: the tile shape and the K split fix the f32 summation order, so they are
-        // chosen HERE, once, from plan constants only (a typical list of APSE_EXPECTED_DETS detections per image of the
-        // context's max_batch -- like every other layer's shape; never from the batch of a forward or an earlier frame's
-        // count).  Within a context a frame's masks / embeddings are then the same bits whatever ran before it, in whatever
-        // batch; contexts with equal configuration (shards, pipeline slots) agree with each other.  The live count only
-        // sizes the grid (m_hint).
-        const int kd = c->cfg.dets_per_image < APSE_EXPECTED_DETS ? c->cfg.dets_per_image : APSE_EXPECTED_DETS;
-        const int rows = kd * c->cfg.max_batch * p.OH * p.OW;
-        sk = 1;
-        cs.cfg = apse_conv_pick_cfg(rows < Mfull ? rows : Mfull, Cout, p.steps_total, &sk);
-    }
-    p.splitk = sk;
-    if (sk > 1) {
-        const size_t need = (size_t)sk * Mfull * Cout;
-        if (need > c->ws_floats) c->ws_floats = need;
-    }
-    // fused Winograd for the named f32 3x3 layers: a plan constant (layer and shape, never the batch of a forward); cs.cfg stays
-    // the tiled config the layer would otherwise run and labels its profile slot.  Only maps of at least APSE_WINO_MIN_BLOCKS
-    // blocks per image (p3 of a 4K frame: 252): the small-frame configurations keep the direct kernel and its exact results
-    // (conv_winograd_f32)
-    if (c->f32_winograd && winograd_layer(sp.name) && count_kind == 0 && apse_conv_winograd_ok(p, c->cfg.max_batch * in_items_mult) &&
-        apse_conv_winograd_blocks(p) >= APSE_WINO_MIN_BLOCKS) {
-        p.wu = dupload(c, winograd_filters(rows.data(), Cout, Cin, cin_p));
-        if (!p.wu) return fail(c, APSE_E_NOMEM, "weight upload failed at " + sp.name);
-    }
-    if (out) *out = o;
-    plan.push_back(st);
-    return APSE_OK;
+    if (c->ev_used + 2 > APSE_EV_HALF) return -1;
+    const int e0 = c->ev_base + c->ev_used;
+    c->ev_used += 2;
+    return e0;
 }
 
 static int run_plan(apse_ctx* c, std::vector<Step>& plan, int batch, hipStream_t s) {
@@ -491,38 +78,25 @@ static int run_plan(apse_ctx* c, std::vector<Step>& plan, int batch, hipStream_t
                 }
             }
             else if (st.c.count_kind == 1 && batch == 1) p.m_count = propcnt_dev;
-            int e0 = -1;
-            if (c->prof_on && c->ev_used == 0) {
-                // calibration pair: two back-to-back records; their elapsed time (the marker overhead a timed
-                // kernel also pays) is subtracted from every measurement of this forward
-                hipEventRecord(c->ev_pool[c->ev_base], s);
-                hipEventRecord(c->ev_pool[c->ev_base + 1], s);
-                c->ev_used = 2;
-            }
-            if (c->prof_on && c->ev_used + 2 <= APSE_EV_HALF) { e0 = c->ev_base + c->ev_used; c->ev_used += 2; }
+            const int e0 = take_event_pair(c, s);
+            const hipEvent_t ev0 = e0 >= 0 ? c->ev_pool[e0] : nullptr, ev1 = e0 >= 0 ? c->ev_pool[e0 + 1] : nullptr;
             if (st.c.pool_y) {
-                rc = apse_k_stem_pool16(p.x, p.w16, p.bias, st.c.pool_y, batch, p.H, p.W, p.prec, s, e0 >= 0 ? c->ev_pool[e0] : nullptr,
-                                        e0 >= 0 ? c->ev_pool[e0 + 1] : nullptr);
+                rc = apse_k_stem_pool16(p.x, p.w16, p.bias, st.c.pool_y, batch, p.H, p.W, p.prec, s, ev0, ev1);
                 cfg = APSE_CFG_STEMPOOL;
             } else if (p.wu) {
                 // Winograd: profiled in the slot of the tiled config it replaces, with the layer's algorithmic FLOPs
-                rc = apse_launch_conv_winograd(p, s, e0 >= 0 ? c->ev_pool[e0] : nullptr, e0 >= 0 ? c->ev_pool[e0 + 1] : nullptr);
+                rc = apse_launch_conv_winograd(p, s, ev0, ev1);
             } else {
-                rc = apse_launch_conv(p, cfg, s, e0 >= 0 ? c->ev_pool[e0] : nullptr, e0 >= 0 ? c->ev_pool[e0 + 1] : nullptr);
+                rc = apse_launch_conv(p, cfg, s, ev0, ev1);
                 cfg = apse_conv_effective_cfg(p, cfg);                        // profile label of the kernel that actually ran
             }
             if (e0 >= 0) c->pending.push_back({cfg, st.c.flops_per_item, st.c.count_kind, st.c.b_mult, batch, e0, e0 + 1});
         } else if (st.kind == S_BNECK) {
-            int e0 = -1;
-            if (c->prof_on && c->ev_used == 0) {
-                hipEventRecord(c->ev_pool[c->ev_base], s);
-                hipEventRecord(c->ev_pool[c->ev_base + 1], s);
-                c->ev_used = 2;
-            }
-            if (c->prof_on && c->ev_used + 2 <= APSE_EV_HALF) { e0 = c->ev_base + c->ev_used; c->ev_used += 2; }
+            const int e0 = take_event_pair(c, s);
             const ConvParams& q1 = st.c.p;
             rc = apse_k_bottleneck64_fused16(st.x, st.p3.res, st.y, q1.w16, q1.bias, st.p2.w16, st.p2.bias, st.p3.w16, st.p3.bias, batch,
-                                             st.H, st.W, st.C, st.st, s, e0 >= 0 ? c->ev_pool[e0] : nullptr, e0 >= 0 ? c->ev_pool[e0 + 1] : nullptr);
+                                             st.H, st.W, st.C, st.st, s, e0 >= 0 ? c->ev_pool[e0] : nullptr,
+                                             e0 >= 0 ? c->ev_pool[e0 + 1] : nullptr);
             if (e0 >= 0) c->pending.push_back({APSE_CFG_BNECK, st.c.flops_per_item, 0, 1, batch, e0, e0 + 1});
         } else if (st.kind == S_MAXPOOL) {
             rc = apse_k_maxpool3x3s2(st.x, st.y, batch, st.H, st.W, st.C, st.st, s);
@@ -534,521 +108,22 @@ static int run_plan(apse_ctx* c, std::vector<Step>& plan, int batch, hipStream_t
     return APSE_OK;
 }
 
-// ------------------------------------------------------------------------------------------------
-static void layout_results(apse_ctx* c) {
-    apse_results_layout& L = c->lay;
-    memset(&L, 0, sizeof(L));
-    const int B = c->cfg.max_batch, kd = c->cfg.dets_per_image, n = B * kd, E = c->cfg.embed_dim;
-    L.n_max = n; L.dets_per_image = kd; L.embed_dim = E; L.max_batch = B;
-    size_t o = 0;
-    auto take = [&](size_t bytes) { size_t r = o; o += (bytes + 15) / 16 * 16; return r; };
-    L.total = take(4);
-    L.offset = take(4 * (B + 1));
-    L.prop_count = take(4 * B);
-    L.img = take(4 * n); L.cls = take(4 * n); L.roi = take(4 * n); L.score = take(4 * n);
-    L.box_resized = take(16 * n); L.box = take(16 * n); L.valid = take(4 * n); L.rect = take(16 * n);
-    L.mass = take(4 * n); L.centroid = take(8 * n);
-    L.closest = take((size_t)8 * n * kd);
-    L.embedding = take((size_t)4 * n * E);
-    L.bytes = o;
-}
-
-// Box-inference buffers of both plans: candidates, class lists (wide kernels), kept detections.
-static void alloc_box_inference(apse_ctx* c) {
-    const apse_config& g = c->cfg;
-    const int B = g.max_batch, POST = g.rpn_post_topk, K = g.num_classes, KD = g.dets_per_image;
-    c->wide = K > APSE_NARROW_CLASSES;
-    if (c->wide) {
-        c->cls_list = dalloc<int>(c, (size_t)B * K * POST, false);
-        c->cls_cnt = dalloc<int>(c, (size_t)B * K);                 // zero; nms_prepare_list leaves it zero after every forward
-    }
-    c->cand_boxes = dalloc<float>(c, (size_t)B * POST * K * 4);
-    c->cand_scores = dalloc<float>(c, (size_t)B * POST * K);
-    c->cand_valid = dalloc<int>(c, (size_t)B * POST * K);
-    c->probs = dalloc<float>(c, (size_t)B * POST * (K + 1));
-    c->det_boxes = dalloc<float>(c, (size_t)B * KD * 4);
-    c->det_scores = dalloc<float>(c, (size_t)B * KD);
-    c->det_entry = dalloc<int>(c, (size_t)B * KD);
-    c->det_cnt = dalloc<int>(c, (size_t)B);
-}
-
-// Tail of both plans: mask bit planes, the association head (roi_pool of a feat_C-channel map -> FC -> L2 normalise), the
-// split-K workspace and the resize staging.
-static int finish_plan(apse_ctx* c, int feat_C) {
-    const apse_config& g = c->cfg;
-    const int B = g.max_batch, KD = g.dets_per_image, NM = B * KD;
-    int rc;
-    c->wpr = (g.frame_w + 63) / 64;
-    for (int k = 0; k < 2; ++k) c->bits2[k] = dalloc<uint64_t>(c, (size_t)NM * g.frame_h * c->wpr, false);
-    c->sums = dalloc<unsigned long long>(c, (size_t)NM * 3);      // cleared by pack_detections in front of every mask tail
-    if (!c->bits2[0] || !c->bits2[1]) return fail(c, APSE_E_NOMEM, "mask bit planes alloc");
-    // ---- association head: roi_pool(p2) -> FC (RxR valid conv) -> L2 normalise
-    const int R = g.assoc_roi;
-    Tens ap = make_t(c, "assoc_pooled", NM, R, R, feat_C);
-    Tens er;
-    {
-        ConvSpec sp{"assoc_fc", {"association.fc"}, R, R, 1, 0, 0, R, R};
-        c->emb_raw = dalloc<float>(c, (size_t)NM * g.embed_dim);
-        rc = add_conv(c, c->embedfc, sp, ap, KD, &er, "assoc_fc", nullptr, 0, 0, 2, c->emb_raw);
-        if (rc) return rc;
-        const ConvParams& fp = c->embedfc[0].c.p;
-        // the same filters through the K-sliced form when the shape allows (K = 25600, N = 128 in the reference); APSE_NO_ASSOC_FC
-        // (read when the context is built) keeps the split-K convolution + normalise kernels
-        if (fp.w && fp.KWCp == R * feat_C && apse_assoc_fc_ok(fp.KH * fp.KWCp, g.embed_dim) && !getenv("APSE_NO_ASSOC_FC")) {
-            c->ws_assoc = dalloc<float>(c, (size_t)(fp.KH * fp.KWCp / 128) * NM * g.embed_dim, false);
-            if (!c->ws_assoc) return fail(c, APSE_E_NOMEM, "association FC workspace");
-        }
-    }
-    if (c->ws_floats) {
-        c->ws = dalloc<float>(c, c->ws_floats, false);
-        if (!c->ws) return fail(c, APSE_E_NOMEM, "split-K workspace alloc");
-    }
-    c->tile_cnt = dalloc<int>(c, 65536);        // zero-initialised; every launch leaves it zero
-    c->rs_pitch = (g.image_w * 3 + 15) & ~15;            // row pitch of the intermediate image: dword loads in the vertical pass
-    c->rs_tmp = dalloc<uint8_t>(c, (size_t)B * g.frame_h * c->rs_pitch, false);
-    hipError_t e = hipDeviceSynchronize();
-    if (e != hipSuccess) return fail(c, APSE_E_HIP, std::string("plan build: ") + hipGetErrorString(e));
+int fill_camera(UndistortParams& p, int H, int W, const double* m, const double* dist, int ndist, int do_undistort, int do_gamma) {
+    memset(&p, 0, sizeof p);
+    if (!m || ndist > 14 || ndist < 0 || (ndist > 0 && !dist)) return APSE_E_INVALID;
+    for (int i = 0; i < ndist && i < 12; ++i) p.k[i] = dist[i];
+    if (ndist > 12 && (dist[12] != 0.0 || (ndist > 13 && dist[13] != 0.0))) return APSE_E_INVALID;   // tilt model not built
+    // inverse of the 3x3 camera matrix (double, adjugate / determinant)
+    const double a = m[0], b = m[1], c = m[2], dd = m[3], e = m[4], f = m[5], g = m[6], h = m[7], k = m[8];
+    const double det = a * (e * k - f * h) - b * (dd * k - f * g) + c * (dd * h - e * g);
+    if (det == 0.0) return APSE_E_INVALID;
+    const double id = 1.0 / det;
+    p.ir[0] = (e * k - f * h) * id; p.ir[1] = (c * h - b * k) * id; p.ir[2] = (b * f - c * e) * id;
+    p.ir[3] = (f * g - dd * k) * id; p.ir[4] = (a * k - c * g) * id; p.ir[5] = (c * dd - a * f) * id;
+    p.ir[6] = (dd * h - e * g) * id; p.ir[7] = (b * g - a * h) * id; p.ir[8] = (a * e - b * dd) * id;
+    p.fx = m[0]; p.fy = m[4]; p.u0 = m[2]; p.v0 = m[5];
+    p.H = H; p.W = W; p.do_undistort = do_undistort; p.do_gamma = do_gamma;
     return APSE_OK;
-}
-
-static int build_plan(apse_ctx* c) {
-    const apse_config& g = c->cfg;
-    const int B = g.max_batch;
-    c->PH = apse_roundup(g.image_h, 32);
-    c->PW = apse_roundup(g.image_w, 32);
-    layout_results(c);
-    c->res = dalloc<uint8_t>(c, c->lay.bytes);
-    if (!c->res) return fail(c, APSE_E_NOMEM, "results alloc");
-    int rc;
-    // ---- backbone
-    Tens cur;
-    bool fused_stem = false;
-    if (storage_type(c)) {
-        // 16-bit storage modes: space-to-depth(2) input (elementwise.hip, input_store) and the stem as a 4x4 / stride-1 convolution
-        // over 16 channels: one 64-element k-step per filter row on the scheduled 16-bit kernel (K = 256 instead of the 448 a
-        // 7-pixel x 8-channel run would pad to; the f32-input stem ran on the legacy conditional-load kernel at 428 us per batch 8)
-        Tens x0 = make_t(c, "input", B, c->PH / 2, c->PW / 2, 16, storage_type(c));
-        ConvSpec sp{"stem.conv1", {"backbone.bottom_up.stem.conv1"}, 4, 4, 1, 2, 1};
-        sp.s2d = 1;
-        // ... and the max-pool behind it in the same kernel (stem_pool16.hip): the stem output never goes to HBM.
-        // APSE_NO_STEM_FUSE (read when the context is built): the two-kernel form, for the equality test and A/B runs.
-        if (!getenv("APSE_NO_STEM_FUSE")) {
-            Tens pooled = make_t(c, "stem", B, (x0.H + 2 - 3) / 2 + 1, (x0.W + 2 - 3) / 2 + 1, 64, storage_type(c));
-            if (!pooled.p) return fail(c, APSE_E_NOMEM, "stem alloc");
-            Tens unused;
-            rc = add_conv(c, c->backbone, sp, x0, 1, &unused, "stem.conv1", nullptr, 0, 0, 0, nullptr, &pooled);
-            if (rc) return rc;
-            c->t.erase("stem.conv1");                       // no such tensor in this form
-            c->backbone.back().c.pool_y = pooled.p;
-            cur = pooled;
-            fused_stem = true;
-        } else {
-            rc = add_conv(c, c->backbone, sp, x0, 1, &cur, "stem.conv1", nullptr, 0, 0, 0);
-        }
-    } else {
-        Tens x0 = make_t(c, "input", B, c->PH, c->PW, 4);
-        rc = add_conv(c, c->backbone, ConvSpec{"stem.conv1", {"backbone.bottom_up.stem.conv1"}, 7, 7, 2, 3, 1}, x0, 1, &cur,
-                      "stem.conv1", nullptr, 0, 0, 0);
-    }
-    if (rc) return rc;
-    if (!fused_stem) {
-        Step st; st.kind = S_MAXPOOL; st.x = cur.p; st.H = cur.H; st.W = cur.W; st.C = cur.C;
-        Tens o = make_t(c, "stem", B, (cur.H + 2 - 3) / 2 + 1, (cur.W + 2 - 3) / 2 + 1, cur.C, cur.st);
-        st.y = o.p; st.c.name = "stem.pool"; st.st = cur.st;
-        c->backbone.push_back(st);
-        cur = o;
-    }
-    for (int si = 0; si < 4; ++si) {
-        char stage[16];
-        snprintf(stage, sizeof stage, "res%d", si + 2);
-        for (int bi = 0; bi < g.blocks[si]; ++bi) {
-            char pre[96];
-            snprintf(pre, sizeof pre, "backbone.bottom_up.%s.%d", stage, bi);
-            const std::string P = pre;
-            const int stride = (bi == 0 && si > 0) ? 2 : 1;
-            Tens a, b2, sc, out;
-            const Tens* resp = &cur;
-            if (getw(c, P + ".shortcut.weight")) {
-                rc = add_conv(c, c->backbone, ConvSpec{P + ".shortcut", {P + ".shortcut"}, 1, 1, stride, 0, 0}, cur, 1, &sc,
-                              P + ".shortcut", nullptr, 0, 0, 0);
-                if (rc) return rc;
-                resp = &sc;
-            }
-            rc = add_conv(c, c->backbone, ConvSpec{P + ".conv1", {P + ".conv1"}, 1, 1, stride, 0, 1}, cur, 1, &a, P + ".conv1",
-                          nullptr, 0, 0, 0);
-            if (rc) return rc;
-            rc = add_conv(c, c->backbone, ConvSpec{P + ".conv2", {P + ".conv2"}, 3, 3, 1, 1, 1}, a, 1, &b2, P + ".conv2",
-                          nullptr, 0, 0, 0);
-            if (rc) return rc;
-            const bool last = (bi == g.blocks[si] - 1);
-            rc = add_conv(c, c->backbone, ConvSpec{P + ".conv3", {P + ".conv3"}, 1, 1, 1, 0, 1}, b2, 1, &out,
-                          last ? std::string(stage) : P + ".out", resp, 1, 0, 0);
-            if (rc) return rc;
-            // 16-bit storage modes, 64 mid channels (res2): conv1 -> conv2 -> conv3 + residual as ONE launch with the two
-            // 64-channel intermediates in LDS (bottleneck16.hip; same bits as the three launches).  APSE_NO_BNECK_FUSE (read when
-            // the context is built) keeps the three-kernel form, for the equality test and A/B runs.
-            {
-                const size_t n = c->backbone.size();
-                const ConvParams &q1 = c->backbone[n - 3].c.p, &q2 = c->backbone[n - 2].c.p, &q3 = c->backbone[n - 1].c.p;
-                const int st16 = storage_type(c);
-                if (st16 && stride == 1 && a.C == 64 && out.C == 256 && (cur.C == 64 || cur.C == 256) && q1.w16 && q2.w16 && q3.w16 &&
-                    q1.x_st == st16 && q1.y_st == st16 && q2.y_st == st16 && q3.y_st == st16 && q3.res_st == st16 && q2.KWCp == 192 &&
-                    q1.KWCp == cur.C && q3.KWCp == 64 && (size_t)B * cur.H * cur.W * cur.C * 2 < 0xfffffff0ull &&
-                    !getenv("APSE_NO_BNECK_FUSE")) {
-                    Step fs;
-                    fs.kind = S_BNECK;
-                    fs.c = c->backbone[n - 3].c;
-                    fs.c.name = P + ".fused";
-                    fs.c.flops_per_item = c->backbone[n - 3].c.flops_per_item + c->backbone[n - 2].c.flops_per_item + c->backbone[n - 1].c.flops_per_item;
-                    fs.p2 = q2; fs.p3 = q3;
-                    fs.x = cur.p; fs.y = out.p; fs.H = cur.H; fs.W = cur.W; fs.C = cur.C; fs.st = st16;
-                    c->backbone.resize(n - 3);
-                    c->backbone.push_back(fs);
-                }
-            }
-            cur = out;
-        }
-    }
-    // ---- FPN (top-down): inner5 = lateral5(res5); p5 = output5(inner5); inner_l = lateral_l(res_l) + up(inner_{l+1})
-    Tens inner, pl[5];
-    for (int lvl = 5; lvl >= 2; --lvl) {
-        char ln[64], on[64], rn[16], in_name[16], pn[8];
-        snprintf(ln, sizeof ln, "backbone.fpn_lateral%d", lvl);
-        snprintf(on, sizeof on, "backbone.fpn_output%d", lvl);
-        snprintf(rn, sizeof rn, "res%d", lvl);
-        snprintf(in_name, sizeof in_name, "inner%d", lvl);
-        snprintf(pn, sizeof pn, "p%d", lvl);
-        Tens ninner;
-        rc = add_conv(c, c->backbone, ConvSpec{ln, {ln}, 1, 1, 1, 0, 0}, c->t[rn], 1, &ninner, in_name,
-                      lvl == 5 ? nullptr : &inner, lvl == 5 ? 0 : 2, 0, 0);
-        if (rc) return rc;
-        inner = ninner;
-        rc = add_conv(c, c->backbone, ConvSpec{on, {on}, 3, 3, 1, 1, 0}, inner, 1, &pl[lvl - 2], pn, nullptr, 0, 0, 0);
-        if (rc) return rc;
-    }
-    {
-        Step st; st.kind = S_SUBSAMPLE; st.x = pl[3].p; st.H = pl[3].H; st.W = pl[3].W; st.C = 256;
-        pl[4] = make_t(c, "p6", B, (pl[3].H - 1) / 2 + 1, (pl[3].W - 1) / 2 + 1, 256, pl[3].st);
-        st.y = pl[4].p; st.c.name = "p6"; st.st = pl[3].st;
-        c->backbone.push_back(st);
-    }
-    // ---- RPN head per level: conv3x3+relu, fused 1x1 (3 objectness + 12 deltas) -> ld 16
-    static const int sizes[5] = {32, 64, 128, 256, 512};
-    static const int strides[5] = {4, 8, 16, 32, 64};
-    memset(&c->rl_host, 0, sizeof(c->rl_host));
-    c->rl_host.head_ld = 16;
-    c->rl_host.pre_topk = g.rpn_pre_topk;
-    // The 3x3 convolution runs per level; its outputs are slices of ONE buffer ([level][max_batch][H][W][256]) so that the
-    // fused 1x1 head (objectness + deltas, shared weights) is a single launch over all rows of all levels
-    // (five launches of 10-20 us, four of them with a handful of blocks, become one).
-    size_t rows_total = 0, row_off[6] = {0};
-    for (int l = 0; l < 5; ++l) { row_off[l] = rows_total; rows_total += (size_t)B * pl[l].H * pl[l].W; }
-    row_off[5] = rows_total;
-    const int rpn_st = storage_type(c);
-    Tens t_all = make_t(c, "rpn_t_all", 1, 1, (int)rows_total, 256, rpn_st);
-    if (!t_all.p) return fail(c, APSE_E_NOMEM, "rpn feature buffer");
-    for (int l = 0; l < 5; ++l) {
-        char tn[32];
-        snprintf(tn, sizeof tn, "rpn_t%d", l + 2);
-        Tens view = t_all;
-        view.p = reinterpret_cast<float*>(reinterpret_cast<char*>(t_all.p) + row_off[l] * 256 * (rpn_st ? 2 : 4));
-        Tens tt;
-        rc = add_conv(c, c->rpnhead, ConvSpec{tn, {"proposal_generator.rpn_head.conv"}, 3, 3, 1, 1, 1}, pl[l], 1, &tt, tn, nullptr,
-                      0, 0, 0, nullptr, &view);
-        if (rc) return rc;
-    }
-    Tens h_all;
-    {
-        Tens in_all = t_all;                       // [1][rows_total][256] as one 1 x rows image
-        float* hbuf = dalloc<float>(c, rows_total * 16);
-        if (!hbuf) return fail(c, APSE_E_NOMEM, "rpn head buffer");
-        rc = add_conv(c, c->rpnhead,
-                      ConvSpec{"rpn_head_all", {"proposal_generator.rpn_head.objectness_logits", "proposal_generator.rpn_head.anchor_deltas"},
-                               1, 1, 1, 0, 0},
-                      in_all, 1, &h_all, "rpn_head_all", nullptr, 0, 16, 0, hbuf);
-        if (rc) return rc;
-        ConvStep& hs = c->rpnhead.back().c;
-        hs.fixed_items = 1;                        // all rows of all levels, whatever the batch of this forward
-        hs.flops_per_item /= (double)B;            // profile accounting is per image
-    }
-    for (int l = 0; l < 5; ++l) {
-        char hn[32];
-        snprintf(hn, sizeof hn, "rpn_head%d", l + 2);
-        Tens hh = h_all;
-        hh.p = h_all.p + row_off[l] * 16;
-        hh.H = pl[l].H; hh.W = pl[l].W; hh.C = 16;
-        c->t[hn] = hh;
-        RpnLevel& L = c->rl_host.lv[l];
-        L.head = hh.p; L.H = hh.H; L.W = hh.W; L.stride = strides[l];
-        L.n = hh.H * hh.W * 3;
-        L.k = L.n < g.rpn_pre_topk ? L.n : g.rpn_pre_topk;
-        static const double ratios[3] = {0.5, 1.0, 2.0};
-        for (int a = 0; a < 3; ++a) {
-            const double area = (double)sizes[l] * sizes[l];
-            const double w = sqrt(area / ratios[a]), h = ratios[a] * w;
-            L.base[a][0] = (float)(-w / 2.0); L.base[a][1] = (float)(-h / 2.0);
-            L.base[a][2] = (float)(w / 2.0); L.base[a][3] = (float)(h / 2.0);
-        }
-    }
-    c->rl_dev = dalloc<RpnLevels>(c, 1);
-    hipMemcpy(c->rl_dev, &c->rl_host, sizeof(RpnLevels), hipMemcpyHostToDevice);
-    // top-k tournament plan
-    {
-        int slot = 0;
-        std::vector<std::vector<int>> cur_slots(5), cur_counts(5);
-        std::vector<TopkJob> st0;
-        for (int l = 0; l < 5; ++l) {
-            const int n = c->rl_host.lv[l].n;
-            for (int beg = 0; beg < n; beg += 4096) {
-                TopkJob j; memset(&j, 0, sizeof j);
-                j.kind = 0; j.level = l; j.begin = beg; j.count = (n - beg) < 4096 ? (n - beg) : 4096;
-                j.dst = slot++; j.dst_count = j.count < g.rpn_pre_topk ? j.count : g.rpn_pre_topk;
-                cur_slots[l].push_back(j.dst); cur_counts[l].push_back(j.dst_count);
-                st0.push_back(j);
-            }
-        }
-        c->stages.push_back(st0);
-        for (;;) {
-            std::vector<TopkJob> stn;
-            bool any = false;
-            for (int l = 0; l < 5; ++l) {
-                if (cur_slots[l].size() <= 1) continue;
-                any = true;
-                std::vector<int> ns, nc;
-                for (size_t i = 0; i < cur_slots[l].size(); i += 4) {
-                    TopkJob j; memset(&j, 0, sizeof j);
-                    j.kind = 1; j.level = l; int tot = 0;
-                    for (size_t k = i; k < i + 4 && k < cur_slots[l].size(); ++k) {
-                        j.src[j.nsrc] = cur_slots[l][k]; j.src_count[j.nsrc] = cur_counts[l][k]; tot += cur_counts[l][k]; ++j.nsrc;
-                    }
-                    j.dst = slot++; j.dst_count = tot < g.rpn_pre_topk ? tot : g.rpn_pre_topk;
-                    ns.push_back(j.dst); nc.push_back(j.dst_count);
-                    stn.push_back(j);
-                }
-                cur_slots[l] = ns; cur_counts[l] = nc;
-            }
-            if (!any) break;
-            c->stages.push_back(stn);
-        }
-        c->nslots = slot;
-        for (int l = 0; l < 5; ++l) c->final_slot_host[l] = cur_slots[l][0];
-        for (auto& sv : c->stages) c->stage_dev.push_back(dupload(c, sv));
-        std::vector<int> fs(c->final_slot_host, c->final_slot_host + 5);
-        c->final_slot_dev = dupload(c, fs);
-        c->lists = dalloc<uint64_t>(c, (size_t)B * slot * 1024);
-    }
-    const int PRE = g.rpn_pre_topk, POST = g.rpn_post_topk, K = g.num_classes, KD = g.dets_per_image;
-    c->dec_boxes = dalloc<float>(c, (size_t)B * 5 * PRE * 4);
-    c->dec_scores = dalloc<float>(c, (size_t)B * 5 * PRE);
-    c->dec_valid = dalloc<int>(c, (size_t)B * 5 * PRE);
-    c->maxc = dalloc<uint32_t>(c, (size_t)2 * B);
-    const int ncat = K > 8 ? K : 8;                                   // NMS categories per image: 5 RPN levels, K classes
-    c->keep_idx = dalloc<int>(c, (size_t)B * ncat * NMS_SLOT);
-    c->keep_cnt = dalloc<int>(c, (size_t)B * ncat);
-    c->nms_scratch = dalloc<uint8_t>(c, apse_nms_scratch_bytes(ncat * B));
-    c->props = dalloc<float>(c, (size_t)B * POST * 4);
-    c->prop_scores = dalloc<float>(c, (size_t)B * POST);
-    c->prop_entry = dalloc<int>(c, (size_t)B * POST);
-    // ---- box head: ROIAlign 7x7 -> fc1 (7x7 valid conv) -> fc2 -> fused predictor (K+1 logits, 4K deltas), ld round_up(5K+1, 32)
-    for (int l = 0; l < 4; ++l) { c->fm.p[l] = pl[l].p; c->fm.H[l] = pl[l].H; c->fm.W[l] = pl[l].W; c->fm.scale[l] = 1.0f / (float)strides[l]; }
-    c->fm.st = pl[0].st;
-    Tens pooled = make_t(c, "box_pooled", B * POST, 7, 7, 256, storage_type(c));
-    Tens f1, f2, pr;
-    rc = add_conv(c, c->boxhead, ConvSpec{"box_fc1", {"roi_heads.box_head.fc1"}, 7, 7, 1, 0, 1, 7, 7}, pooled, POST, &f1, "box_fc1",
-                  nullptr, 0, 0, 1);
-    if (rc) return rc;
-    rc = add_conv(c, c->boxhead, ConvSpec{"box_fc2", {"roi_heads.box_head.fc2"}, 1, 1, 1, 0, 1}, f1, POST, &f2, "box_fc2", nullptr, 0,
-                  0, 1);
-    if (rc) return rc;
-    rc = add_conv(c, c->boxhead,
-                  ConvSpec{"box_pred", {"roi_heads.box_predictor.cls_score", "roi_heads.box_predictor.bbox_pred"}, 1, 1, 1, 0, 0}, f2,
-                  POST, &pr, "box_pred", nullptr, 0, apse_roundup(5 * K + 1, 32), 1);
-    if (rc) return rc;
-    c->pred_ld = apse_roundup(5 * K + 1, 32);
-    if (pr.C != c->pred_ld || c->t["box_pred"].st != 0) return fail(c, APSE_E_INVALID, "fused box predictor layout");
-    alloc_box_inference(c);
-    // ---- mask head on the packed detection list
-    const int NM = B * KD;
-    Tens mp = make_t(c, "mask_pooled", NM, 14, 14, 256, storage_type(c));
-    Tens m = mp, md, ml;
-    for (int i = 1; i <= 4; ++i) {
-        char nm[48], wn[64];
-        snprintf(nm, sizeof nm, "mask_fcn%d", i);
-        snprintf(wn, sizeof wn, "roi_heads.mask_head.mask_fcn%d", i);
-        Tens o;
-        rc = add_conv(c, c->maskhead, ConvSpec{nm, {wn}, 3, 3, 1, 1, 1}, m, KD, &o, nm, nullptr, 0, 0, 2);
-        if (rc) return rc;
-        m = o;
-    }
-    {
-        ConvSpec sp{"mask_deconv", {"roi_heads.mask_head.deconv"}, 1, 1, 1, 0, 1};
-        sp.deconv = 1;
-        rc = add_conv(c, c->maskhead, sp, m, KD, &md, "mask_deconv", nullptr, 0, 0, 2);
-        if (rc) return rc;
-    }
-    rc = add_conv(c, c->maskhead, ConvSpec{"mask_logits", {"roi_heads.mask_head.predictor"}, 1, 1, 1, 0, 0}, md, KD, &ml,
-                  "mask_logits", nullptr, 0, 0, 2);
-    if (rc) return rc;
-    return finish_plan(c, 256);
-}
-
-// ------------------------------------------------------------------------------------------------ C4 plan (arch 1)
-// detectron2 Base-RCNN-C4: ResNet stem + res2..res4 on the UNPADDED image (size_divisibility 0), StandardRPNHead on res4 (15
-// anchors per cell), Res5ROIHeads: ROIAlignV2 14x14 on res4 -> res5 (first block stride 2 in its 1x1) -> 7x7 mean -> predictor;
-// mask branch: ROIAlignV2 14x14 of the detections -> res5 -> deconv 2x2 + ReLU -> 1x1 predictor (14x14 logits).  f32 only.
-static int add_res5(apse_ctx* c, std::vector<Step>& plan, const Tens& in, int items, int count_kind, const std::string& tag, Tens* out) {
-    Tens cur = in;
-    for (int bi = 0; bi < c->cfg.blocks[3]; ++bi) {
-        const std::string P = "roi_heads.res5." + std::to_string(bi);
-        const std::string T = tag + "." + std::to_string(bi);
-        const int stride = bi == 0 ? 2 : 1;
-        Tens a, b2, sc, o;
-        const Tens* resp = &cur;
-        int rc;
-        if (getw(c, P + ".shortcut.weight")) {
-            rc = add_conv(c, plan, ConvSpec{T + ".shortcut", {P + ".shortcut"}, 1, 1, stride, 0, 0}, cur, items, &sc, T + ".shortcut",
-                          nullptr, 0, 0, count_kind);
-            if (rc) return rc;
-            resp = &sc;
-        }
-        rc = add_conv(c, plan, ConvSpec{T + ".conv1", {P + ".conv1"}, 1, 1, stride, 0, 1}, cur, items, &a, T + ".conv1", nullptr, 0, 0,
-                      count_kind);
-        if (rc) return rc;
-        rc = add_conv(c, plan, ConvSpec{T + ".conv2", {P + ".conv2"}, 3, 3, 1, 1, 1}, a, items, &b2, T + ".conv2", nullptr, 0, 0,
-                      count_kind);
-        if (rc) return rc;
-        rc = add_conv(c, plan, ConvSpec{T + ".conv3", {P + ".conv3"}, 1, 1, 1, 0, 1}, b2, items, &o, T + ".out" + std::to_string(bi), resp,
-                      1, 0, count_kind);
-        if (rc) return rc;
-        cur = o;
-    }
-    *out = cur;
-    return APSE_OK;
-}
-
-static int build_plan_c4(apse_ctx* c) {
-    const apse_config& g = c->cfg;
-    const int B = g.max_batch;
-    c->PH = g.image_h;                    // size_divisibility 0: no padding
-    c->PW = g.image_w;
-    layout_results(c);
-    c->res = dalloc<uint8_t>(c, c->lay.bytes);
-    if (!c->res) return fail(c, APSE_E_NOMEM, "results alloc");
-    int rc;
-    // ---- backbone: stem + max-pool + res2..res4 (keys backbone.stem.*, backbone.res{2,3,4}.N.*)
-    Tens cur;
-    Tens x0 = make_t(c, "input", B, c->PH, c->PW, 4);
-    rc = add_conv(c, c->backbone, ConvSpec{"stem.conv1", {"backbone.stem.conv1"}, 7, 7, 2, 3, 1}, x0, 1, &cur, "stem.conv1", nullptr, 0,
-                  0, 0);
-    if (rc) return rc;
-    {
-        Step st; st.kind = S_MAXPOOL; st.x = cur.p; st.H = cur.H; st.W = cur.W; st.C = cur.C;
-        Tens o = make_t(c, "stem", B, (cur.H + 2 - 3) / 2 + 1, (cur.W + 2 - 3) / 2 + 1, cur.C);
-        st.y = o.p; st.c.name = "stem.pool"; st.st = 0;
-        c->backbone.push_back(st);
-        cur = o;
-    }
-    for (int si = 0; si < 3; ++si) {
-        const std::string stage = "res" + std::to_string(si + 2);
-        for (int bi = 0; bi < g.blocks[si]; ++bi) {
-            const std::string P = "backbone." + stage + "." + std::to_string(bi);
-            const int stride = (bi == 0 && si > 0) ? 2 : 1;
-            Tens a, b2, sc, out;
-            const Tens* resp = &cur;
-            if (getw(c, P + ".shortcut.weight")) {
-                rc = add_conv(c, c->backbone, ConvSpec{P + ".shortcut", {P + ".shortcut"}, 1, 1, stride, 0, 0}, cur, 1, &sc, P + ".shortcut",
-                              nullptr, 0, 0, 0);
-                if (rc) return rc;
-                resp = &sc;
-            }
-            rc = add_conv(c, c->backbone, ConvSpec{P + ".conv1", {P + ".conv1"}, 1, 1, stride, 0, 1}, cur, 1, &a, P + ".conv1", nullptr, 0,
-                          0, 0);
-            if (rc) return rc;
-            rc = add_conv(c, c->backbone, ConvSpec{P + ".conv2", {P + ".conv2"}, 3, 3, 1, 1, 1}, a, 1, &b2, P + ".conv2", nullptr, 0, 0, 0);
-            if (rc) return rc;
-            const bool last = bi == g.blocks[si] - 1;
-            rc = add_conv(c, c->backbone, ConvSpec{P + ".conv3", {P + ".conv3"}, 1, 1, 1, 0, 1}, b2, 1, &out, last ? stage : P + ".out",
-                          resp, 1, 0, 0);
-            if (rc) return rc;
-            cur = out;
-        }
-    }
-    const Tens res4 = c->t["res4"];
-    if (res4.C < 256 || (res4.C & 255)) return fail(c, APSE_E_INVALID, "C4: res4 needs a multiple of 256 channels");
-    // ---- RPN head on res4: conv 3x3 + ReLU, then objectness (15) and deltas (60) fused into one 1x1 with an 80-wide row
-    {
-        Tens t, h;
-        rc = add_conv(c, c->rpnhead, ConvSpec{"rpn_conv", {"proposal_generator.rpn_head.conv"}, 3, 3, 1, 1, 1}, res4, 1, &t, "rpn_conv",
-                      nullptr, 0, 0, 0);
-        if (rc) return rc;
-        rc = add_conv(c, c->rpnhead,
-                      ConvSpec{"rpn_head", {"proposal_generator.rpn_head.objectness_logits", "proposal_generator.rpn_head.anchor_deltas"},
-                               1, 1, 1, 0, 0},
-                      t, 1, &h, "rpn_head", nullptr, 0, 80, 0);
-        if (rc) return rc;
-        if (c->rpnhead.back().c.p.Cout != 75) return fail(c, APSE_E_INVALID, "C4 RPN head: expected 15 objectness + 60 delta channels");
-        C4Rpn& R = c->c4r;
-        memset(&R, 0, sizeof R);
-        R.head = h.p; R.H = h.H; R.W = h.W; R.ld = 80; R.stride = 16;
-        R.n = h.H * h.W * 15;
-        R.k = R.n < g.rpn_pre_topk ? R.n : g.rpn_pre_topk;
-        static const int sizes[5] = {32, 64, 128, 256, 512};
-        static const double ratios[3] = {0.5, 1.0, 2.0};
-        for (int si = 0; si < 5; ++si)
-            for (int a = 0; a < 3; ++a) {          // DefaultAnchorGenerator: sizes outer, ratios inner
-                const double area = (double)sizes[si] * sizes[si];
-                const double w = sqrt(area / ratios[a]), hh = ratios[a] * w;
-                float* bb = R.base[3 * si + a];
-                bb[0] = (float)(-w / 2.0); bb[1] = (float)(-hh / 2.0); bb[2] = (float)(w / 2.0); bb[3] = (float)(hh / 2.0);
-            }
-    }
-    const int PRE = g.rpn_pre_topk, POST = g.rpn_post_topk, K = g.num_classes, KD = g.dets_per_image;
-    c->dec_boxes = dalloc<float>(c, (size_t)B * PRE * 4);
-    c->dec_scores = dalloc<float>(c, (size_t)B * PRE);
-    c->dec_valid = dalloc<int>(c, (size_t)B * PRE);
-    c->maxc = dalloc<uint32_t>(c, (size_t)2 * B);
-    c->c4_nms = dalloc<uint8_t>(c, apse_c4_nms_scratch_bytes(B), false);
-    const int ncat = K > 8 ? K : 8;
-    c->keep_idx = dalloc<int>(c, (size_t)B * ncat * NMS_SLOT);
-    c->keep_cnt = dalloc<int>(c, (size_t)B * ncat);
-    c->nms_scratch = dalloc<uint8_t>(c, apse_nms_scratch_bytes(ncat * B));
-    c->props = dalloc<float>(c, (size_t)B * POST * 4);
-    c->prop_scores = dalloc<float>(c, (size_t)B * POST);
-    c->prop_entry = dalloc<int>(c, (size_t)B * POST);
-    if (!c->dec_boxes || !c->c4_nms || !c->props) return fail(c, APSE_E_NOMEM, "C4 proposal buffers");
-    // ---- box branch: ROIAlign 14x14 of res4 -> res5 -> mean over 7x7 (box_mean) -> fused predictor
-    Tens pooled = make_t(c, "box_pooled", B * POST, 14, 14, res4.C);
-    if (!pooled.p) return fail(c, APSE_E_NOMEM, "C4 box features");
-    Tens r5;
-    rc = add_res5(c, c->c4_res5box, pooled, POST, 1, "box_res5", &r5);
-    if (rc) return rc;
-    c->t["box_res5"] = r5;
-    Tens mean = make_t(c, "box_mean", B * POST, 1, 1, r5.C);
-    Tens pr;
-    rc = add_conv(c, c->boxhead,
-                  ConvSpec{"box_pred", {"roi_heads.box_predictor.cls_score", "roi_heads.box_predictor.bbox_pred"}, 1, 1, 1, 0, 0}, mean,
-                  POST, &pr, "box_pred", nullptr, 0, apse_roundup(5 * K + 1, 32), 1);
-    if (rc) return rc;
-    c->pred_ld = apse_roundup(5 * K + 1, 32);
-    if (pr.C != c->pred_ld) return fail(c, APSE_E_INVALID, "fused box predictor layout");
-    alloc_box_inference(c);
-    // ---- mask branch on the packed detection list: ROIAlign 14x14 -> res5 -> deconv + ReLU -> predictor (14 x 14 logits)
-    const int NM = B * KD;
-    Tens mp = make_t(c, "mask_pooled", NM, 14, 14, res4.C);
-    Tens m5, md, ml;
-    rc = add_res5(c, c->maskhead, mp, KD, 2, "mask_res5", &m5);
-    if (rc) return rc;
-    {
-        ConvSpec sp{"mask_deconv", {"roi_heads.mask_head.deconv"}, 1, 1, 1, 0, 1};
-        sp.deconv = 1;
-        rc = add_conv(c, c->maskhead, sp, m5, KD, &md, "mask_deconv", nullptr, 0, 0, 2);
-        if (rc) return rc;
-    }
-    rc = add_conv(c, c->maskhead, ConvSpec{"mask_logits", {"roi_heads.mask_head.predictor"}, 1, 1, 1, 0, 0}, md, KD, &ml, "mask_logits",
-                  nullptr, 0, 0, 2);
-    if (rc) return rc;
-    if (ml.H != 14 || ml.W != 14) return fail(c, APSE_E_INVALID, "C4 mask logits must be 14 x 14");
-    return finish_plan(c, res4.C);
 }
 
 // ================================================================================================ C ABI
@@ -1300,7 +375,7 @@ int apse_box_head(apse_ctx* c, int batch, void* stream) {
         rc = pack_from_dets(c, batch, s);
         return rc ? fail(c, rc, "pack launch failed") : APSE_OK;
     }
-    rc = apse_k_box_candidates(c->t["box_pred"].p, 32, K, c->props, propcnt, P, (float)g.image_h, (float)g.image_w, g.score_thresh,
+    rc = apse_k_box_candidates(c->t["box_pred"].p, c->pred_ld, K, c->props, propcnt, P, (float)g.image_h, (float)g.image_w, g.score_thresh,
                                wts, (float)log(1000.0 / 16.0), c->cand_boxes, c->cand_scores, c->cand_valid,
                                c->maxc + g.max_batch, c->probs, batch, s);
     if (rc) return fail(c, rc, "box candidates launch failed");
@@ -1692,290 +767,6 @@ double apse_flops(apse_ctx* c, int batch, double proposals, double detections) {
     return f;
 }
 
-// ------------------------------------------------------------------------------------------------ stateless ops
-size_t apse_conv_packed_elems(const apse_conv_desc* d) {
-    const int cin_p = pow2_at_least(d->Cin);
-    return (size_t)apse_roundup(d->Cout, 128) * d->KH * apse_roundup(d->KW * cin_p, 32);
-}
-
-int apse_conv_pack_weight(const apse_conv_desc* d, const float* w, int cin_real, const float* scale, float* packed) {
-    if (!d || !w || !packed) return APSE_E_INVALID;
-    const int cin_p = pow2_at_least(d->Cin);
-    const int KWCp = apse_roundup(d->KW * cin_p, 32);
-    memset(packed, 0, apse_conv_packed_elems(d) * sizeof(float));
-    pack_oihw(w, d->Cout, cin_real, d->KH, d->KW, cin_p, scale, packed, KWCp);
-    return APSE_OK;
-}
-
-int apse_conv2d(const apse_conv_desc* d, const float* x, const float* w, const float* bias, const float* res, float* y, float* ws,
-                size_t ws_bytes, void* stream) {
-    if (!d || !x || !w || !y) return APSE_E_INVALID;
-    const int cin_p = pow2_at_least(d->Cin);
-    if (cin_p != d->Cin) return APSE_E_INVALID;
-    ConvParams p;
-    memset(&p, 0, sizeof p);
-    p.x = x; p.w = w; p.bias = bias; p.res = res; p.y = y; p.ws = ws;
-    p.B = d->B; p.H = d->H; p.W = d->W; p.cin_log2 = apse_ilog2(cin_p);
-    p.KH = d->KH; p.KW = d->KW; p.stride = d->stride; p.pad = d->pad;
-    p.KWCp = apse_roundup(d->KW * cin_p, 32);
-    p.OH = (d->H + 2 * d->pad - d->KH) / d->stride + 1;
-    p.OW = (d->W + 2 * d->pad - d->KW) / d->stride + 1;
-    p.Cout = d->Cout; p.relu = d->relu; p.res_mode = d->res_mode;
-    p.M = p.B * p.OH * p.OW; p.m_per_item = p.OH * p.OW;
-    p.y_ld = d->Cout; p.steps_total = p.KH * (p.KWCp / 32);
-    p.prec = (d->prec == 1 || d->prec == 2) ? d->prec : 0;
-    p.x_st = d->x_st; p.res_st = d->res_st; p.y_st = d->y_st;
-    if (p.x_st < 0 || p.x_st > 2 || p.res_st < 0 || p.res_st > 2 || p.y_st < 0 || p.y_st > 2) return APSE_E_INVALID;
-    if (p.prec && p.x_st && p.x_st != p.prec) return APSE_E_INVALID;       // 16-bit x must already be the operand type
-    if (p.x_st && cin_p < 8) return APSE_E_INVALID;
-    int sk = 1;
-    int cfg = apse_conv_pick_cfg(p.M, p.Cout, p.steps_total, &sk);
-    if (d->cfg >= 0) { cfg = d->cfg; sk = 1; p.no_stream = (d->cfg != APSE_CFG_STREAM && d->cfg != APSE_CFG_GLDS && d->cfg != APSE_CFG_SKINNY); }
-    if (d->splitk > 0) sk = d->splitk;
-    if (sk > p.steps_total) sk = p.steps_total;
-    p.splitk = sk;
-    if (sk > 1 && (size_t)sk * p.M * p.Cout * sizeof(float) > ws_bytes) return APSE_E_INVALID;
-    if (sk > 1 && d->fuse_reduce) {
-        static int* cnt = nullptr;
-        if (!cnt) { if (hipMalloc(reinterpret_cast<void**>(&cnt), 65536 * sizeof(int)) != hipSuccess) return APSE_E_NOMEM; hipMemset(cnt, 0, 65536 * sizeof(int)); }
-        p.tile_cnt = cnt;
-    }
-    if (!p.prec) return apse_launch_conv(p, cfg, (hipStream_t)stream);
-    // 16-bit operands: round the filters like a context does at load (this stateless entry is a test / tool helper: the
-    // rounded copy is rebuilt by a small kernel on the caller's stream in front of every call, in a buffer that only grows)
-    const size_t ne = (size_t)apse_roundup(p.Cout, 128) * p.KH * p.KWCp;
-    static uint16_t* d16 = nullptr;
-    static size_t d16_cap = 0;
-    if (ne > d16_cap) {
-        hipDeviceSynchronize();
-        if (d16) hipFree(d16);
-        d16 = nullptr; d16_cap = 0;
-        if (hipMalloc(reinterpret_cast<void**>(&d16), ne * 2) != hipSuccess) return APSE_E_NOMEM;
-        d16_cap = ne;
-    }
-    int rc = apse_k_round16(w, d16, ne, p.prec, (hipStream_t)stream);
-    if (rc) return rc;
-    p.w16 = d16;
-    return apse_launch_conv(p, cfg, (hipStream_t)stream);
-}
-
-int apse_winograd_pack_filter(const float* w, int Cout, int Cin, float* packed) {
-    if (!w || !packed || Cout < 1 || Cin < 8 || pow2_at_least(Cin) != Cin) return APSE_E_INVALID;
-    const std::vector<float> u = winograd_filters(w, Cout, Cin, Cin);
-    memcpy(packed, u.data(), u.size() * sizeof(float));
-    return APSE_OK;
-}
-
-int apse_winograd_conv2d(const apse_conv_desc* d, const float* x, const float* wu, const float* bias, float* y, void* stream) {
-    if (!d || !x || !wu || !y || d->B < 1 || d->H < 1 || d->W < 1 || d->Cin < 8 || pow2_at_least(d->Cin) != d->Cin) return APSE_E_INVALID;
-    ConvParams p;
-    memset(&p, 0, sizeof p);
-    p.x = x; p.wu = wu; p.bias = bias; p.y = y;
-    p.B = d->B; p.H = d->H; p.W = d->W; p.cin_log2 = apse_ilog2(d->Cin);
-    p.KH = d->KH; p.KW = d->KW; p.stride = d->stride; p.pad = d->pad;
-    p.OH = d->H; p.OW = d->W; p.Cout = d->Cout; p.relu = d->relu;
-    p.M = p.B * p.OH * p.OW; p.m_per_item = p.OH * p.OW;
-    p.y_ld = d->Cout; p.splitk = 1;
-    p.res_mode = d->res_mode; p.prec = d->prec; p.x_st = d->x_st; p.y_st = d->y_st;      // anything but 0 is refused by the launcher
-    return apse_launch_conv_winograd(p, (hipStream_t)stream);
-}
-
-int apse_maxpool3x3s2(const float* x, float* y, int B, int H, int W, int C, void* stream) {
-    return apse_k_maxpool3x3s2(x, y, B, H, W, C, 0, (hipStream_t)stream);
-}
-
-int apse_maxpool3x3s2_typed(const void* x, void* y, int B, int H, int W, int C, int storage, void* stream) {
-    if (!x || !y || B < 1 || H < 1 || W < 1 || C < 4 || (C & 3) || storage < 0 || storage > 2) return APSE_E_INVALID;
-    return apse_k_maxpool3x3s2(x, y, B, H, W, C, storage, (hipStream_t)stream);
-}
-
-static int roi_align_stateless(const void* const* feats, const int* hs, const int* ws, const float* rois, int n, int per_img,
-                               int out_size, int st, void* out, void* stream) {
-    if (!feats || !hs || !ws || !rois || !out || n < 0 || out_size < 1 || st < 0 || st > 2) return APSE_E_INVALID;
-    FpnMaps F;
-    static const float sc[4] = {0.25f, 0.125f, 0.0625f, 0.03125f};
-    for (int l = 0; l < 4; ++l) { F.p[l] = feats[l]; F.H[l] = hs[l]; F.W[l] = ws[l]; F.scale[l] = sc[l]; }
-    F.st = st;
-    // all rois live: a one-element count array is not available here, so use a device int holding n via total
-    static int* total_dev = nullptr;
-    if (!total_dev) hipMalloc(reinterpret_cast<void**>(&total_dev), sizeof(int));
-    hipMemcpyAsync(total_dev, &n, sizeof(int), hipMemcpyHostToDevice, (hipStream_t)stream);
-    hipStreamSynchronize((hipStream_t)stream);
-    // roi_img derived from per_img: build on device via a tiny host vector
-    std::vector<int> img(n);
-    for (int i = 0; i < n; ++i) img[i] = per_img > 0 ? i / per_img : 0;
-    int* img_dev = nullptr;
-    if (hipMalloc(reinterpret_cast<void**>(&img_dev), sizeof(int) * (n > 0 ? n : 1)) != hipSuccess) return APSE_E_NOMEM;
-    hipMemcpy(img_dev, img.data(), sizeof(int) * n, hipMemcpyHostToDevice);
-    int rc = apse_k_roi_align(&F, rois, img_dev, nullptr, total_dev, 0, n, out_size, out, st, (hipStream_t)stream);
-    hipStreamSynchronize((hipStream_t)stream);
-    hipFree(img_dev);
-    return rc;
-}
-
-int apse_roi_align(const float* const* feats, const int* hs, const int* ws, const float* rois, int n, int per_img, int out_size,
-                   float* out, void* stream) {
-    return roi_align_stateless(reinterpret_cast<const void* const*>(feats), hs, ws, rois, n, per_img, out_size, 0, out, stream);
-}
-
-int apse_roi_align_typed(const void* const* feats, const int* hs, const int* ws, const float* rois, int n, int per_img,
-                         int out_size, int storage, void* out, void* stream) {
-    return roi_align_stateless(feats, hs, ws, rois, n, per_img, out_size, storage, out, stream);
-}
-
-int apse_roi_pool(const float* feat, int H, int W, const float* rois, const int* roi_img, int n, int out_size, float scale,
-                  float* out, void* stream) {
-    static int* total_dev = nullptr;
-    if (!total_dev) hipMalloc(reinterpret_cast<void**>(&total_dev), sizeof(int));
-    hipMemcpyAsync(total_dev, &n, sizeof(int), hipMemcpyHostToDevice, (hipStream_t)stream);
-    hipStreamSynchronize((hipStream_t)stream);
-    return apse_k_roi_pool(feat, 0, H, W, rois, roi_img, total_dev, n, out_size, scale, out, 0, 0, (hipStream_t)stream);
-}
-
-int apse_nms_rank(const float* boxes, const float* scores, const int* valid, int n, int cat_div, int cat_mod, int ncat, float thr,
-                  int topk, float* out_boxes, float* out_scores, int* out_index, int* out_count, void* stream) {
-    if (ncat < 1 || ncat > 8 || n > 8192) return APSE_E_INVALID;
-    hipStream_t s = (hipStream_t)stream;
-    int *keep_idx = nullptr, *keep_cnt = nullptr;
-    uint32_t* maxc = nullptr;
-    if (hipMalloc(reinterpret_cast<void**>(&keep_idx), sizeof(int) * 8 * NMS_SLOT) != hipSuccess) return APSE_E_NOMEM;
-    hipMalloc(reinterpret_cast<void**>(&keep_cnt), sizeof(int) * 8);
-    hipMalloc(reinterpret_cast<void**>(&maxc), sizeof(uint32_t));
-    // max coordinate over the valid boxes (torchvision batched_nms): computed on the host for this stateless op
-    std::vector<float> hb((size_t)n * 4);
-    std::vector<int> hv(n);
-    hipMemcpy(hb.data(), boxes, hb.size() * 4, hipMemcpyDeviceToHost);
-    hipMemcpy(hv.data(), valid, hv.size() * 4, hipMemcpyDeviceToHost);
-    float m = 0.f;
-    bool any = false;
-    for (int i = 0; i < n; ++i)
-        if (hv[i]) for (int k = 0; k < 4; ++k) { m = (!any || hb[i * 4 + k] > m) ? hb[i * 4 + k] : m; any = true; }
-    uint32_t mb;
-    memcpy(&mb, &m, 4);
-    hipMemcpy(maxc, &mb, 4, hipMemcpyHostToDevice);
-    void* scratch = nullptr;
-    if (hipMalloc(&scratch, apse_nms_scratch_bytes(8)) != hipSuccess) return APSE_E_NOMEM;
-    int rc = apse_k_nms_percat(boxes, scores, valid, n, cat_div, cat_mod, maxc, thr, keep_idx, keep_cnt, ncat, scratch, 0, 1, 0, s);
-    if (!rc) rc = apse_k_rank_final(boxes, scores, n, keep_idx, keep_cnt, ncat, topk, out_boxes, out_scores, out_index, out_count, nullptr, 1, s);
-    hipStreamSynchronize(s);
-    hipFree(keep_idx); hipFree(keep_cnt); hipFree(maxc); hipFree(scratch);
-    return rc;
-}
-
-static int dense_scratch(int H, int W, uint64_t** bits, unsigned long long** sums) {
-    static uint64_t* b = nullptr;
-    static unsigned long long* sm = nullptr;
-    static size_t words = 0;
-    const size_t need = (size_t)H * ((W + 63) / 64);
-    if (need > words) {
-        if (b) hipFree(b);
-        if (hipMalloc(reinterpret_cast<void**>(&b), need * 8) != hipSuccess) return APSE_E_NOMEM;
-        words = need;
-    }
-    if (!sm && hipMalloc(reinterpret_cast<void**>(&sm), 4 * sizeof(unsigned long long)) != hipSuccess) return APSE_E_NOMEM;
-    *bits = b; *sums = sm;
-    return APSE_OK;
-}
-
-int apse_mask_centroid_dense(const uint8_t* mask, int H, int W, int* out3, void* stream) {
-    uint64_t* bits; unsigned long long* sums;
-    int rc = dense_scratch(H, W, &bits, &sums);
-    if (rc) return rc;
-    hipStream_t s = (hipStream_t)stream;
-    rc = apse_k_dense_to_bits(mask, H, W, (W + 63) / 64, bits, sums, s);
-    if (rc) return rc;
-    unsigned long long h[3];
-    if (hipMemcpyAsync(h, sums, sizeof h, hipMemcpyDeviceToHost, s) != hipSuccess) return APSE_E_HIP;
-    hipStreamSynchronize(s);
-    out3[2] = (int)h[0];
-    out3[0] = h[0] ? (int)(h[1] / h[0]) : -1;
-    out3[1] = h[0] ? (int)(h[2] / h[0]) : -1;
-    return APSE_OK;
-}
-
-int apse_mask_closest_dense(const uint8_t* mask, int H, int W, float px, float py, int* out2, void* stream) {
-    uint64_t* bits; unsigned long long* sums;
-    int rc = dense_scratch(H, W, &bits, &sums);
-    if (rc) return rc;
-    hipStream_t s = (hipStream_t)stream;
-    rc = apse_k_dense_to_bits(mask, H, W, (W + 63) / 64, bits, sums, s);
-    if (rc) return rc;
-    rc = apse_k_closest_single(bits, H, W, (W + 63) / 64, px, py, sums + 3, s);
-    if (rc) return rc;
-    unsigned long long best;
-    if (hipMemcpyAsync(&best, sums + 3, sizeof best, hipMemcpyDeviceToHost, s) != hipSuccess) return APSE_E_HIP;
-    hipStreamSynchronize(s);
-    if (best == ~0ull) { out2[0] = out2[1] = -1; return APSE_OK; }
-    const unsigned lin = (unsigned)(best & 0xffffffffu);
-    out2[0] = (int)(lin % (unsigned)W) + 1;
-    out2[1] = (int)(lin / (unsigned)W) + 1;
-    return APSE_OK;
-}
-
-int apse_l2_normalize(const float* x, float* y, int n, int D, void* stream) {
-    return apse_k_l2_normalize(x, y, D, nullptr, n, (hipStream_t)stream);
-}
-int apse_sqdist(const float* a, const float* b, int O, int N, int D, float* out, void* stream) {
-    return apse_k_sqdist(a, b, O, N, D, out, (hipStream_t)stream);
-}
-static int fill_camera(UndistortParams& p, int H, int W, const double* m, const double* dist, int ndist, int do_undistort, int do_gamma) {
-    memset(&p, 0, sizeof p);
-    if (!m || ndist > 14 || ndist < 0 || (ndist > 0 && !dist)) return APSE_E_INVALID;
-    for (int i = 0; i < ndist && i < 12; ++i) p.k[i] = dist[i];
-    if (ndist > 12 && (dist[12] != 0.0 || (ndist > 13 && dist[13] != 0.0))) return APSE_E_INVALID;   // tilt model not built
-    // inverse of the 3x3 camera matrix (double, adjugate / determinant)
-    const double a = m[0], b = m[1], c = m[2], dd = m[3], e = m[4], f = m[5], g = m[6], h = m[7], k = m[8];
-    const double det = a * (e * k - f * h) - b * (dd * k - f * g) + c * (dd * h - e * g);
-    if (det == 0.0) return APSE_E_INVALID;
-    const double id = 1.0 / det;
-    p.ir[0] = (e * k - f * h) * id; p.ir[1] = (c * h - b * k) * id; p.ir[2] = (b * f - c * e) * id;
-    p.ir[3] = (f * g - dd * k) * id; p.ir[4] = (a * k - c * g) * id; p.ir[5] = (c * dd - a * f) * id;
-    p.ir[6] = (dd * h - e * g) * id; p.ir[7] = (b * g - a * h) * id; p.ir[8] = (a * e - b * dd) * id;
-    p.fx = m[0]; p.fy = m[4]; p.u0 = m[2]; p.v0 = m[5];
-    p.H = H; p.W = W; p.do_undistort = do_undistort; p.do_gamma = do_gamma;
-    return APSE_OK;
-}
-
-// Lab tables of a gamma LUT, device-resident for the stateless operator: one copy PER DEVICE (keyed by hipGetDevice), rebuilt
-// when the LUT changes, guarded by a mutex (the operator is a test / tool entry; a context keeps its own copy)
-static int lab_tables_device(const uint8_t* lut, hipStream_t s, LabTables** out) {
-    struct PerDev { LabTables* dev = nullptr; uint8_t lut[256]; bool have = false; };
-    static std::mutex mu;
-    static std::map<int, PerDev> cache;
-    static LabTables host;
-    int device = 0;
-    if (hipGetDevice(&device) != hipSuccess) return APSE_E_HIP;
-    std::lock_guard<std::mutex> lock(mu);
-    PerDev& e = cache[device];
-    if (!e.dev && hipMalloc(reinterpret_cast<void**>(&e.dev), sizeof(LabTables)) != hipSuccess) return APSE_E_NOMEM;
-    if (!e.have || memcmp(e.lut, lut, 256) != 0) {
-        hipStreamSynchronize(s);                       // an earlier launch may still read the previous tables
-        lab_tables_build(&host, lut);
-        if (hipMemcpy(e.dev, &host, sizeof(LabTables), hipMemcpyHostToDevice) != hipSuccess) return APSE_E_HIP;
-        memcpy(e.lut, lut, 256);
-        e.have = true;
-    }
-    *out = e.dev;
-    return APSE_OK;
-}
-
-int apse_undistort_gamma(const uint8_t* src, uint8_t* dst, int B, int H, int W, const double* m, const double* dist, int ndist,
-                         const uint8_t* lut, int do_undistort, int do_gamma, void* stream) {
-    if (!src || !dst || (do_gamma && !lut)) return APSE_E_INVALID;
-    UndistortParams p;
-    int rc = fill_camera(p, H, W, m, dist, ndist, do_undistort, do_gamma);
-    if (rc) return rc;
-    LabTables* lab = nullptr;
-    if (do_gamma && (rc = lab_tables_device(lut, (hipStream_t)stream, &lab))) return rc;
-    return apse_k_undistort_gamma(&p, src, dst, lab, B, (hipStream_t)stream);
-}
-
-size_t apse_lab_tables_host(const uint8_t* lut256, void* out, size_t cap) {
-    if (!lut256 || !out || cap < sizeof(LabTables)) return sizeof(LabTables);
-    lab_tables_build(reinterpret_cast<LabTables*>(out), lut256);
-    return sizeof(LabTables);
-}
-
 int apse_set_camera(apse_ctx* c, const double* m, const double* dist, int ndist, const uint8_t* lut_host, int do_undistort, int do_gamma) {
     if (!c) return APSE_E_INVALID;
     if (!do_undistort && !do_gamma) { c->cam_on = false; return APSE_OK; }
@@ -2016,11 +807,6 @@ int apse_set_camera(apse_ctx* c, const double* m, const double* dist, int ndist,
     c->cam = p;
     c->cam_on = true;
     return APSE_OK;
-}
-int apse_resize_normalize(const uint8_t* frames, uint8_t* tmp, float* out, uint8_t* resized, const int* hb, const int* hc, int hk,
-                          const int* vb, const int* vc, int vk, int B, int H, int W, int OH, int OW, int PH, int PW,
-                          const float* mean3, void* stream) {
-    return apse_k_pil_resize(frames, tmp, out, 0, resized, hb, hc, hk, vb, vc, vk, B, H, W, OH, OW, PH, PW, mean3, nullptr, nullptr, nullptr, nullptr, 0, (hipStream_t)stream);
 }
 
 }  // extern "C"

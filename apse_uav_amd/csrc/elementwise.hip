@@ -5,7 +5,7 @@
 //    (/root/reference/dcnn/engines/track_predictor.py:48-49, dcnn/networks/track_rcnn.py:35).
 //  * stem max-pool 3x3/2 and FPN p6 subsample (detectron2 ResNet stem / LastLevelMaxPool,
 //    reached from track_rcnn.py:42).
-#include "apse_common.h"
+#include "apse_kernels.h"
 #include "preproc_pixel.h"
 #include <string.h>
 #include <stdio.h>

@@ -11,24 +11,9 @@
 //                     (dcnn/utils/mask_utils.py:6-23 compute_closest_point); targets = every detection's
 //                     centroid in the same image, so the host pick (which needs track ids) happens later.
 // f32 arithmetic is compiled with -ffp-contract=off (products and sums rounded like the CPU path).
-#include "apse_common.h"
+#include "apse_kernels.h"
 
-struct PasteParams {
-    const float* boxes;      // packed [n][4], resized-image coordinates
-    const int* cls;          // packed [n]
-    const int* total;        // device count of packed detections
-    const float* logits;     // [n][M][M][ldc] mask head output (NHWC), class channel = cls[n]
-    int M, ldc;
-    float sx, sy;            // output/resized scale factors (f32 of the Python doubles)
-    int out_h, out_w;
-    int words_per_row;       // ceil(out_w / 64)
-    float thresh;
-    float* boxes_out;        // [n][4] scaled + clipped boxes
-    int* valid;              // [n] nonempty after scaling
-    int* rect;               // [n][4] x0, y0, x1, y1 paste window
-    uint64_t* bits;          // [n][out_h][words_per_row]
-    unsigned long long* sums;   // [n][3] mass, sum(x+1), sum(y+1): zero when the launch starts (pack_detections clears them)
-};
+// PasteParams: apse_kernels.h
 
 #define MT_TARGETS 100            // detections per image (TEST.DETECTIONS_PER_IMAGE <= 100, apse_create)
 #define MT_MAXDET 1024            // packed detections per forward (apse_create enforces max_batch * dets_per_image <= this)

@@ -22,7 +22,7 @@
 //   predictor     dX = d W[class] under the deconvolution's ReLU mask, dW[class] and db[class]: per-RoI sums, then RoIs in
 //                 ascending order per class.
 // Determinism: no float atomics; every sum has a fixed order that depends on the shapes only.
-#include "apse_common.h"
+#include "apse_kernels.h"
 #include "../../include/apse_hip.h"
 #include <math.h>
 #include <string.h>
@@ -32,7 +32,7 @@ namespace {
 constexpr int kC = 256;                 // channels of the head
 constexpr int kPool = 14, kUp = 28;     // RoI grid, logits grid
 constexpr int kPix = kPool * kPool, kUpPix = kUp * kUp;
-constexpr int kPlanDets = 8;            // APSE_EXPECTED_DETS of detector.hip: the list length a context shapes its mask-head GEMMs for
+constexpr int kPlanDets = 8;            // APSE_EXPECTED_DETS of plan.hip: the list length a context shapes its mask-head GEMMs for
 
 int invalid(const char* msg) { return apse_fail_global(APSE_E_INVALID, msg); }
 int launched() { return hipGetLastError() == hipSuccess ? APSE_OK : apse_fail_global(APSE_E_HIP, "mask_train: kernel launch failed"); }

@@ -4,7 +4,7 @@
 // The per-pixel arithmetic lives in preproc_pixel.h; inside a context the same function feeds the horizontal resize pass
 // directly (apse_set_camera -> pil_resize_h<true>), so this stand-alone form (24.9 MB read + 24.9 MB written per 4K frame)
 // is the stateless operator of the tests / FramePreprocessor only.
-#include "apse_common.h"
+#include "apse_kernels.h"
 #include "preproc_pixel.h"
 
 __global__ __launch_bounds__(256) void undistort_gamma(const UndistortParams p, const uint8_t* __restrict__ src,

@@ -5,15 +5,10 @@
 //  * l2_normalize, sqdist_matrix : AssociationHead's F.normalize (dcnn/networks/association_head.py:25)
 //                     and RcnnTracker.calculate_distance_matrix (dcnn/engines/rcnn_tracker.py:192-221)
 // Output layout is [roi][ph][pw][C]; the consuming FC weights are permuted (c,h,w)->(h,w,c) at load.
-#include "apse_common.h"
+#include "apse_kernels.h"
 #include <float.h>
 
-struct FpnMaps {
-    const void* p[4];      // p2..p5, each [B][H][W][256], f32 or 16-bit (st)
-    int H[4], W[4];
-    float scale[4];        // 1/4 .. 1/32
-    int st;                // storage type of the maps: 0 f32, 1 bf16, 2 f16
-};
+// FpnMaps: apse_kernels.h
 
 __device__ __forceinline__ f32x4 ld4(const float* p) { return *reinterpret_cast<const f32x4*>(p); }
 

@@ -10,10 +10,10 @@
 //                                                             nms_percat, rank_final
 //   FastRCNNOutputs.inference / fast_rcnn_inference_single_image -> box_candidates,
 //                                                             nms_percat, rank_final
-#include "apse_common.h"
+#include "apse_kernels.h"
 
 #define TK_N 4096          // elements sorted per block in the top-k tournament
-#define NMS_MAX 1024       // boxes per category (<= 1000 by construction)
+#define NMS_MAX APSE_NMS_SLOT   // boxes per category (<= 1000 by construction); the host sizes the keep lists by the same constant
 
 __device__ __forceinline__ uint32_t mono_key(float f) {   // order-preserving float -> uint
     uint32_t u = __float_as_uint(f);
@@ -96,28 +96,7 @@ __device__ __forceinline__ void block_bitonic_sort(uint64_t* a, int tid) {
 }
 
 // ---------------------------------------------------------------- RPN top-k tournament
-struct RpnLevel {
-    const float* head;     // [B][H*W][head_ld] : channels 0..2 objectness, 3..14 deltas (a*4+coord)
-    int H, W, stride;
-    int n;                 // H*W*3
-    int k;                 // min(pre_topk, n)
-    float base[3][4];      // cell anchors (x0,y0,x1,y1)
-};
-struct RpnLevels {
-    RpnLevel lv[5];
-    int head_ld;
-    int pre_topk;          // 1000
-};
-struct TopkJob {
-    int kind;              // 0: raw logits chunk, 1: merge of lists
-    int level;
-    int begin, count;      // kind 0: element range within the level
-    int nsrc;
-    int src[4];            // kind 1: source list slots
-    int src_count[4];
-    int dst;               // destination list slot
-    int dst_count;         // min(pre_topk, total)
-};
+// RpnLevel, RpnLevels, TopkJob: apse_kernels.h (filled by plan.hip)
 
 // lists: [B][nslots][1024] u64.  kind 0: sort one 4096-element chunk of raw logits (bitonic, LDS).
 // kind 1: merge up to four sorted lists by rank (position + binary-search counts in the other lists):

@@ -15,7 +15,7 @@
 // Block = 4 waves.  Wave w holds the filters of output channels 32 (w & 1) .. + 31 in registers (16 taps x 16 B per lane)
 // for the whole (persistent) block and takes five of the ten 32-row tiles of the 297 convolution outputs; A fragments come
 // straight from the input tile in LDS: lane (row, slot) reads the 16 bytes of channels 8 slot .. + 7 of pixel (oy + ky, ox + kx).
-#include "apse_common.h"
+#include "apse_kernels.h"
 #include <type_traits>
 
 #define SP_TPH 4

@@ -3,7 +3,7 @@
 The transforms are written out here once, in the kernel's operation order, so that the CPU tests can check the
 matrices and the numerics of the f32 Winograd path without a GPU:
 
-    U = G g G^T        (filter, 4x4 per (cout, cin): computed in float64, rounded to f32 once; detector.hip does the same)
+    U = G g G^T        (filter, 4x4 per (cout, cin): computed in float64, rounded to f32 once; plan.hip does the same)
     V = B^T d B        (input tile 4x4: row combinations first, then column combinations, every step in f32)
     M = sum_cin U * V  (per transform component xi = 4 i + j, channels ascending)
     Y = A^T M A        (output 2x2: row combinations first, then column combinations), + bias, optional ReLU

@@ -83,7 +83,7 @@ def _live_bytes(model, res):
 def history_independence(tracker, frame_a, image_hw, rng_seed=0):
     """Frame A after forwards that left 0, 8 and 100 detections in the packed list must give the same BYTES: the
     tile shape / K split of the count-limited GEMMs (mask head, deconv, mask logits, association FC) are plan
-    constants, the previous count only sizes their grid (csrc/detector.hip add_conv / run_plan)."""
+    constants, the previous count only sizes their grid (csrc/plan.hip add_conv, csrc/detector.hip run_plan)."""
     pr = tracker.predictor
     model = pr.model
     dev = pr._upload([frame_a])
