@@ -7,6 +7,51 @@ import torch
 from apse_uav_amd import _lib
 
 
+# ---------------------------------------------------------------------------------------------- kernel launchers (roi.hip)
+class FpnMaps(C.Structure):
+    """Mirror of ``struct FpnMaps``.  apse_uav_amd/csrc/apse_kernels.h is the source of truth: four map pointers (p2..p5, each
+    [B][H][W][256]), H[4], W[4], scale[4] and the storage type st (0 f32, 1 bf16, 2 f16).  The launcher takes it by HOST pointer."""
+    _fields_ = [("p", C.c_void_p * 4), ("H", C.c_int * 4), ("W", C.c_int * 4), ("scale", C.c_float * 4), ("st", C.c_int)]
+
+
+_vp, _i, _f = C.c_void_p, C.c_int, C.c_float
+# argument tables of the ``apse_k_*`` launchers of csrc/roi.hip, in the order apse_kernels.h declares them (exported from
+# libapse_hip.so with default visibility; the last argument is the stream)
+ROI_KERNEL_SIG = {
+    "apse_k_roi_align": ([C.POINTER(FpnMaps), _vp, _vp, _vp, _vp, _i, _i, _i, _vp, _i, _vp], _i),
+    "apse_k_roi_pool": ([_vp, _i, _i, _i, _vp, _vp, _vp, _i, _i, _f, _vp, _i, _i, _vp], _i),
+    "apse_k_roi_align_c4": ([_vp, _i, _i, _i, _f, _vp, _vp, _vp, _vp, _i, _i, _i, _vp, _vp], _i),
+    "apse_k_roi_pool_c4": ([_vp, _i, _i, _i, _vp, _vp, _vp, _i, _i, _f, _vp, _vp], _i),
+    "apse_k_mean_cells": ([_vp, _i, _i, _i, _vp, _vp], _i),
+    "apse_k_mask_resize": ([_vp, _i, _i, _i, _i, _i, _vp, _vp], _i),
+    "apse_k_roi_align_masked": ([_vp, _i, _i, _i, _i, _vp, _vp, _i, _i, _i, _f, _vp, _vp], _i),
+    "apse_k_l2_normalize": ([_vp, _vp, _i, _vp, _i, _vp], _i),
+    "apse_assoc_fc_ok": ([_i, _i], C.c_bool),
+    "apse_k_assoc_fc": ([_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _vp, _vp, _vp], _i),
+    "apse_k_sqdist": ([_vp, _vp, _i, _i, _i, _vp, _vp], _i),
+}
+
+
+def roi_kernels():
+    """The loaded library with the roi.hip launchers' argument types set."""
+    lib = _lib.load()
+    for name, (args, ret) in ROI_KERNEL_SIG.items():
+        fn = getattr(lib, name)
+        fn.argtypes = args
+        fn.restype = ret
+    return lib
+
+
+def fpn_maps(tensors, dims, st, scales=(0.25, 0.125, 0.0625, 0.03125)):
+    F = FpnMaps()
+    for k in range(4):
+        F.p[k] = tensors[k].data_ptr()
+        F.H[k], F.W[k] = dims[k]
+        F.scale[k] = scales[k]
+    F.st = st
+    return F
+
+
 def to_nhwc(x, cpad=None):
     x = x.permute(0, 2, 3, 1).contiguous()
     if cpad and cpad > x.shape[3]:

@@ -13,6 +13,8 @@ import pytest
 import torch
 import torch.nn.functional as F
 
+import roi_ref
+
 pytestmark = pytest.mark.gpu
 
 
@@ -403,8 +405,9 @@ def test_roi_align_parity(logdir):
                          (cy + bh / 2).clamp(0, 192)], dim=1)
     boxes[0] = torch.tensor([0., 0., 336., 192.])
     boxes[1] = torch.tensor([10., 10., 10.5, 10.2])
-    boxes[2] = torch.tensor([0., 80., 336., 108.])        # wide and flat on the finest level: 13 samples per bin across, a
-    #                                                       tap window wider than RA_CAP cells -> the per-sample loop
+    boxes[2] = torch.tensor([0., 80., 336., 108.])        # wide and flat on the finest level: 12 samples per bin across, tap
+    #                                                       windows of 13 cells: still the separable form (the per-sample
+    #                                                       loop needs 17; tests/test_gpu_roi_ops.py reaches it)
     boxes[3] = torch.tensor([-20., -30., 40., 25.])       # samples left of / above the map
     boxes[4] = torch.tensor([300., 170., 400., 260.])     # samples right of / below the map
     for R in (7, 14):
@@ -420,6 +423,13 @@ def test_roi_align_parity(logdir):
         st = err_stats(out.cpu().permute(0, 3, 1, 2), ref)
         _log(logdir, "roi_align/%d" % R, st)
         assert st["nan"] == 0 and st["max_abs"] < 1e-4, st       # f32, bilinear weights: order-of-sum noise
+        # and element by element inside the derived f32 bound of the float64 reference (tests/roi_ref.py)
+        host = [to_nhwc(f).numpy() for f in feats]
+        plan = roi_ref.roi_align_plan(boxes.numpy(), sizes, roi_ref.FPN_SCALES, R)
+        res = roi_ref.roi_align_apply(plan, np.zeros(n, np.int64), lambda lv, img, y0, y1, x0, x1: host[lv][img, y0:y1, x0:x1], R)
+        ok, worst = roi_ref.check(out.cpu().numpy(), res)
+        _log(logdir, "roi_align_bound/%d" % R, dict(worst_err_over_bound=worst))
+        assert ok, worst
 
 
 @pytest.mark.parametrize("st,dtype", [(1, torch.bfloat16), (2, torch.float16)])
@@ -442,7 +452,7 @@ def test_roi_align_16bit_maps(logdir, st, dtype):
                          (cy + bh / 2).clamp(0, 192)], dim=1)
     boxes[0] = torch.tensor([0., 0., 336., 192.])
     boxes[1] = torch.tensor([10., 10., 10.5, 10.2])         # one sample per bin, window of 1-2 cells (odd tail of a half-wave)
-    boxes[2] = torch.tensor([0., 80., 336., 108.])          # per-sample loop
+    boxes[2] = torch.tensor([0., 80., 336., 108.])          # the widest windows an 84-cell map gives (13 cells: separable form)
     boxes[per] = torch.tensor([-20., -30., 40., 25.])
     boxes[per + 1] = torch.tensor([300., 170., 400., 260.])
     fd = [to_nhwc(f.float()).to(dtype).cuda().contiguous() for f in feats]
