@@ -153,6 +153,7 @@ def load():
         "apse_mots_split_idmap": ([vp, i, i, i, vp, sz, vp, vp, vp, vp, sz, vp], i),
         "apse_mots_rle_to_bits": ([vp, vp, i, i, i, vp, vp], i),
         "apse_mots_overlaps": ([vp, i, vp, i, vp, i, vp, vp], i),
+        "apse_mots_shift_overlaps": ([vp, i, vp, i, i, i, vp, vp], i),
         "apse_mots_render_idmap": ([vp, vp, i, i, i, vp, vp], i),
         "apse_resize_normalize": ([vp, vp, vp, vp, vp, vp, i, vp, vp, i, i, i, i, i, i, i, i, C.POINTER(f * 3), vp], i),
         "apse_assoc_fc_workspace_bytes": ([i, i, i], sz),
@@ -203,7 +204,7 @@ EXPORTS = ["apse_create", "apse_destroy", "apse_last_error", "apse_version", "ap
            "apse_l2_normalize", "apse_sqdist", "apse_undistort_gamma", "apse_lab_tables_host", "apse_resize_normalize", "apse_replay_create", "apse_replay_destroy",
            "apse_replay_step", "apse_replay_packed", "apse_replay_max_id", "apse_replay_next_id", "apse_render_workspace_bytes",
            "apse_render_instances", "apse_render_pack_mask", "apse_render_font_host", "apse_mots_split_workspace_bytes",
-           "apse_mots_split_idmap", "apse_mots_rle_to_bits", "apse_mots_overlaps", "apse_mots_render_idmap",
+           "apse_mots_split_idmap", "apse_mots_rle_to_bits", "apse_mots_overlaps", "apse_mots_shift_overlaps", "apse_mots_render_idmap",
            "apse_assoc_fc_workspace_bytes", "apse_assoc_fc_forward", "apse_assoc_fc_backward", "apse_triplet_workspace_bytes",
            "apse_triplet_hard_forward", "apse_triplet_all_forward", "apse_triplet_hard_backward", "apse_triplet_all_backward",
            "apse_sgd_step", "apse_coco_box_iou", "apse_coco_poly_to_bits", "apse_coco_match",

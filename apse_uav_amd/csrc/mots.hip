@@ -6,6 +6,8 @@
 //                 values in ascending order and packs the windows, and the bits (one wave per window row: one __ballot per word)
 //   rle_to_bits   one wave per window row, one lane per pixel: the run holding the pixel is an upper_bound over the run ends
 //   overlaps      one block per pair: popcounts of the words of a's window against b's (or the OR of the union list's) words
+//   shift_overlaps  one block per pair: the same counts with a translated by (dx, dy) and cropped to the frame (the mask-IoU
+//                 association metric, utils/mask_utils.py): a funnel shift of two of a's words against each word of b
 //   render_idmap  one wave per 64-pixel row segment: each lane keeps the owner of its pixel over the objects in index order
 // Only integer arithmetic and order-independent integer atomics: every result is exact and bit-reproducible.
 #include "apse_common.h"
@@ -234,6 +236,77 @@ __global__ void __launch_bounds__(256) overlaps_kernel(const apse_mots_window* w
     }
 }
 
+// ---------------------------------------------------------------- shift_overlaps
+__device__ __forceinline__ int wave_sum(int v) {             // wave64 butterfly: every lane must arrive
+    for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off);
+    return v;
+}
+
+// bits lo..hi-1 of a word for 64-bit bounds that may lie anywhere: the part of [lo, hi) inside [0, 64)
+__device__ __forceinline__ uint64_t clip_mask(long long lo, long long hi) {
+    lo = lo < 0 ? 0 : lo;
+    hi = hi > 64 ? 64 : hi;
+    return lo < hi ? span_mask((int)lo, (int)hi) : 0;
+}
+
+// T(a) = a moved by (dx, dy), zero fill, cropped to the H x W frame.  |T(a)| is counted over a's own words (each word keeps
+// the pixels whose target column is inside the frame); |T(a) & b| over b's words, where the word of T(a) at absolute word
+// column bw is the funnel shift of a's words q and q + 1 with bw * 64 - dx = q * 64 + off, 0 <= off < 64 (floor division:
+// the offset is never negative, and off == 0 takes no second word, so no shift by 64 occurs).
+__global__ void __launch_bounds__(256) shift_overlaps_kernel(const apse_mots_window* windows, int n_windows, const int* quads,
+                                                             int H, int W, int* out) {
+    __shared__ int s_sum[3];
+    if (threadIdx.x < 3) s_sum[threadIdx.x] = 0;
+    __syncthreads();
+    const int p = blockIdx.x;
+    const int ia = quads[4 * p], ib = quads[4 * p + 1];
+    apse_mots_window a = {}, b = {};                         // an index outside the list: the empty mask
+    if (ia >= 0 && ia < n_windows) a = windows[ia];
+    if (ib >= 0 && ib < n_windows) b = windows[ib];
+    const long long dx = quads[4 * p + 2], dy = quads[4 * p + 3];
+    int inter = 0, area_t = 0, area_b = 0;
+    const int ax0 = a.rect[0] >> 6;
+    const int arows = a.rect[3] - a.rect[1];
+    const long long awords = a.rect[0] < a.rect[2] && arows > 0 && a.bits ? (long long)arows * a.words_per_row : 0;
+    for (long long i = threadIdx.x; i < awords; i += 256) {
+        const int r = (int)(i / a.words_per_row), c = (int)(i - (long long)r * a.words_per_row);
+        const int y = a.rect[1] + r, aw = ax0 + c;
+        const long long ty = y + dy;
+        if (ty < 0 || ty >= H) continue;
+        const long long x0 = (long long)aw * 64 + dx;        // target column of bit 0
+        area_t += __popcll(window_word(a, y, aw) & clip_mask(-x0, W - x0));
+    }
+    const int bx0 = b.rect[0] >> 6;
+    const int brows = b.rect[3] - b.rect[1];
+    const long long bwords = b.rect[0] < b.rect[2] && brows > 0 && b.bits ? (long long)brows * b.words_per_row : 0;
+    for (long long i = threadIdx.x; i < bwords; i += 256) {
+        const int r = (int)(i / b.words_per_row), c = (int)(i - (long long)r * b.words_per_row);
+        const int y = b.rect[1] + r, bw = bx0 + c;
+        const uint64_t wb = window_word(b, y, bw);
+        if (!wb) continue;
+        area_b += __popcll(wb);
+        const long long sy = y - dy;                          // source row in a
+        if (y < 0 || y >= H || sy < a.rect[1] || sy >= a.rect[3]) continue;
+        const long long s = (long long)bw * 64 - dx;         // source column of bit 0
+        const long long q = s >= 0 ? s >> 6 : -((-s + 63) >> 6);
+        const int off = (int)(s - q * 64);
+        uint64_t t = window_word(a, (int)sy, (int)q) >> off;
+        if (off) t |= window_word(a, (int)sy, (int)q + 1) << (64 - off);
+        t &= clip_mask(-(long long)bw * 64, W - (long long)bw * 64);
+        inter += __popcll(t & wb);
+    }
+    inter = wave_sum(inter);
+    area_t = wave_sum(area_t);
+    area_b = wave_sum(area_b);
+    if ((threadIdx.x & 63) == 0) {                           // one LDS add per wave and count
+        atomicAdd(&s_sum[0], inter);
+        atomicAdd(&s_sum[1], area_t);
+        atomicAdd(&s_sum[2], area_b);
+    }
+    __syncthreads();
+    if (threadIdx.x < 3) out[3 * p + threadIdx.x] = s_sum[threadIdx.x];
+}
+
 // ---------------------------------------------------------------- render_idmap
 __global__ void __launch_bounds__(256) render_idmap_kernel(const apse_mots_object* __restrict__ objs, int n, int H, int W,
                                                            uint16_t* __restrict__ idmap, RenderValues vals) {
@@ -300,6 +373,15 @@ int apse_mots_overlaps(const apse_mots_window* windows, int n_windows, const int
     if (n_union > 0 && !union_idx) return APSE_E_INVALID;
     if (npairs == 0) return APSE_OK;
     overlaps_kernel<<<npairs, 256, 0, (hipStream_t)stream>>>(windows, pairs, union_idx, n_union, out);
+    return hipGetLastError() == hipSuccess ? APSE_OK : APSE_E_HIP;
+}
+
+int apse_mots_shift_overlaps(const apse_mots_window* windows, int n_windows, const int* quads, int npairs, int H, int W,
+                             int* out, void* stream) {
+    if (!frame_ok(H, W) || n_windows < 0 || npairs < 0 || npairs > APSE_MOTS_MAX_PAIRS) return APSE_E_INVALID;
+    if (npairs > 0 && (!windows || !quads || !out || n_windows < 1)) return APSE_E_INVALID;
+    if (npairs == 0) return APSE_OK;
+    shift_overlaps_kernel<<<npairs, 256, 0, (hipStream_t)stream>>>(windows, n_windows, quads, H, W, out);
     return hipGetLastError() == hipSuccess ? APSE_OK : APSE_E_HIP;
 }
 

@@ -26,7 +26,7 @@ import numpy as np
 import torch
 
 from ..networks.track_rcnn import TrackRCNN
-from .rcnn_tracker import RcnnTracker, instances_from_record
+from .rcnn_tracker import RcnnTracker, instances_from_record, require_embeddings_metric
 from .track_predictor import FrameUploader
 
 
@@ -36,6 +36,7 @@ MAX_DEPTH = 8           # ~250 MB of weights + 1.6 GB of activations per slot; b
 class PipelinedRcnnTracker:
     def __init__(self, config, image_size, weights, depth=3, want_masks=False, detector_state=None, **tracker_kwargs):
         assert 1 <= depth <= MAX_DEPTH, "depth 1..%d" % MAX_DEPTH
+        require_embeddings_metric(tracker_kwargs.get("association_metric", "embeddings"), "PipelinedRcnnTracker")
         self.tracker = RcnnTracker(config, image_size, weights, detector_state=detector_state, **tracker_kwargs)
         self.depth = depth
         self.want_masks = want_masks

@@ -5,8 +5,11 @@ Same constructor signature, attributes, constants and per-frame semantics
 detector -> ROI-pooled p2 features -> 128-d embedding -> squared-L2 distance matrix ->
 Hungarian assignment (scipy, as in the reference) -> ``dist < 0.6`` associates, other
 detections become new objects in detection order -> objects unseen for > 100 frames are
-dropped.  The metric is hard-wired to 'embeddings' like the reference's ``next_frame`` (:69);
-its other two branches are dead code there (undefined names).
+dropped.  ``association_metric`` selects the metric: 'embeddings' (the default, the only one the reference's
+``next_frame`` reaches, :69), or the reference's two other branches, dead there only through undefined names
+(:91-120) and restated here from their rules: 'mask_iou' (greedy, centroid-aligned mask IoU
+>= 0.7 against every stored object, utils/mask_utils.py) and 'bbox_center_dist' (every object whose box centre is
+within a squared pixel distance).  Neither needs an association head: ``weights=None`` is accepted with them.
 
 GPU work (detector, roi_pool, association FC + normalise, distance matrix, mask centroid /
 closest points) runs in ``libapse_hip.so``; the sequential id bookkeeping stays on the host.
@@ -22,22 +25,36 @@ from ..networks.association_head import AssociationHead
 from ..structures.instances import Boxes, Instances
 from ..structures.object_instances import ObjectInstances
 from ..structures.window_mask import MaskList, WindowMask
-from ..utils import csv_log
+from ..utils import csv_log, mask_utils
 from ..weights import load_association_file
 from .track_predictor import TrackPredictor
 
 # module-level constants, as in the reference (rcnn_tracker.py:32-34 keeps them outside the config too)
 ASSOCIATION_ROI_SIZE = 10
+ASSOCIATION_METRICS = ('embeddings', 'mask_iou', 'bbox_center_dist')
+
+
+def require_embeddings_metric(metric, who):
+    """The drivers that associate from records alone (pipelined, native replay) know the 'embeddings' metric only."""
+    if metric != 'embeddings':
+        raise NotImplementedError("%s associates with the 'embeddings' metric only (got %r): use RcnnTracker.next_frame"
+                                  % (who, metric))
 
 
 class RcnnTracker:
 
     def __init__(self, config, image_size, weights, association_metric='embeddings', DISPLAY_INFO=[], metadata=None,
-                 detector_state=None):
+                 detector_state=None, bbox_center_dist_threshold=None):
+        if association_metric not in ASSOCIATION_METRICS:
+            raise ValueError("association_metric %r: expected one of %s" % (association_metric, ", ".join(ASSOCIATION_METRICS)))
+        if weights is None and association_metric == 'embeddings':
+            raise ValueError("the 'embeddings' metric needs association head weights (weights=None)")
         self.metadata = metadata
         self.DISPLAY_INFO = DISPLAY_INFO
         self.association_metric = association_metric
         self.MASKS_IOU_THRESHOLD = 0.7
+        # squared pixel distance of box centres; the reference never defines it (rcnn_tracker.py:101), so there is no default
+        self.BBOX_CENTER_DIST_THRESHOLD = bbox_center_dist_threshold
         self.ASSOCIATION_EMBEDDING_THRESHOLD = 0.6
         self.OBJECT_UNDETECTED_FRAMES_TH = 100
         self.crop_features = False
@@ -48,11 +65,13 @@ class RcnnTracker:
         self.backbone_features_depth = self.predictor.model.backbone.output_shape()[
             config.MODEL.ROI_HEADS.IN_FEATURES[0]].channels
 
-        self.association_head = AssociationHead(roi_size=ASSOCIATION_ROI_SIZE, input_depth=self.backbone_features_depth)
-        state = load_association_file(weights) if isinstance(weights, str) else weights
-        self.association_head.load_state_dict(state)
-        self.association_head.to(self.device)
-        self.predictor.model.attach_association_head(self.association_head)
+        self.association_head = None
+        if weights is not None:
+            self.association_head = AssociationHead(roi_size=ASSOCIATION_ROI_SIZE, input_depth=self.backbone_features_depth)
+            state = load_association_file(weights) if isinstance(weights, str) else weights
+            self.association_head.load_state_dict(state)
+            self.association_head.to(self.device)
+            self.predictor.model.attach_association_head(self.association_head)
 
         self.objects = ObjectInstances(image_size=image_size, display_info=self.DISPLAY_INFO, metadata=metadata)
         self.frame_count = 0
@@ -72,6 +91,8 @@ class RcnnTracker:
 
     def next_record(self, record):
         """Same association driven by a per-frame record (FrameResults.record)."""
+        if self.association_metric == 'mask_iou':
+            raise NotImplementedError("'mask_iou' needs the mask bits and a record carries none: use next_frame")
         self.frame_count += 1
         return self._finish_frame(instances_from_record(record, self.image_size, self.device), None, host_replay=True)
 
@@ -79,7 +100,7 @@ class RcnnTracker:
         """``host_replay`` is accepted for older callers; since round 4 the record path always associates on the host."""
         self._last_record = getattr(detections, "_record", None)
         self._obj_det = {}
-        self.associate_detections_to_objects(detections, backbone_features=backbone_features, metric='embeddings')
+        self.associate_detections_to_objects(detections, backbone_features=backbone_features, metric=self.association_metric)
         self.objects.delete_undetected_objects(self.OBJECT_UNDETECTED_FRAMES_TH)
         if 'objects' in self.DISPLAY_INFO: print(self.objects)
         recent_objects = self.objects.get_recent_objects()
@@ -90,10 +111,72 @@ class RcnnTracker:
     def associate_detections_to_objects(self, detections, backbone_features=None, metric='embeddings'):
         if 'detections' in self.DISPLAY_INFO:
             print(len(detections), ' detections:')
-        if metric != 'embeddings':
-            raise NotImplementedError("only the 'embeddings' metric is live in the reference (rcnn_tracker.py:69)")
-        if len(detections) > 0:
-            self._associate(detections, backbone_features)
+        if metric == 'bbox_center_dist':
+            self._associate_bbox_center_dist(detections)
+        elif metric == 'mask_iou':
+            self._associate_mask_iou(detections)
+        elif metric == 'embeddings':
+            if self.association_head is None:
+                raise ValueError("the 'embeddings' metric needs association head weights (weights=None)")
+            if len(detections) > 0:
+                self._associate(detections, backbone_features)
+        else:
+            raise ValueError("metric %r: expected one of %s" % (metric, ", ".join(ASSOCIATION_METRICS)))
+
+    def _associate_bbox_center_dist(self, detections):
+        """rcnn_tracker.py:91-106: every object whose box centre lies within the squared pixel distance takes the detection
+        (its box is overwritten at once, so a later detection meets the updated centre); a detection that matched none is a
+        new object.  Host arithmetic in f32, as ``Boxes.get_centers`` and ``torch.sum`` of the squares give."""
+        if self.BBOX_CENTER_DIST_THRESHOLD is None:
+            raise ValueError("'bbox_center_dist' needs a threshold: the reference never defines BBOX_CENTER_DIST_THRESHOLD; "
+                             "pass bbox_center_dist_threshold= (squared pixels)")
+        for detection_id in range(len(detections)):
+            center = detections.pred_boxes[detection_id].get_centers().cpu()
+            associated = False
+            for object_index in range(len(self.objects)):
+                object_center = self.objects.pred_boxes[object_index].get_centers().cpu()
+                dist = torch.sum((center - object_center) ** 2)
+                if dist < self.BBOX_CENTER_DIST_THRESHOLD:
+                    associated = True
+                    self.objects.associate_detection(detection_id, object_index, detections)
+                    self._obj_det[self.objects.ids[object_index]] = detection_id
+            if not associated:
+                self.objects.add_new_object(detection_id, detections)
+                self._obj_det[self.objects.ids[-1]] = detection_id
+
+    def _associate_mask_iou(self, detections):
+        """rcnn_tracker.py:108-120: detections in order; each takes the IoU of its centroid-aligned mask with every stored
+        object (stale ones included), the first maximum, and associates when it reaches MASKS_IOU_THRESHOLD, else becomes a
+        new object.  The reference reads ``self.objects.pred_masks`` afresh for every detection, so an object born or
+        re-associated earlier in the frame already carries that earlier detection's mask: the frame's matrix therefore has a
+        column for every stored object and one for every detection, and ``column[k]`` follows the mask object k holds.  It is
+        computed once (utils/mask_utils.masks_iou_matrix: one launch, one D2H copy)."""
+        n = len(detections)
+        if n == 0:
+            return
+        det_masks = list(detections.pred_masks)
+        n_obj = len(self.objects)
+        obj_masks = list(self.objects.pred_masks) if n_obj else []
+        iou = None
+        if n_obj + n > 1:
+            iou = mask_utils.masks_iou_matrix(det_masks, obj_masks + (det_masks if n > 1 else []))
+        column = list(range(n_obj))
+        for detection_id in range(n):
+            match_index = -1
+            if len(self.objects) > 0:
+                ious_with_objects = iou[detection_id, column]
+                match_index = int(np.argmax(ious_with_objects))
+                # the reference compares Python floats (.item() of the f32 quotient): f32(7) / f32(10) is below 0.7
+                if not float(ious_with_objects[match_index]) >= self.MASKS_IOU_THRESHOLD:
+                    match_index = -1
+            if match_index >= 0:
+                self.objects.associate_detection(detection_id, match_index, detections)
+                column[match_index] = n_obj + detection_id
+                self._obj_det[self.objects.ids[match_index]] = detection_id
+            else:
+                self.objects.add_new_object(detection_id, detections)
+                column.append(n_obj + detection_id)
+                self._obj_det[self.objects.ids[-1]] = detection_id
 
     def _associate(self, detections, backbone_features):
         rec = getattr(detections, "_record", None)

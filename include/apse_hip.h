@@ -6,6 +6,7 @@
  *   dcnn/networks/track_rcnn.py:16-58      TrackRCNN.inference       (preprocess, backbone+FPN, RPN, ROI heads, postprocess)
  *   dcnn/engines/rcnn_tracker.py:156-221   get_features_rois, association head, distance matrix
  *   dcnn/utils/mask_utils.py:6-38          get_mask_centroid, compute_closest_point
+ *   dcnn/utils/mask_utils.py:41-77         compute_masks_iou, translate_and_crop_mask (the 'mask_iou' association metric)
  * Each entry point below names the reference code it replaces.  apse_uav_amd/_lib.py is the ctypes
  * binding; INTEGRATION.md shows the stub a maintainer of the reference would add.
  *
@@ -346,8 +347,8 @@ size_t apse_render_font_host(uint8_t* out, size_t cap);
  * word 0 holds pixels (x0 >> 6) << 6 .. +63, bit i = pixel + i.  Bits outside the rect are ignored on input and 0 on output, so
  * two windows of one frame are aligned on absolute 64-pixel columns.
  * Limits (APSE_E_INVALID outside them): frames 1 <= H <= APSE_MAX_FRAME_H, 1 <= W <= APSE_MAX_FRAME_W; id maps u16; at most
- * APSE_MOTS_MAX_OBJECTS values per split and objects per render or RLE call; at most APSE_MOTS_MAX_PAIRS pairs and
- * APSE_MOTS_MAX_UNION union members per overlaps call.  KITTI MOTS frames hold tens of objects. */
+ * APSE_MOTS_MAX_OBJECTS values per split and objects per render or RLE call; at most APSE_MOTS_MAX_PAIRS pairs per overlaps or
+ * shift_overlaps call and APSE_MOTS_MAX_UNION union members per overlaps call.  KITTI MOTS frames hold tens of objects. */
 #define APSE_MOTS_MAX_OBJECTS 1024
 #define APSE_MOTS_MAX_PAIRS 65536
 #define APSE_MOTS_MAX_UNION 1024
@@ -381,6 +382,13 @@ int apse_mots_rle_to_bits(const int* ends, const int* ends_off, int n, int h, in
  * union_idx[0 .. n_union) (an empty list is the empty region), and out[p][2] = -1. */
 int apse_mots_overlaps(const apse_mots_window* windows, int n_windows, const int* pairs, int npairs, const int* union_idx,
                        int n_union, int* out, void* stream);
+/* out[p] = {|T(a) & b|, |T(a)|, |b|} for quads[p] = {a, b, dx, dy} over windows[0 .. n_windows): T(a) has pixel (x, y) set iff a
+ * has (x - dx, y - dy) set and 0 <= x < W, 0 <= y < H (translate, zero fill, crop to the frame).  The overlap of
+ * dcnn/utils/mask_utils.py:41-77 compute_masks_iou (translate_and_crop_mask, then intersection and union); utils/mask_utils.py
+ * divides.  Any dx, dy is legal (a shift of a whole frame or more gives |T(a)| = 0); an index outside the list is the empty
+ * mask.  0 <= npairs <= APSE_MOTS_MAX_PAIRS; npairs == 0 is a no-op. */
+int apse_mots_shift_overlaps(const apse_mots_window* windows, int n_windows, const int* quads, int npairs, int H, int W,
+                             int* out, void* stream);
 /* Tracked objects -> u16 id map [H][W] (device): every pixel belongs to the object of highest score among those whose mask holds
  * it (ties: highest index) and takes values_host[owner] (0: a class MOTS does not score), 0 where no mask is set.  Equal to
  * result_image_from_objects(crop_overlapping_masks(objects)).  objects: device [n]; values_host: host [n], 0..65535. */

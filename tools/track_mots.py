@@ -3,7 +3,7 @@
 standard_rcnn_tracker_test.py.
 
     python tools/track_mots.py SEQMAP --images IMAGE_DIR [--output DIR] [--eval GT_DIR] [--no-write]
-                               [--detector-state FILE] [--association-state FILE]
+                               [--detector-state FILE] [--association-state FILE] [--metric NAME]
 
 IMAGE_DIR holds one folder of PNG / JPEG / BMP frames per sequence (datasets/data_tracking_image_2/training/image_02 in the
 reference); frames are read with Pillow.  For every frame the tracker's objects become the u16 id map of
@@ -11,6 +11,7 @@ result_image_from_objects(crop_overlapping_masks(objects)), rendered on the devi
 (default output/evaluation_results, as the reference).  --eval GT_DIR scores the tracker online against the ground truth
 (utils/mots_eval.MotsEvaluator) and prints eval.py's tables; --no-write skips the PNGs.  Without state files the tracker runs
 on the seeded synthetic weights (apse_uav_amd.weights), which exercises the pipeline but detects nothing meaningful.
+--metric mask_iou tracks without an association head (no --association-state needed): centroid-aligned mask IoU >= 0.7.
 """
 import argparse
 import os
@@ -37,6 +38,7 @@ def main(argv=None):
     ap.add_argument("--no-write", action="store_true")
     ap.add_argument("--detector-state", default="", help="torch.load-able detector state dict")
     ap.add_argument("--association-state", default="", help="torch.load-able association head state dict")
+    ap.add_argument("--metric", default="embeddings", choices=["embeddings", "mask_iou"], help="association metric")
     args = ap.parse_args(argv)
     import torch
     from PIL import Image
@@ -49,6 +51,8 @@ def main(argv=None):
     from apse_uav_amd.weights import synthetic_association_state, synthetic_detector_state
     det = torch.load(args.detector_state) if args.detector_state else synthetic_detector_state(0)
     assoc = torch.load(args.association_state) if args.association_state else synthetic_association_state(1)
+    if args.metric != "embeddings" and not args.association_state:
+        assoc = None
     sequences, _ = parse_mots_seqmap(args.seqmap)
     print("Running evaluation for sequences:")
     for s in sequences:
@@ -59,7 +63,7 @@ def main(argv=None):
         names = image_files(seq_path)
         first = np.asarray(Image.open(os.path.join(seq_path, names[0])).convert("RGB"))
         size = first.shape[:2]
-        tracker = RcnnTracker(setup_cfg(), size, assoc, detector_state=det)
+        tracker = RcnnTracker(setup_cfg(), size, assoc, association_metric=args.metric, detector_state=det)
         out_dir = os.path.join(args.output, seq)
         if not args.no_write:
             os.makedirs(out_dir, exist_ok=True)
