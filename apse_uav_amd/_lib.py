@@ -184,6 +184,7 @@ def load():
         "apse_mask_loss_forward": ([vp, i, vp, vp, i, vp, vp, sz, vp], i),
         "apse_mask_loss_backward": ([vp, i, vp, vp, i, vp, vp, vp], i),
         "apse_mask_predictor_backward": ([vp, vp, vp, vp, i, i, vp, vp, vp, vp, sz, vp], i),
+        "apse_augment_u8": ([vp, i, i, i, vp, vp, vp, vp, vp], i),
     }
     for name, (args, ret) in sig.items():
         if name in TOOL_ENTRIES and LIB_PATH != _TREE_LIB and not hasattr(lib, name):
@@ -211,7 +212,7 @@ EXPORTS = ["apse_create", "apse_destroy", "apse_last_error", "apse_version", "ap
            "apse_coco_accumulate_workspace_bytes", "apse_coco_sort_lists", "apse_coco_accumulate",
            "apse_mask_roi_features", "apse_mask_train_workspace_bytes", "apse_mask_pack_elems", "apse_mask_pack_weight",
            "apse_mask_conv_forward", "apse_mask_conv3x3", "apse_mask_relu_grad", "apse_mask_bias_grad", "apse_mask_wgrad", "apse_mask_loss_forward",
-           "apse_mask_loss_backward", "apse_mask_predictor_backward"]
+           "apse_mask_loss_backward", "apse_mask_predictor_backward", "apse_augment_u8"]
 
 
 def stream_ptr():

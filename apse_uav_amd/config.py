@@ -127,11 +127,15 @@ def get_cfg():
             "ROI_MASK_HEAD": {"NAME": "MaskRCNNConvUpsampleHead", "NUM_CONV": 4, "CONV_DIM": 256,
                               "POOLER_RESOLUTION": 14, "POOLER_SAMPLING_RATIO": 0, "POOLER_TYPE": "ROIAlignV2"},
         },
-        "INPUT": {"MIN_SIZE_TEST": 800, "MAX_SIZE_TEST": 1333, "FORMAT": "BGR"},
+        # the *_TRAIN keys are detectron2's defaults; the reference's Base-RCNN-FPN.yaml, when merged, gives
+        # MIN_SIZE_TRAIN (640, 672, 704, 736, 768, 800)
+        "INPUT": {"MIN_SIZE_TEST": 800, "MAX_SIZE_TEST": 1333, "FORMAT": "BGR", "MIN_SIZE_TRAIN": (800,), "MAX_SIZE_TRAIN": 1333,
+                  "MIN_SIZE_TRAIN_SAMPLING": "choice"},
         "TEST": {"DETECTIONS_PER_IMAGE": 100},
         "DATASETS": {"TRAIN": ("coco_2017_train",), "TEST": ("coco_2017_val",)},
         # build-specific knobs (not in the reference): storage dtype and batch of the HIP path
-        "APSE": {"DTYPE": "f32", "MAX_BATCH": 1, "FUSED_PREPROC": True, "STORAGE16": True},
+        # CONTEXT_CACHE: live contexts TrackRCNN keeps, one per (frame size, image size); 1 = rebuild at every size change
+        "APSE": {"DTYPE": "f32", "MAX_BATCH": 1, "FUSED_PREPROC": True, "STORAGE16": True, "CONTEXT_CACHE": 1},
     })
 
 

@@ -65,6 +65,17 @@ struct PasteParams {
     uint64_t* bits;          // [n][out_h][words_per_row]
     unsigned long long* sums;   // [n][3] mass, sum(x+1), sum(y+1): zero when the launch starts (pack_detections clears them)
 };
+// ---------------------------------------------------------------- training augmentation (augment.hip)
+// One image's parameters as the kernels read them: the f32 weights and the f64 complements, rounded on the host exactly once
+struct AugmentImage {
+    double one_minus_ws, one_minus_wc;   // 1.0 - saturation, 1.0 - contrast (f64)
+    double vec[3];                       // lighting: EIGVEC . (lw * EIGVAL), added to channel 0, 1, 2
+    float wb, ws, wc;                    // f32 of the brightness, saturation and contrast weights
+    int flip;
+};
+struct AugmentBatch {
+    AugmentImage im[64];                 // APSE_AUGMENT_MAX_BATCH; a kernel argument (3.5 KiB)
+};
 
 extern "C" {
 // ---- elementwise.hip
@@ -149,4 +160,7 @@ int apse_k_dense_to_bits(const uint8_t* dense, int out_h, int out_w, int words_p
                          unsigned long long* sums, hipStream_t s);
 // ---- mask_train.hip
 int apse_k_mask_roi_index(int* idx, int n, hipStream_t s);
+// ---- augment.hip
+int apse_k_augment(const uint8_t* src, int B, int H, int W, const AugmentBatch* P_host, uint8_t* out_u8, float* out_chw,
+                   unsigned long long* sums, hipStream_t s);
 }

@@ -6,6 +6,7 @@ sequence of hand-written HIP kernels inside ``libapse_hip.so`` (include/apse_hip
 owns the library context, feeds it weights (detectron2 state_dict key names) and turns the
 results block into the reference's return types.  There is no CPU fallback.
 """
+import collections
 import ctypes as C
 
 import numpy as np
@@ -120,6 +121,10 @@ class TrackRCNN:
         self._assoc = None
         self._ctx = None
         self._ctx_key = None
+        # live contexts, least recently used first: key -> (ctx, results layout, pinned host block, config struct).  At most
+        # cfg.APSE.CONTEXT_CACHE of them (default 1: a size change rebuilds, as TrackPredictor's pre-staging assumes); the
+        # current one is mirrored in _ctx / _ctx_key / _lay / _host / _cfg_c
+        self._cache = collections.OrderedDict()
         self.contexts_built = 0               # apse_create calls so far (one per frame / image size change, weights, head)
         self._lay = None
         self._host = None
@@ -150,26 +155,28 @@ class TrackRCNN:
         """``preproc``: utils.preprocess.FramePreprocessor (camera matrix, distortion, gamma LUT) or None.  The context then runs
         undistort + gamma inside ``apse_preprocess_frames`` (include/apse_hip.h: apse_set_camera)."""
         self._camera = preproc
-        if self._ctx is not None:
-            self._push_camera()
+        for entry in self._cache.values():
+            self._push_camera(entry[0])
 
-    def _push_camera(self):
+    def _push_camera(self, ctx):
         lib = _lib.load()
         pc = self._camera
         if pc is None:
-            _lib.check(lib.apse_set_camera(self._ctx, None, None, 0, None, 0, 0), self._ctx, "apse_set_camera")
+            _lib.check(lib.apse_set_camera(ctx, None, None, 0, None, 0, 0), ctx, "apse_set_camera")
             return
-        _lib.check(lib.apse_set_camera(self._ctx, pc.mtx.ctypes.data_as(C.POINTER(C.c_double)), pc.dist.ctypes.data_as(C.POINTER(C.c_double)),
+        _lib.check(lib.apse_set_camera(ctx, pc.mtx.ctypes.data_as(C.POINTER(C.c_double)), pc.dist.ctypes.data_as(C.POINTER(C.c_double)),
                                        int(pc.dist.size), _lib.ptr(pc.lut_host), int(pc.undistort), int(pc.gamma_correct)),
-                   self._ctx, "apse_set_camera")
+                   ctx, "apse_set_camera")
 
     def _drop_ctx(self):
+        """Destroys every live context (the current one and the cached ones)."""
         self._input_tag = None
         self._running_tag = None
-        if self._ctx is not None:
-            _lib.load().apse_destroy(self._ctx)
-            self._ctx = None
-            self._ctx_key = None
+        self._ctx = None
+        self._ctx_key = None
+        while self._cache:
+            _, entry = self._cache.popitem(last=False)
+            _lib.load().apse_destroy(entry[0])
 
     def __del__(self):
         try:
@@ -182,7 +189,22 @@ class TrackRCNN:
         key = (tuple(frame_hw), tuple(image_hw))
         if self._ctx is not None and self._ctx_key == key:
             return
-        self._drop_ctx()
+        keep = int(self.cfg.APSE.get("CONTEXT_CACHE", 1))
+        if keep <= 1:
+            self._drop_ctx()
+        else:
+            self._input_tag = None
+            self._running_tag = None
+            if key in self._cache:
+                self._cache.move_to_end(key)
+                self._ctx, self._lay, self._host, self._cfg_c = self._cache[key]
+                self._ctx_key = key
+                return
+            self._ctx = None
+            self._ctx_key = None
+            while len(self._cache) >= keep:
+                _, entry = self._cache.popitem(last=False)          # the least recently used one
+                _lib.load().apse_destroy(entry[0])
         if self.device.type != "cuda" or not torch.cuda.is_available():
             raise _lib.ApseError("the apse_uav hot path needs a ROCm GPU (cfg.MODEL.DEVICE=%s): no CPU fallback" % self.device)
         if self._state is None:
@@ -254,10 +276,11 @@ class TrackRCNN:
             raise
         self._ctx, self._ctx_key, self._lay = ctx, key, lay
         self.contexts_built += 1
-        if self._camera is not None:
-            self._push_camera()
         self._host = torch.empty(lay.bytes, dtype=torch.uint8).pin_memory()
         self._cfg_c = c
+        self._cache[key] = (ctx, lay, self._host, c)
+        if self._camera is not None:
+            self._push_camera(ctx)
 
     # ---- stage calls (each enqueues on the current stream)
     def _call(self, fn, *args):
@@ -336,6 +359,13 @@ class TrackRCNN:
         and ``export_feature`` read afterwards."""
         B = self.preprocess_frames(frames)
         self._running_tag = None
+        self._call("apse_backbone", B, _lib.stream_ptr())
+        return B
+
+    def backbone_images(self, images, frame_hw):
+        """``backbone_frames`` from already-resized f32 CHW images [B, 3, h, w] of frames of size ``frame_hw`` (the training
+        loader's augmented images, utils/augment.py)."""
+        B = self.preprocess_images(images, frame_hw)
         self._call("apse_backbone", B, _lib.stream_ptr())
         return B
 

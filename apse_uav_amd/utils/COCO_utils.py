@@ -10,7 +10,8 @@ dcnn/scripts/train/finetune_segmentation.py leans on (dataset dictionaries, ``Po
 * ``mask_targets``: ``PolygonMasks.crop_and_resize`` (``rasterize_polygons_within_box``) at 28 x 28: the polygon transform on the
   host in float64, the rasterisation by ``apse_coco_poly_to_bits`` (equal to pycocotools ``frPyObjects`` + ``merge``).
 * ``MaskTrainLoader``: batches of ``IMS_PER_BATCH`` images -> RoI features of the ground-truth boxes from the frozen backbone
-  (test-size resize; optional seeded horizontal flip), classes and 28 x 28 targets.  Ground truths appear once: detectron2 appends
+  (test-size resize with an optional seeded horizontal flip; or, with ``augment`` / ``min_sizes``, the reference mapper's
+  multi-scale resize, flip and colour chain on the GPU: utils/augment.py), classes and 28 x 28 targets.  Ground truths appear once: detectron2 appends
   the ground truth to proposals that already are the ground truth, and an exact duplicate of every RoI leaves a mean loss and its
   gradient unchanged.
 """
@@ -150,15 +151,38 @@ class MaskTrainLoader:
     images, endlessly, in a seeded shuffled order.  ``model``: a TrackRCNN (FPN) with the frozen detector's weights.
     ``cache_features=True`` keeps every image's RoI features and targets on the device after the first visit (196 KB per object
     for the features); it is off when ``flip`` is on, where an image has two versions.  A batch with more than ``max_rois``
-    ground truths (APSE_MASK_TRAIN_MAX_N) keeps the first ``max_rois``."""
+    ground truths (APSE_MASK_TRAIN_MAX_N) keeps the first ``max_rois``.
 
-    def __init__(self, dicts, model, ims_per_batch=2, seed=0, flip=False, cache_features=False, max_rois=1024):
+    With ``augment`` false and ``min_sizes`` None an image is resized to the TEST size inside the context and ``flip`` mirrors it
+    on the host.  Otherwise the image takes the reference mapper's path on the device (utils/augment.py): ``resize_frames`` to a
+    short edge drawn from ``min_sizes`` (``sampling`` "choice", or "range" = any integer between two sizes; capped by ``max_size``;
+    None = the test size), then ``augment_images`` -- the flip when ``flip`` is on and drawn, and with ``augment`` the brightness /
+    saturation / contrast / lighting chain; a step that is off gets its identity parameter -- then ``preprocess_images``, the
+    backbone and the RoI features; boxes and polygons go through ``transform_annotations``.  The draws per image, in order: size
+    (only with several sizes), flip (only when on), then brightness, saturation, contrast, lighting.  ``cache_features`` is off
+    on that path.  Every image size has a context of its own, so the loader raises ``model.cfg.APSE.CONTEXT_CACHE`` to at least
+    ``len(min_sizes)`` (8 for "range") -- the model then keeps that many contexts alive instead of rebuilding one per image."""
+
+    def __init__(self, dicts, model, ims_per_batch=2, seed=0, flip=False, cache_features=False, max_rois=1024, augment=False,
+                 min_sizes=None, max_size=None, sampling="choice"):
         if getattr(model, "c4", False):
             raise NotImplementedError("mask-head training covers FPN models; C4 (Res5ROIHeads) shares res5 with the box branch")
         self.dicts = list(dicts)
         self.model = model
         self.ims_per_batch = int(ims_per_batch)
         self.flip = bool(flip)
+        self.augment = bool(augment)
+        self.device_path = self.augment or min_sizes is not None
+        self.min_sizes = tuple(int(v) for v in min_sizes) if min_sizes is not None else (int(model.cfg.INPUT.MIN_SIZE_TEST),)
+        self.max_size = int(max_size) if max_size is not None else int(model.cfg.INPUT.MAX_SIZE_TEST)
+        self.sampling = sampling
+        if self.device_path:
+            from . import augment as aug
+            aug.draw_size(np.random.default_rng(0), self.min_sizes, sampling)          # refuses a bad sampling / size list now
+            want = 8 if sampling == "range" else len(self.min_sizes)
+            if int(model.cfg.APSE.get("CONTEXT_CACHE", 1)) < want:
+                model.cfg.APSE.CONTEXT_CACHE = want
+            cache_features = False
         self.cache = {} if (cache_features and not flip) else None
         self.max_rois = int(max_rois)
         self.rng = np.random.default_rng(seed)
@@ -201,6 +225,28 @@ class MaskTrainLoader:
             self.cache[key] = item
         return item
 
+    def augmented_item(self, d, size, params):
+        """One image down the device path: resized to short edge ``size``, augmented with ``params`` (utils.augment.AugmentParams),
+        through the frozen backbone: (features, classes, targets) of its transformed ground-truth boxes."""
+        from PIL import Image
+        from . import augment as aug
+        model = self.model
+        frame = np.asarray(Image.open(d["file_name"]).convert("RGB"))[:, :, ::-1].copy()
+        H, W = frame.shape[:2]
+        if (H, W) != (d["height"], d["width"]):
+            raise ValueError("%s is %dx%d, the annotations say %dx%d" % (d["file_name"], H, W, d["height"], d["width"]))
+        boxes = np.array([[a["bbox"][0], a["bbox"][1], a["bbox"][0] + a["bbox"][2], a["bbox"][1] + a["bbox"][3]]
+                          for a in d["annotations"]], np.float64).reshape(-1, 4)
+        polys = [a["segmentation"] for a in d["annotations"]]
+        classes = torch.tensor([a["category_id"] for a in d["annotations"]], dtype=torch.int64)
+        ih, iw = resample.resize_shortest_edge(H, W, size, self.max_size)
+        boxes, polys = aug.transform_annotations(boxes, polys, (H, W), (ih, iw), params.flip)
+        resized = aug.resize_frames(torch.from_numpy(frame[None]).to(model.device), ih, iw)
+        _, chw, _ = aug.augment_images(resized, [params], want_u8=False)
+        model.backbone_images(chw, (H, W))
+        feats = model.mask_roi_features(boxes.astype(np.float32))
+        return feats, classes, mask_targets(polys, boxes, model.device)
+
     def __iter__(self):
         return self
 
@@ -210,6 +256,11 @@ class MaskTrainLoader:
             if not self._order:
                 self._order = [int(i) for i in self.rng.permutation(len(self.dicts))]
             d = self.dicts[self._order.pop(0)]
+            if self.device_path:
+                from . import augment as aug
+                size = aug.draw_size(self.rng, self.min_sizes, self.sampling)
+                items.append(self.augmented_item(d, size, aug.draw_params(self.rng, self.flip, self.augment)))
+                continue
             flipped = bool(self.flip and self.rng.random() < 0.5)
             items.append(self.image_item(d, flipped))
         feats = torch.cat([i[0] for i in items])[:self.max_rois]

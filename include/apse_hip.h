@@ -568,6 +568,26 @@ int apse_mask_loss_backward(const float* logits_dev, int K, const int* classes_d
 int apse_mask_predictor_backward(const float* d_dev, const float* a5_dev, const int* classes_dev, const float* w_pred_dev, int n, int K,
                                  float* g5_dev, float* dw_dev, float* db_dev, float* ws, size_t ws_bytes, void* stream);
 
+/* ---- Training augmentation (csrc/augment.hip): the transforms the reference's DatasetMapper applies after ResizeShortestEdge
+ * (dcnn/utils/UAV_utils.py:311-449) -- RandomFlip, RandomBrightness, RandomSaturation, RandomContrast, RandomLighting of
+ * detectron2 0.1.2 / fvcore, in that order, on resized u8 BGR images.  The rules, with the type of every operation (numpy 1.18
+ * value-based casting), are DESIGN.md "Training augmentation"; each blend ends in clip(x, 0, 255) and a truncating conversion to
+ * u8 that the next blend reads.  Stateless: no context, enqueues on `stream` only, no allocation, no synchronisation.  The only
+ * cross-thread sum is an integer sum, so results are bit-reproducible.
+ * brightness / saturation / contrast: the blend weights (1.0 = off); lighting_vec = EIGVEC . (lw * EIGVAL), f64, added to
+ * channels 0, 1, 2 unscaled as detectron2 does (0 = off).  With every step off the output is the input, mirrored when flip.
+ * src [B][H][W][3] u8; out_u8 [B][H][W][3] and / or out_chw [B][3][H][W] f32 (the layout apse_preprocess_images reads, the same
+ * integers as out_u8); either may be NULL, not both; out_u8 must not overlap src (src is read twice).  sums_dev [B] receives the
+ * exact sum S of the 3 H W values of each image after the saturation step (cleared on the stream first; the contrast step's mean
+ * is S / (3 H W), derived on the device).  params: host memory, B entries, read before the call returns.
+ * Limits (APSE_E_INVALID outside them, text in apse_last_error(NULL), nothing launched): 1 <= H <= APSE_MAX_FRAME_H,
+ * 1 <= W <= APSE_MAX_FRAME_W, 1 <= B <= APSE_AUGMENT_MAX_BATCH (the per-image parameters travel as one kernel argument);
+ * src, params and sums not NULL. */
+#define APSE_AUGMENT_MAX_BATCH 64
+typedef struct { int flip; double brightness, saturation, contrast; double lighting_vec[3]; } apse_augment_params;
+int apse_augment_u8(const uint8_t* src_dev, int B, int H, int W, const apse_augment_params* params_host,
+                    uint8_t* out_u8_dev, float* out_chw_dev, unsigned long long* sums_dev, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -83,7 +83,14 @@ def main(argv=None):
     ap.add_argument("--warmup-factor", type=float, default=0.001)
     ap.add_argument("--k-folds", type=int, default=1000)
     ap.add_argument("--seed", type=int, default=0)
-    ap.add_argument("--flip", action="store_true", help="random horizontal flip (the only augmentation)")
+    ap.add_argument("--flip", action="store_true", help="random horizontal flip")
+    ap.add_argument("--augment", action="store_true",
+                    help="the reference mapper's colour chain on the GPU: random brightness, saturation, contrast (0.9 .. 1.1 each) "
+                         "and lighting (0.2); the held-out images stay unaugmented")
+    ap.add_argument("--min-sizes", default="", metavar="S1,S2,...",
+                    help="multi-scale training: the short edge of every training image is drawn from these sizes, e.g. "
+                         "640,672,704,736,768,800 (default: the test size)")
+    ap.add_argument("--max-size", type=int, default=0, help="cap of the long edge with --min-sizes / --augment (default: the test one)")
     ap.add_argument("--cache-features", action="store_true")
     ap.add_argument("--stop-at", type=int, default=0, help="stop after this iteration's checkpoint (an interrupted run, for --resume)")
     ap.add_argument("--resume", action="store_true")
@@ -155,7 +162,9 @@ def main(argv=None):
 
     full = merge_full_mask_rcnn(detector, head.state_dict())
     pred = TrackPredictor(cfg, state_dict=full)
-    loader = COCO_utils.MaskTrainLoader(train_dicts, pred.model, args.ims_per_batch, args.seed, args.flip, args.cache_features)
+    min_sizes = tuple(int(v) for v in args.min_sizes.split(",")) if args.min_sizes else None
+    loader = COCO_utils.MaskTrainLoader(train_dicts, pred.model, args.ims_per_batch, args.seed, args.flip, args.cache_features,
+                                        augment=args.augment, min_sizes=min_sizes, max_size=args.max_size or None)
     if chk is not None and "loader" in chk:
         loader.load_state_dict(chk["loader"])
 
