@@ -17,7 +17,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 _TREE_LIB = os.path.join(_HERE, "libapse_hip.so")
 LIB_PATH = os.environ.get("APSE_HIP_LIB") or _TREE_LIB
 # entries that only tools/ use: a build from before they existed may still be loaded through APSE_HIP_LIB (load())
-TOOL_ENTRIES = ("apse_winograd_pack_filter", "apse_winograd_conv2d")
+TOOL_ENTRIES = ("apse_winograd_pack_filter", "apse_winograd_conv2d", "apse_lane_stats")
 
 APSE_OK = 0
 
@@ -42,6 +42,11 @@ class ConfigArch(Config):
     """apse_config with the appended ``arch`` field (0 FPN, 1 C4).  ``Config`` keeps the earlier layout: a caller that passes its
     size gets FPN."""
     _fields_ = [("arch", C.c_int)]
+
+
+class ConfigLane(ConfigArch):
+    """apse_config with the appended ``tail_lane`` field (0 default = on, < 0 off)."""
+    _fields_ = [("tail_lane", C.c_int)]
 
 
 class ResultsLayout(C.Structure):
@@ -112,6 +117,7 @@ def load():
         "apse_read_results": ([vp, vp, sz, vp], i),
         "apse_read_results_begin": ([vp, vp, sz, vp], i),
         "apse_read_results_end": ([vp, vp], i),
+        "apse_lane_stats": ([vp, C.POINTER(C.c_longlong * 4)], i),
         "apse_copy_mask_window": ([vp, i, i, i, i, i, vp, vp], i),
         "apse_copy_mask_windows": ([vp, i, vp, vp, vp, vp, vp], i),
         "apse_host_copy": ([vp, vp, sz, i], i),
@@ -199,7 +205,7 @@ def load():
 EXPORTS = ["apse_create", "apse_destroy", "apse_last_error", "apse_version", "apse_set_weight", "apse_finalize_weights",
            "apse_set_resize_tables", "apse_set_camera", "apse_preprocess_frames", "apse_preprocess_images", "apse_backbone", "apse_rpn", "apse_rpn_levels",
            "apse_box_head", "apse_set_detections", "apse_mask_tail", "apse_embed", "apse_forward", "apse_results_describe",
-           "apse_read_results", "apse_read_results_begin", "apse_read_results_end", "apse_copy_mask_window", "apse_copy_mask_windows", "apse_host_copy", "apse_feature_shape", "apse_export_feature", "apse_debug_tensor",
+           "apse_read_results", "apse_read_results_begin", "apse_read_results_end", "apse_lane_stats", "apse_copy_mask_window", "apse_copy_mask_windows", "apse_host_copy", "apse_feature_shape", "apse_export_feature", "apse_debug_tensor",
            "apse_flops", "apse_profile", "apse_profile_read", "apse_conv_packed_elems", "apse_conv_pack_weight", "apse_conv2d", "apse_winograd_pack_filter", "apse_winograd_conv2d", "apse_maxpool3x3s2",
            "apse_maxpool3x3s2_typed", "apse_roi_align", "apse_roi_align_typed", "apse_roi_pool", "apse_roi_features", "apse_nms_rank", "apse_mask_centroid_dense", "apse_mask_closest_dense",
            "apse_l2_normalize", "apse_sqdist", "apse_undistort_gamma", "apse_lab_tables_host", "apse_resize_normalize", "apse_replay_create", "apse_replay_destroy",

@@ -135,7 +135,9 @@ def get_cfg():
         "DATASETS": {"TRAIN": ("coco_2017_train",), "TEST": ("coco_2017_val",)},
         # build-specific knobs (not in the reference): storage dtype and batch of the HIP path
         # CONTEXT_CACHE: live contexts TrackRCNN keeps, one per (frame size, image size); 1 = rebuild at every size change
-        "APSE": {"DTYPE": "f32", "MAX_BATCH": 1, "FUSED_PREPROC": True, "STORAGE16": True, "CONTEXT_CACHE": 1},
+        # TAIL_LANE: a forward's selection / heads / results copy on the context's second stream, beside the next frame's trunk
+        # (apse_config.tail_lane; the environment variable APSE_TAIL_LANE=0 switches it off for every context)
+        "APSE": {"DTYPE": "f32", "MAX_BATCH": 1, "FUSED_PREPROC": True, "STORAGE16": True, "CONTEXT_CACHE": 1, "TAIL_LANE": True},
     })
 
 

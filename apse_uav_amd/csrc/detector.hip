@@ -1,8 +1,9 @@
 // libapse_hip.so context: run_plan (the per-forward launch sequence) and the context's C ABI of include/apse_hip.h.
 // The plan it runs is built in plan.hip; the stateless operators of the ABI are in ops.hip (detector_ctx.h says which file
 // holds what).  Host-side C++ only orchestrates; all arithmetic is in the HIP kernels of this directory.
-// One context per device/process rank; the caller's stream carries every launch (no hidden syncs
-// except apse_read_results).
+// One context per device/process rank.  The caller's stream carries every launch, with one exception: a forward enqueued
+// while a results copy is pending (a caller that runs ahead) keeps resize, trunk, FPN and the RPN convolutions there and sends
+// the rest and its results copy to the context's tail lane (below).  No hidden syncs except apse_read_results.
 #include "detector_ctx.h"
 
 #include <math.h>
@@ -33,12 +34,118 @@ static int take_event_pair(apse_ctx* c, hipStream_t s) {
     return e0;
 }
 
+// ---- the tail lane (detector_ctx.h)
+// The lane carries a forward only when the caller runs ahead: the forward was enqueued while a results copy was pending
+// (between apse_read_results_begin and _end), i.e. there is a frame beside whose tail the next trunk can run.  A caller that
+// reads each forward before enqueuing the next has nothing to overlap, and several contexts in flight on streams of their own
+// already fill the idle capacity: both keep every launch on the caller's stream (measured: DESIGN.md section 6).
+static bool lane_active(const apse_ctx* c) { return c->lane_on && !c->prof_on && c->lane_armed; }
+
+// The lane's stream and events, all or nothing: after a failure the context has no lane (c->lane stays null).
+static void lane_teardown(apse_ctx* c) {
+    hipEvent_t* evs[5] = {&c->fork_ev, &c->follow_ev, &c->tail_ev, &c->bits_ev[0], &c->bits_ev[1]};
+    for (hipEvent_t* e : evs) { if (*e) hipEventDestroy(*e); *e = nullptr; }
+    if (c->lane) hipStreamDestroy(c->lane);
+    c->lane = nullptr;
+    c->fork_pending = c->follow_pending = c->tail_live = c->bits_live[0] = c->bits_live[1] = false;
+    c->caller_dirty = true;          // a later lane starts behind whatever the caller's stream holds
+}
+
+static int lane_create(apse_ctx* c) {
+    if (c->lane) return APSE_OK;
+    hipEvent_t* evs[5] = {&c->fork_ev, &c->follow_ev, &c->tail_ev, &c->bits_ev[0], &c->bits_ev[1]};
+    hipError_t e = hipSuccess;
+    for (hipEvent_t* ev : evs) if (e == hipSuccess) e = hipEventCreateWithFlags(ev, hipEventDisableTiming);
+    // non-blocking: the legacy default stream (bench.py's headline loop) would serialise against a blocking one
+    if (e == hipSuccess) e = hipStreamCreateWithFlags(&c->lane, hipStreamNonBlocking);
+    if (e != hipSuccess) {
+        lane_teardown(c);
+        return fail(c, APSE_E_HIP, std::string("tail lane: ") + hipGetErrorString(e));
+    }
+    return APSE_OK;
+}
+
+// true when everything recorded under `ev` has finished.  A not-ready answer is no error: it alone is taken off the runtime's
+// last-error slot (which PyTorch reads after its own launches); any other error stays there.
+static bool event_done(hipEvent_t ev) {
+    if (hipEventQuery(ev) == hipSuccess) return true;
+    if (hipPeekAtLastError() == hipErrorNotReady) (void)hipGetLastError();
+    return false;
+}
+
+// The stream of one ABI entry's lane-owned launches: the lane, made to wait for what the caller's stream holds for it, or the
+// caller's stream when the lane is off.  Leaving the scope records tail_ev behind whatever the entry did enqueue, also on an
+// error return, so that no later wait refers to an event that was never recorded.
+struct LaneScope {
+    apse_ctx* c = nullptr; hipStream_t s = nullptr; bool on = false;
+    int bits_k = -1;                 // apse_mask_tail: the bit-plane set this entry writes; its event is recorded with tail_ev
+    int begin(apse_ctx* c_, hipStream_t caller) {
+        c = c_; s = caller;
+        if (!lane_active(c)) return APSE_OK;
+        int rc = lane_create(c);
+        if (rc) return rc;
+        if (c->caller_dirty) {
+            HIPCHK(c, hipEventRecord(c->fork_ev, caller));
+            c->caller_dirty = false; c->fork_pending = true;
+        }
+        if (c->fork_pending) { HIPCHK(c, hipStreamWaitEvent(c->lane, c->fork_ev, 0)); c->fork_pending = false; }
+        if (c->follow_pending) { HIPCHK(c, hipStreamWaitEvent(c->lane, c->follow_ev, 0)); c->follow_pending = false; }
+        s = c->lane; on = true;
+        return APSE_OK;
+    }
+    ~LaneScope() {
+        if (!on) return;
+        if (bits_k >= 0 && hipEventRecord(c->bits_ev[bits_k], c->lane) == hipSuccess) c->bits_live[bits_k] = true;
+        if (hipEventRecord(c->tail_ev, c->lane) == hipSuccess) c->tail_live = true;
+    }
+};
+
+// Entries outside the forward: the caller's stream waits for the lane (for `ev`: tail_ev, or the event of one bit-plane set).
+static int lane_join(apse_ctx* c, hipStream_t s, hipEvent_t ev, bool live) {
+    if (!c->lane || !live || event_done(ev)) return APSE_OK;
+    HIPCHK(c, hipStreamWaitEvent(s, ev, 0));
+    ++c->lane_stats[1];
+    return APSE_OK;
+}
+static int lane_join(apse_ctx* c, hipStream_t s) { return lane_join(c, s, c->tail_ev, c->tail_live); }
+// ... and when such an entry has put work that reads or writes lane-owned buffers on the caller's stream, the lane's next
+// launch follows it
+static int lane_follow(apse_ctx* c, hipStream_t s) {
+    if (!c->lane) return APSE_OK;
+    HIPCHK(c, hipEventRecord(c->follow_ev, s));
+    c->follow_pending = true;
+    return APSE_OK;
+}
+// the same for an entry without a stream argument: the host waits until the lane is empty
+static int lane_drain(apse_ctx* c) {
+    if (!c->lane) return APSE_OK;
+    if (c->tail_live && !event_done(c->tail_ev)) ++c->lane_stats[1];
+    HIPCHK(c, hipStreamSynchronize(c->lane));
+    ++c->lane_stats[3];
+    return APSE_OK;
+}
+
+// lane_stats[0]: one per forward (a forward starts with apse_backbone) whose tail went to the lane, however many of
+// apse_rpn_levels / apse_set_detections it calls
+static void count_lane_forward(apse_ctx* c, bool on) {
+    if (!on || c->fwd_counted) return;
+    ++c->lane_stats[0];
+    c->fwd_counted = true;
+}
+
 static int run_plan(apse_ctx* c, std::vector<Step>& plan, int batch, hipStream_t s) {
     int* total_dev = reinterpret_cast<int*>(c->res + c->lay.total);
     int* propcnt_dev = reinterpret_cast<int*>(c->res + c->lay.prop_count);
+    float* ws = (c->lane && s == c->lane) ? c->ws_lane : c->ws;
     for (size_t si = 0; si < plan.size(); ++si) {
         Step& st = plan[si];
         int rc = APSE_OK;
+        if (&plan == &c->backbone && (int)si == c->fpn_step && c->lane && c->tail_live && !event_done(c->tail_ev)) {
+            // the FPN and the RPN convolutions overwrite what the previous forward's heads read (p2..p5, rpn_t_all, the RPN
+            // logits / deltas): wait for its tail.  stem..res5 write none of these; this also bounds the run-ahead to one frame.
+            ++c->lane_stats[2];
+            HIPCHK(c, hipStreamWaitEvent(s, c->tail_ev, 0));
+        }
         if (st.kind == S_CONV) {
             ConvParams p = st.c.p;
             // next convolution of this plan: its filters are prefetched by this launch
@@ -53,7 +160,7 @@ static int run_plan(apse_ctx* c, std::vector<Step>& plan, int batch, hipStream_t
                 }
             p.B = st.c.fixed_items > 0 ? st.c.fixed_items : batch * st.c.b_mult;
             p.M = p.B * p.OH * p.OW;
-            p.ws = c->ws;
+            p.ws = ws;
             // In-launch split-K reduction (last arriver) measured SLOWER here than the separate reduce kernel
             // (f32 132 -> 111 FPS): 64-512 KB of slabs per tile and an agent-scope release (L2 write-back) per
             // block; it stays available through apse_conv_desc.fuse_reduce for small slabs.
@@ -137,8 +244,9 @@ const char* apse_version(void) { return "apse_hip 0.6 (gfx950, f32 / bf16 / f16 
 int apse_create(const apse_config* cfg, apse_ctx** out) {
     if (!cfg || !out) return fail(nullptr, APSE_E_INVALID, "null argument");
     // callers built against the header before `arch` was appended pass the shorter size: FPN
-    const int old_size = (int)offsetof(apse_config, arch);
-    if (cfg->struct_size != (int)sizeof(apse_config) && cfg->struct_size != old_size)
+    // ... and before `tail_lane`: the default (lane on)
+    const int old_size = (int)offsetof(apse_config, arch), arch_size = (int)offsetof(apse_config, tail_lane);
+    if (cfg->struct_size != (int)sizeof(apse_config) && cfg->struct_size != old_size && cfg->struct_size != arch_size)
         return fail(nullptr, APSE_E_INVALID, "apse_config size mismatch");
     apse_config cf;
     memset(&cf, 0, sizeof cf);
@@ -193,6 +301,11 @@ int apse_create(const apse_config* cfg, apse_ctx** out) {
         const char* e = getenv("APSE_F32_WINOGRAD");
         c->f32_winograd = !(e && atoi(e) == 0);
     }
+    {
+        // the tail lane: FPN only (the C4 heads read res4, which the next trunk writes early)
+        const char* e = getenv("APSE_TAIL_LANE");
+        c->lane_on = !c->c4 && cfg->tail_lane >= 0 && !(e && atoi(e) == 0);
+    }
     *out = c;
     return APSE_OK;
 }
@@ -200,6 +313,10 @@ int apse_create(const apse_config* cfg, apse_ctx** out) {
 void apse_destroy(apse_ctx* c) {
     if (!c) return;
     hipSetDevice(c->cfg.device);
+    if (c->lane) {
+        hipStreamSynchronize(c->lane);              // pending tail work reads the buffers freed below
+        lane_teardown(c);
+    }
     for (void* p : c->allocs) hipFree(p);
     if (c->rf_mask) hipFree(c->rf_mask);
     if (c->mrf_idx) hipFree(c->mrf_idx);
@@ -280,6 +397,10 @@ int apse_preprocess_images(apse_ctx* c, const float* images, int batch, void* st
 
 int apse_backbone(apse_ctx* c, int batch, void* stream) {
     NEED_READY(c, batch);
+    c->caller_dirty = true;                         // the lane's next launch follows the maps written here
+    c->lane_armed = c->read_pending != nullptr;     // this forward runs ahead of a read: its tail goes to the lane
+    c->fwd_since_read = true;
+    c->fwd_counted = false;
     return run_plan(c, c->backbone, batch, (hipStream_t)stream);
 }
 
@@ -292,8 +413,18 @@ int apse_rpn_levels(apse_ctx* c, int batch, int level_mask, void* stream) {
     hipStream_t s = (hipStream_t)stream;
     const apse_config& g = c->cfg;
     if (c->c4 && level_mask != 31) return fail(c, APSE_E_INVALID, "C4 (arch 1) has one RPN level: level_mask must be 31");
-    int rc = run_plan(c, c->rpnhead, batch, s);
+    int rc;
+    // without an apse_backbone in front (whose first FPN step has joined the lane) the convolutions below would rewrite the RPN
+    // maps while the lane's selection of the previous call may still read them: join here
+    if (!c->caller_dirty && (rc = lane_join(c, s))) return rc;
+    rc = run_plan(c, c->rpnhead, batch, s);
     if (rc) return rc;
+    // the fork: selection and everything behind it go to the tail lane, behind the RPN convolutions just enqueued
+    c->caller_dirty = true;
+    LaneScope ln;
+    if ((rc = ln.begin(c, s))) return rc;
+    count_lane_forward(c, ln.on);
+    s = ln.s;
     if (c->c4) {
         int* propcnt = reinterpret_cast<int*>(c->res + c->lay.prop_count);
         rc = apse_k_c4_rpn(&c->c4r, g.rpn_pre_topk, g.rpn_post_topk, (float)g.image_h, (float)g.image_w, (float)log(1000.0 / 16.0),
@@ -335,11 +466,13 @@ static int pack_from_dets(apse_ctx* c, int batch, hipStream_t s) {
 
 int apse_box_head(apse_ctx* c, int batch, void* stream) {
     NEED_READY(c, batch);
-    hipStream_t s = (hipStream_t)stream;
+    LaneScope ln;
+    int rc = ln.begin(c, (hipStream_t)stream);
+    if (rc) return rc;
+    hipStream_t s = ln.s;
     const apse_config& g = c->cfg;
     int* propcnt = reinterpret_cast<int*>(c->res + c->lay.prop_count);
     const int P = g.rpn_post_topk, K = g.num_classes;
-    int rc;
     if (c->c4) {
         const Tens& f = c->t["res4"];
         rc = apse_k_roi_align_c4(f.p, f.H, f.W, f.C, 1.0f / 16.0f, c->props, nullptr, propcnt, nullptr, P, batch * P, 14,
@@ -392,7 +525,11 @@ int apse_box_head(apse_ctx* c, int batch, void* stream) {
 int apse_set_detections(apse_ctx* c, const float* boxes, const int* classes, const float* scores, const int* counts, int batch,
                         void* stream) {
     NEED_READY(c, batch);
-    hipStream_t s = (hipStream_t)stream;
+    LaneScope ln;
+    int rc = ln.begin(c, (hipStream_t)stream);
+    if (rc) return rc;
+    count_lane_forward(c, ln.on);
+    hipStream_t s = ln.s;
     const apse_config& g = c->cfg;
     const int KD = g.dets_per_image, K = g.num_classes;
     const size_t nb = (size_t)g.max_batch * KD;
@@ -428,18 +565,20 @@ int apse_set_detections(apse_ctx* c, const float* boxes, const int* classes, con
     HIPCHK(c, hipMemcpyAsync(c->det_entry, de, nbb * 4, hipMemcpyHostToDevice, s));
     HIPCHK(c, hipMemcpyAsync(c->det_cnt, dc, (size_t)batch * 4, hipMemcpyHostToDevice, s));
     HIPCHK(c, hipEventRecord(c->given_ev[slot], s));
-    int rc = pack_from_dets(c, batch, s);
+    rc = pack_from_dets(c, batch, s);
     return rc ? fail(c, rc, "pack launch failed") : APSE_OK;
 }
 
 int apse_mask_tail(apse_ctx* c, int batch, void* stream) {
     NEED_READY(c, batch);
-    hipStream_t s = (hipStream_t)stream;
+    LaneScope ln;
+    int rc = ln.begin(c, (hipStream_t)stream);
+    if (rc) return rc;
+    hipStream_t s = ln.s;
     const apse_config& g = c->cfg;
     uint8_t* r = c->res;
     const int NM = batch * g.dets_per_image;
     int* total = (int*)(r + c->lay.total);
-    int rc;
     if (c->c4) {
         const Tens& f = c->t["res4"];
         rc = apse_k_roi_align_c4(f.p, f.H, f.W, f.C, 1.0f / 16.0f, (float*)(r + c->lay.box_resized), (int*)(r + c->lay.img), nullptr,
@@ -465,6 +604,7 @@ int apse_mask_tail(apse_ctx* c, int batch, void* stream) {
     if (c->sums_dirty) HIPCHK(c, hipMemsetAsync(c->sums, 0, (size_t)g.max_batch * g.dets_per_image * 3 * sizeof(unsigned long long), s));
     c->sums_dirty = true;
     c->bits_cur ^= 1;
+    ln.bits_k = c->bits_cur;               // recorded when the entry leaves, also on an error below
     if (!c->read_pending) c->bits_read = c->bits_cur;
     uint64_t* bits = c->bits2[c->bits_cur];
     p.bits = bits; p.sums = c->sums;
@@ -479,12 +619,14 @@ int apse_mask_tail(apse_ctx* c, int batch, void* stream) {
 
 int apse_embed(apse_ctx* c, int batch, void* stream) {
     NEED_READY(c, batch);
-    hipStream_t s = (hipStream_t)stream;
+    LaneScope ln;
+    int rc = ln.begin(c, (hipStream_t)stream);
+    if (rc) return rc;
+    hipStream_t s = ln.s;
     const apse_config& g = c->cfg;
     uint8_t* r = c->res;
     const int NM = batch * g.dets_per_image;
     int* total = (int*)(r + c->lay.total);
-    int rc;
     if (c->c4) {
         const Tens& f = c->t["res4"];
         rc = apse_k_roi_pool_c4(f.p, f.H, f.W, f.C, (float*)(r + c->lay.box), (int*)(r + c->lay.img), total, NM, g.assoc_roi,
@@ -530,9 +672,14 @@ int apse_read_results_begin(apse_ctx* c, void* host_dst, size_t bytes, void* str
     if (!c || !c->finalized) return fail(c, APSE_E_STATE, "not finalized");
     if (bytes < c->lay.bytes) return fail(c, APSE_E_INVALID, "results buffer too small");
     if (!c->read_ev) HIPCHK(c, hipEventCreateWithFlags(&c->read_ev, hipEventDisableTiming));
-    HIPCHK(c, hipMemcpyAsync(host_dst, c->res, c->lay.bytes, hipMemcpyDeviceToHost, (hipStream_t)stream));
-    HIPCHK(c, hipEventRecord(c->read_ev, (hipStream_t)stream));
+    // on the lane, behind the tail that fills the block: the next forward's trunk, enqueued on the caller's stream, is not waited for
+    LaneScope ln;
+    int rc = ln.begin(c, (hipStream_t)stream);
+    if (rc) return rc;
+    HIPCHK(c, hipMemcpyAsync(host_dst, c->res, c->lay.bytes, hipMemcpyDeviceToHost, ln.s));
+    HIPCHK(c, hipEventRecord(c->read_ev, ln.s));
     c->read_pending = host_dst;
+    c->fwd_since_read = false;
     c->bits_read = c->bits_cur;                  // the mask windows that belong to these results
     if (c->prof_on) {                            // this forward's event pairs go to _end; the next forward records into the other half
         c->pending_read.swap(c->pending);
@@ -549,6 +696,15 @@ int apse_read_results_end(apse_ctx* c, void* host_dst) {
     if (!c->read_pending || c->read_pending != host_dst) return fail(c, APSE_E_STATE, "apse_read_results_end without a matching _begin");
     HIPCHK(c, hipEventSynchronize(c->read_ev));
     c->read_pending = nullptr;
+    if (c->lane && !c->fwd_since_read && !c->prof_on) {
+        // The caller has stopped running ahead (no forward was enqueued behind this read): give the lane's stream back.  An idle
+        // extra stream is not free for the REST of the process -- the runtime spreads streams over four hardware queues, and one
+        // idle non-blocking stream, created in front of them, cost four pipelined contexts 3 % (measured on the parent library
+        // too: DESIGN.md section 6).  The next forward that runs ahead creates it again.
+        HIPCHK(c, hipStreamSynchronize(c->lane));
+        lane_teardown(c);
+        ++c->lane_stats[3];
+    }
     c->hint_total = *reinterpret_cast<const int*>(reinterpret_cast<const uint8_t*>(host_dst) + c->lay.total);
     {
         // closest-point table: the device leaves (f32 distance bits << 32 | row-major pixel index) keys, all ones = no point;
@@ -596,6 +752,11 @@ int apse_read_results(apse_ctx* c, void* host_dst, size_t bytes, void* stream) {
 
 int apse_profile(apse_ctx* c, int enable) {
     if (!c) return APSE_E_INVALID;
+    // the event pairs time single kernels of ONE stream: while profiling is on the lane is off.  Either switch first empties the
+    // lane, and the first lane launch after profiling follows what the caller's stream was given meanwhile.
+    int rc = lane_drain(c);
+    if (rc) return rc;
+    c->caller_dirty = true;
     if (enable && c->ev_pool.empty()) {
         c->ev_pool.resize(2 * APSE_EV_HALF);
         for (auto& e : c->ev_pool) if (hipEventCreate(&e) != hipSuccess) return fail(c, APSE_E_HIP, "hipEventCreate");
@@ -605,6 +766,12 @@ int apse_profile(apse_ctx* c, int enable) {
     c->pending_read.clear();
     c->cal_read = -1;
     c->ev_used = 0;
+    return APSE_OK;
+}
+
+int apse_lane_stats(apse_ctx* c, long long* out4) {
+    if (!c || !out4) return APSE_E_INVALID;
+    memcpy(out4, c->lane_stats, sizeof(c->lane_stats));
     return APSE_OK;
 }
 
@@ -622,9 +789,12 @@ int apse_copy_mask_window(apse_ctx* c, int det, int x0, int y0, int x1, int y1, 
         return fail(c, APSE_E_INVALID, "bad mask window");
     const int w0 = x0 >> 6, w1 = (x1 + 63) >> 6;
     const uint64_t* src = c->bits2[c->bits_read] + ((size_t)det * g.frame_h + y0) * c->wpr + w0;
+    // joins the mask tail that wrote this set only: the next forward's tail (the other set) may still be running
+    int rc = lane_join(c, (hipStream_t)stream, c->bits_ev[c->bits_read], c->bits_live[c->bits_read]);
+    if (rc) return rc;
     HIPCHK(c, hipMemcpy2DAsync(dst, (size_t)(w1 - w0) * 8, src, (size_t)c->wpr * 8, (size_t)(w1 - w0) * 8, (size_t)(y1 - y0),
                                hipMemcpyDeviceToDevice, (hipStream_t)stream));
-    return APSE_OK;
+    return lane_follow(c, (hipStream_t)stream);
 }
 
 int apse_copy_mask_windows(apse_ctx* c, int n, const int* dets, const int* rects, uint64_t* dst, const long long* dst_off, void* stream) {
@@ -641,8 +811,11 @@ int apse_copy_mask_windows(apse_ctx* c, int n, const int* dets, const int* rects
         src[k] = ((long long)dets[k] * g.frame_h + y0) * c->wpr + w0;
         nw[k] = w1 - w0; rows[k] = y1 - y0;
     }
-    int rc = apse_k_copy_mask_windows(c->bits2[c->bits_read], dst, n, src, dst_off, nw, rows, c->wpr, (hipStream_t)stream);
-    return rc ? fail(c, rc, "mask windows launch failed") : APSE_OK;
+    int rc = lane_join(c, (hipStream_t)stream, c->bits_ev[c->bits_read], c->bits_live[c->bits_read]);
+    if (rc) return rc;
+    rc = apse_k_copy_mask_windows(c->bits2[c->bits_read], dst, n, src, dst_off, nw, rows, c->wpr, (hipStream_t)stream);
+    if (rc) return fail(c, rc, "mask windows launch failed");
+    return lane_follow(c, (hipStream_t)stream);
 }
 
 int apse_feature_shape(apse_ctx* c, const char* name, int* chw3) {
@@ -658,8 +831,11 @@ int apse_export_feature(apse_ctx* c, const char* name, float* dst, int batch, vo
     auto it = c->t.find(name);
     if (it == c->t.end()) return fail(c, APSE_E_MISSING, std::string("no tensor ") + name);
     const Tens& t = it->second;
-    int rc = apse_k_nhwc_to_nchw(t.p, dst, batch, t.H * t.W, t.C, t.st, (hipStream_t)stream);
-    return rc ? fail(c, rc, "export launch failed") : APSE_OK;
+    int rc = lane_join(c, (hipStream_t)stream);
+    if (rc) return rc;
+    rc = apse_k_nhwc_to_nchw(t.p, dst, batch, t.H * t.W, t.C, t.st, (hipStream_t)stream);
+    if (rc) return fail(c, rc, "export launch failed");
+    return lane_follow(c, (hipStream_t)stream);
 }
 
 int apse_roi_features(apse_ctx* c, int image, const float* rois, const uint8_t* masks, int n, int roi_size, float* out, void* stream) {
@@ -673,7 +849,8 @@ int apse_roi_features(apse_ctx* c, int image, const float* rois, const uint8_t* 
     const Tens& p2 = c->t["p2"];
     // spatial_scale = feature width / original width (roi_features_generator.py:105; the padded width, like rcnn_tracker.py:165)
     const float scale = (float)p2.W / (float)g.frame_w;
-    int rc;
+    int rc = lane_join(c, s);          // reads p2 only (written on the caller's stream): nothing for the lane to follow
+    if (rc) return rc;
     if (!masks) {
         rc = apse_k_roi_pool(p2.p, p2.st, p2.H, p2.W, rois, nullptr, nullptr, n, roi_size, scale, out, image, 1, s);
         return rc ? fail(c, rc, "roi_pool launch failed") : APSE_OK;
@@ -712,7 +889,9 @@ int apse_mask_roi_features(apse_ctx* c, int image, const float* rois, int n, flo
     FpnMaps fm = c->fm;
     for (int l = 0; l < 4; ++l)
         fm.p[l] = reinterpret_cast<const char*>(fm.p[l]) + (size_t)image * fm.H[l] * fm.W[l] * 256 * (fm.st ? 2 : 4);
-    int rc = apse_k_mask_roi_index(c->mrf_idx, n, s);
+    int rc = lane_join(c, s);          // reads p2..p5 only (written on the caller's stream): nothing for the lane to follow
+    if (rc) return rc;
+    rc = apse_k_mask_roi_index(c->mrf_idx, n, s);
     if (rc) return fail(c, rc, "mask_roi_features index launch failed");
     rc = apse_k_roi_align(&fm, rois, c->mrf_idx, nullptr, c->mrf_idx + n, 0, n, 14, out, 0, s);
     return rc ? fail(c, rc, "roi_align(14) launch failed") : APSE_OK;
@@ -751,8 +930,10 @@ int apse_debug_tensor(apse_ctx* c, const char* name, void* dst, size_t max_bytes
     if (bytes) *bytes = n;
     if (!dst) return APSE_OK;
     if (n > max_bytes) return fail(c, APSE_E_INVALID, "debug buffer too small for " + nm);
+    int rc = lane_join(c, (hipStream_t)stream);
+    if (rc) return rc;
     HIPCHK(c, hipMemcpyAsync(dst, src, n, hipMemcpyDeviceToDevice, (hipStream_t)stream));
-    return APSE_OK;
+    return lane_follow(c, (hipStream_t)stream);
 }
 
 double apse_flops(apse_ctx* c, int batch, double proposals, double detections) {
@@ -769,6 +950,7 @@ double apse_flops(apse_ctx* c, int batch, double proposals, double detections) {
 
 int apse_set_camera(apse_ctx* c, const double* m, const double* dist, int ndist, const uint8_t* lut_host, int do_undistort, int do_gamma) {
     if (!c) return APSE_E_INVALID;
+    if (lane_drain(c)) return APSE_E_HIP;
     if (!do_undistort && !do_gamma) { c->cam_on = false; return APSE_OK; }
     if (do_gamma && !lut_host) return fail(c, APSE_E_INVALID, "gamma needs a 256-entry LUT");
     UndistortParams p;

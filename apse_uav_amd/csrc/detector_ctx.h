@@ -84,6 +84,28 @@ struct apse_ctx {
     // the event pool has two halves: apse_read_results_begin hands the half (and the pending list) of the forward it reads to _end
     // and switches recording to the other half, so a forward enqueued between the two halves of a read keeps its own events
     int ev_base = 0, cal_read = -1; std::vector<Pending> pending_read;
+    // The tail lane: a second stream of the context.  Of a forward that runs ahead (enqueued while a results
+    // copy is pending: lane_armed) the proposal selection, box head, mask tail, embedding and results copy are enqueued on it; the
+    // caller's stream keeps resize, trunk, FPN and the RPN convolutions, so the next frame's stem..res5 run beside this frame's
+    // latency-bound tail.  Every other forward is on the caller's stream alone.  Off altogether: APSE_TAIL_LANE=0 (read once, at
+    // apse_create), apse_config.tail_lane < 0, C4, and while profiling (prof_on) -- then every launch is on the caller's stream.
+    //   fork_ev    recorded on the caller's stream behind work the lane's next launch must follow (the RPN convolutions)
+    //   follow_ev  the same behind an entry that read or wrote lane-owned buffers on the caller's stream (apse_debug_tensor ...)
+    //   tail_ev    recorded on the lane behind the last launch of every lane entry: the first FPN step of the next apse_backbone
+    //              and every joining entry wait for it
+    //   bits_ev[k] behind the mask tail that wrote bit-plane set k (apse_copy_mask_window(s) wait for their set only)
+    bool lane_on = true;
+    bool lane_armed = false;         // set per forward by apse_backbone: it was enqueued while a results copy was pending
+    bool fwd_since_read = false;     // a forward was enqueued since the last apse_read_results_begin (the caller is running ahead)
+    hipStream_t lane = nullptr;
+    hipEvent_t fork_ev = nullptr, follow_ev = nullptr, tail_ev = nullptr, bits_ev[2] = {nullptr, nullptr};
+    bool caller_dirty = false;       // the caller's stream holds library work that fork_ev does not cover yet
+    bool fork_pending = false, follow_pending = false;      // recorded, and the lane has not been made to wait for it yet
+    bool tail_live = false, bits_live[2] = {false, false};  // the event has been recorded at least once
+    float* ws_lane = nullptr;        // split-K workspace of the head plans when they run on the lane (c->ws stays the trunk's)
+    int fpn_step = -1;               // index in `backbone` of the first FPN step (the first lateral): where the trunk joins the lane
+    long long lane_stats[4] = {0, 0, 0, 0};      // apse_lane_stats
+    bool fwd_counted = false;        // this forward (since the last apse_backbone) is already in lane_stats[0]
     // stateless-op scratch
     uint64_t* op_bits = nullptr; unsigned long long* op_sums = nullptr; size_t op_bits_words = 0;
     // C4 (cfg.arch 1, Res5ROIHeads): the RPN on res4, the res5 stage on the box ROIs (c4_res5box, then the 7x7 mean and the

@@ -362,6 +362,22 @@ static int finish_plan(apse_ctx* c, int feat_C) {
         c->ws = dalloc<float>(c, c->ws_floats, false);
         if (!c->ws) return fail(c, APSE_E_NOMEM, "split-K workspace alloc");
     }
+    if (c->lane_on) {
+        // the head plans run on the tail lane beside the next frame's trunk, whose res5 reduces use c->ws: a workspace of their own,
+        // sized like c->ws (add_conv) from the split-K layers of the three head plans only (run_plan selects it by stream)
+        size_t need = 0;
+        for (const std::vector<Step>* pl : {&c->boxhead, &c->maskhead, &c->embedfc})
+            for (const Step& st : *pl) {
+                const ConvParams& q = st.c.p;
+                if (st.kind != S_CONV || q.splitk <= 1) continue;
+                const size_t n = (size_t)q.splitk * B * st.c.b_mult * q.OH * q.OW * q.Cout;
+                if (n > need) need = n;
+            }
+        if (need) {
+            c->ws_lane = dalloc<float>(c, need, false);
+            if (!c->ws_lane) return fail(c, APSE_E_NOMEM, "tail lane split-K workspace alloc");
+        }
+    }
     c->tile_cnt = dalloc<int>(c, 65536);        // zero-initialised; every launch leaves it zero
     c->rs_pitch = (g.image_w * 3 + 15) & ~15;            // row pitch of the intermediate image: dword loads in the vertical pass
     c->rs_tmp = dalloc<uint8_t>(c, (size_t)B * g.frame_h * c->rs_pitch, false);
@@ -507,6 +523,9 @@ int build_plan(apse_ctx* c) {
         }
     }
     // ---- FPN (top-down): inner5 = lateral5(res5); p5 = output5(inner5); inner_l = lateral_l(res_l) + up(inner_{l+1})
+    // The first lateral is where a trunk joins the tail lane: from here on the plan overwrites maps that the previous forward's
+    // heads read (p2..p5, then the RPN buffers); nothing in front of it does.
+    c->fpn_step = (int)c->backbone.size();
     Tens inner, pl[5];
     for (int lvl = 5; lvl >= 2; --lvl) {
         char ln[64], on[64], rn[16], in_name[16], pn[8];

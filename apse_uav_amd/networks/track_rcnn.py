@@ -129,6 +129,7 @@ class TrackRCNN:
         self._lay = None
         self._host = None
         self._camera = None                   # FramePreprocessor: undistort + gamma fused into preprocess_frames
+        self.tail_lane = None                 # None: cfg.APSE.TAIL_LANE; False: contexts without the tail lane (apse_config.tail_lane)
         self._input_tag = None                # frames (objects) the network input was pre-staged with, or None
         self._running_tag = None              # (frames, rpn_levels) whose forward is already enqueued and not yet read, or None
         self.last_results = None
@@ -248,6 +249,14 @@ class TrackRCNN:
             c.assoc_scale = c4_res4_size(c.image_h, c.image_w)[1] / float(c.frame_w)
         c.compute_dtype = {"f32": 0, "bf16": 1, "f16": 2, "fp16": 2}[str(cfg.APSE.DTYPE)]
         c.storage16 = int(bool(cfg.APSE.get("STORAGE16", True))) if c.compute_dtype else 0
+        lane = bool(cfg.APSE.get("TAIL_LANE", True)) if self.tail_lane is None else bool(self.tail_lane)
+        if not lane and hasattr(lib, "apse_lane_stats"):
+            # the default layout stays the one without the field, and so does a lane-off context on a build from before the lane
+            # (loaded through APSE_HIP_LIB for an A/B run: it has no apse_lane_stats, no lane, and refuses the longer layout)
+            c, short = _lib.ConfigLane(), c
+            C.memmove(C.byref(c), C.byref(short), C.sizeof(_lib.ConfigArch))
+            c.struct_size = C.sizeof(_lib.ConfigLane)
+            c.tail_lane = -1
         ctx = C.c_void_p()
         _lib.check(lib.apse_create(C.byref(c), C.byref(ctx)), None, "apse_create: " + lib.apse_last_error(None).decode())
         try:
@@ -339,6 +348,13 @@ class TrackRCNN:
         raw = self._host.numpy().tobytes()
         self.last_results = FrameResults(raw, self._lay, batch)
         return self.last_results
+
+    def lane_stats(self):
+        """apse_lane_stats: (forwards with their tail on the lane, joins that had to wait, FPN waits not yet complete at enqueue,
+        host drains)."""
+        out = (C.c_longlong * 4)()
+        self._call("apse_lane_stats", C.byref(out))
+        return tuple(int(v) for v in out)
 
     def export_feature(self, name, batch):
         shp = (C.c_int * 3)()

@@ -92,6 +92,11 @@ typedef struct apse_config {
                                      res2..res4 (keys backbone.stem.*, backbone.res{2,3,4}.N.*), the RPN on res4 with 15 anchors,
                                      roi_heads.res5 on 14 x 14 ROIAlign crops of res4, 14 x 14 masks, association on res4.  A
                                      caller passing the struct_size of the layout without this field gets 0 */
+    int tail_lane;                /* 0 = default: the proposal selection, heads and results copy of a forward that runs ahead of a
+                                     read go to a second stream of the context (the tail lane, see "per-frame stages" below);
+                                     < 0 = off: every launch on the caller's stream.  The environment variable APSE_TAIL_LANE=0 (read at apse_create) switches it
+                                     off for every context; C4 (arch 1) never has one.  A caller passing the struct_size of a layout
+                                     without this field gets 0 */
 } apse_config;
 
 /* Byte offsets of the per-forward results block (one D2H copy, apse_read_results). n = max_batch*dets_per_image. */
@@ -142,7 +147,20 @@ int apse_set_resize_tables(apse_ctx* ctx, const int* hbounds, const int* hcoef, 
 int apse_set_camera(apse_ctx* ctx, const double* m9, const double* dist, int ndist, const uint8_t* lut256_host, int do_undistort,
                     int do_gamma);
 
-/* ---- per-frame stages (all enqueue on `stream`) ---- */
+/* ---- per-frame stages ----
+ * All enqueue and return.  apse_preprocess_*, apse_backbone and the convolutions of apse_rpn(_levels) go to `stream`.  The rest
+ * of a forward -- proposal selection, apse_box_head / apse_set_detections, apse_mask_tail, apse_embed -- and the copy of
+ * apse_read_results(_begin) go to `stream` too, unless the forward RUNS AHEAD: when apse_backbone is called between
+ * apse_read_results_begin and _end (the software-pipelined loop), that forward's rest goes to the context's TAIL LANE, a
+ * non-blocking stream of its own that follows `stream` by an event behind the RPN convolutions.  The next forward's stem..res5 on `stream` therefore run beside this forward's tail; its first
+ * FPN step waits for the tail (the FPN overwrites the maps the heads read), so at most one forward runs ahead.  Results are
+ * the same bits.  What a caller must know:
+ *   - synchronising `stream` does NOT wait for the heads of a forward that ran ahead: results are complete when apse_read_results(_end) returns,
+ *     and every other entry that touches the context (apse_copy_mask_window(s), apse_export_feature, apse_debug_tensor,
+ *     apse_roi_features, apse_mask_roi_features, apse_profile, apse_set_camera) first makes `stream` (or the host) wait for the lane;
+ *   - use one `stream` per context for the calls of one forward.
+ * The lane is off -- every launch on `stream`, in the order of the calls -- with apse_config.tail_lane < 0, APSE_TAIL_LANE=0,
+ * under C4 and while apse_profile is enabled. */
 /* ResizeShortestEdge.apply_image (PIL bilinear) + preprocess_image: u8 BGR frames [B][frame_h][frame_w][3]
  * -> internal normalised, /32-padded network input (track_predictor.py:48-49, track_rcnn.py:35). */
 int apse_preprocess_frames(apse_ctx* ctx, const uint8_t* frames_dev, int batch, void* stream);
@@ -191,6 +209,11 @@ int apse_read_results(apse_ctx* ctx, void* host_dst, size_t bytes, void* stream)
  * leaves (distance, pixel index) keys in that field). */
 int apse_read_results_begin(apse_ctx* ctx, void* host_dst, size_t bytes, void* stream);
 int apse_read_results_end(apse_ctx* ctx, void* host_dst);
+/* Tail lane counters since apse_create: out4[0] forwards whose tail was enqueued on the lane, [1] times another entry had to
+ * wait for unfinished lane work, [2] first-FPN-step waits whose event was not yet complete when the trunk was enqueued,
+ * [3] times the lane was emptied by a host wait (apse_profile, apse_set_camera, and apse_read_results_end when no forward was
+ * enqueued behind the read: the lane's stream is then destroyed until a forward runs ahead again). */
+int apse_lane_stats(apse_ctx* ctx, long long* out4);
 /* Copies detection i's mask window (rows rect.y0..y1, 64-bit words (x0>>6)..((x1+63)>>6)) to dst_dev: the masks of the forward whose
  * results were last read (apse_read_results / _begin), or of the last forward when no read has been started since. */
 int apse_copy_mask_window(apse_ctx* ctx, int det, int x0, int y0, int x1, int y1, uint64_t* dst_dev, void* stream);

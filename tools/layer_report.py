@@ -12,11 +12,54 @@ ndet *= BATCH                      # the packed detection list of a step holds e
 rows = list(csv.DictReader(open(path)))
 rows.sort(key=lambda r: int(r['Start_Timestamp']))
 idx = [i for i, r in enumerate(rows) if 'pil_resize_h' in r['Kernel_Name'].split('(')[0]]
-fr = rows[idx[-2]:idx[-1]]
+
+
+def base(r):
+    return r['Kernel_Name'].split('(')[0]
+
+
+def union_us(rs):
+    """Time covered by at least one of the kernels (us): equal to their sum on a serial stream, less where two streams overlap."""
+    tot, end = 0, 0
+    for s, e in sorted((int(r['Start_Timestamp']), int(r['End_Timestamp'])) for r in rs):
+        if e > end:
+            tot += e - max(s, end)
+            end = e
+    return tot / 1e3
+
+
+# With the tail lane a forward is on two streams: resize, trunk, FPN and the RPN convolutions on the one that carries pil_resize_h,
+# everything from rpn_topk_stage on (the tail) on the lane, beside the NEXT forward's trunk.  The step reported is the last but
+# one: its trunk launches, then its own tail launches (the lane's group that starts behind this trunk's last launch), so the
+# layer table below sees one forward in plan order.  `window` is everything that ran between the two resizes, whichever
+# forward it belongs to: its union against its sum is the overlap.
+QKEY = next((k for k in ('Stream_Id', 'Queue_Id') if k in rows[0]), None)
+trunk_q = rows[idx[-1]][QKEY] if QKEY else None
+window = rows[idx[-2]:idx[-1]]
+lane_rows = [r for r in rows if QKEY and r[QKEY] != trunk_q]
+TWO_STREAMS = any('rpn_topk_stage' in base(r) for r in lane_rows)
+if TWO_STREAMS:
+    trunk = [r for r in window if r[QKEY] == trunk_q]
+    groups = []
+    for i, r in enumerate(lane_rows):
+        if 'rpn_topk_stage' in base(r) and (i == 0 or 'rpn_topk_stage' not in base(lane_rows[i - 1])):
+            groups.append([])
+        if groups:
+            groups[-1].append(r)
+    fork = int(trunk[-1]['Start_Timestamp'])
+    tail = next((g for g in groups if int(g[0]['Start_Timestamp']) >= fork), groups[-1])
+    fr = trunk + tail
+else:
+    fr = window
 t0 = int(fr[0]['Start_Timestamp'])
-span = (int(fr[-1]['End_Timestamp']) - t0) / 1e3
+span = (max(int(r['End_Timestamp']) for r in fr) - t0) / 1e3
 busy = sum(int(r['End_Timestamp']) - int(r['Start_Timestamp']) for r in fr) / 1e3
 print('step (batch %d): %d kernels, span %.1f us, busy %.1f us' % (BATCH, len(fr), span, busy))
+wsum = sum(int(r['End_Timestamp']) - int(r['Start_Timestamp']) for r in window) / 1e3
+wspan = (int(rows[idx[-1]]['Start_Timestamp']) - int(window[0]['Start_Timestamp'])) / 1e3
+print('window between two resizes (%s): %d kernels, %.1f us; kernel time sum %.1f us, union %.1f us, overlapped %.1f us'
+      % ('two streams: trunk of this forward beside the tail of the one before' if TWO_STREAMS else 'one stream', len(window), wspan,
+         wsum, union_us(window), wsum - union_us(window)))
 layers = []
 
 
@@ -115,8 +158,14 @@ for k, v in others.most_common(14):
 if '--timeline' in sys.argv:
     # every launch of the step in order: start offset, duration and the idle gap before it (us)
     print('timeline (us): start  dur  gap  kernel')
+    # two streams: the launches of the window in start order, the lane's marked `L`; the gap is then the idle time of the whole
+    # card in front of a launch (0 while another stream's kernel is still running)
+    tl = sorted(window, key=lambda r: int(r['Start_Timestamp'])) if TWO_STREAMS else fr
+    t0 = int(tl[0]['Start_Timestamp'])
     prev_end = t0
-    for r in fr:
+    for r in tl:
         s, e = int(r['Start_Timestamp']), int(r['End_Timestamp'])
-        print('  %8.1f %7.1f %6.1f  %s  grid=%s' % ((s - t0) / 1e3, (e - s) / 1e3, (s - prev_end) / 1e3, r['Kernel_Name'].split('(')[0][:70], r.get('Grid_Size', '')))
+        mark = 'L' if TWO_STREAMS and r[QKEY] != trunk_q else ' '
+        print('  %8.1f %7.1f %6.1f %s %s  grid=%s' % ((s - t0) / 1e3, (e - s) / 1e3, max(s - prev_end, 0) / 1e3, mark, r['Kernel_Name'].split('(')[0][:70], r.get('Grid_Size', '')))
         prev_end = max(prev_end, e)
+    print('kernel time: sum %.1f us, union %.1f us' % (sum(int(r['End_Timestamp']) - int(r['Start_Timestamp']) for r in tl) / 1e3, union_us(tl)))
