@@ -18,7 +18,8 @@
 // Global->LDS staging goes through registers, one 16-byte "piece" per MFMA gap: the pieces of k-step s+1
 // (s+2 for the small tiles, which keep two register sets) are fetched during the first half of step s and
 // handed to LDS during its second half (an f32 MFMA k-step is 1024 cycles/wave at 64x64 and 4096 at
-// 128x128); one barrier per k-step.  See DESIGN.md section 3 for the measured effect of each choice.
+// 128x128); one barrier per k-step -- for every f32 tile but 128x128 in front of the step's LAST MFMA group, which then runs
+// over the next step's first fragment reads.  See DESIGN.md section 3 for the measured effect of each choice.
 #include "apse_common.h"
 #include <type_traits>
 
@@ -271,39 +272,52 @@ __global__ __launch_bounds__(64 * WM * WN * WK) void conv_igemm_f32(const ConvPa
             const bool warm_now = warm_pending;
             warm_pending = false;
             if (warm_now) apse_warm_issue(warm, p.next_w, p.next_w_bytes, blockIdx.x, gridDim.x, tid);
+            // f32 small tiles: both register sets exist here, so the second step's operands are requested directly behind the
+            // first's and the two round trips overlap (16-bit operands: behind the first barrier, as before)
+            constexpr bool EARLY2 = DP && PR == 0;
             load_step(s_begin);
+            if constexpr (EARLY2) load_step_bl(1);
             store_step(0);
             if (warm_now) apse_warm_retire(warm);
             __syncthreads();
             if constexpr (DESC) {
                 constexpr int NP = KS * (AP + BP);          // fetch pieces per k-step
                 constexpr int G = 16 * KS / WK;             // MFMA groups per k-step and wave (TM*TN MFMAs each)
+                constexpr int NC = 4 * KS / WK;             // fragment chunks (one ds_read_b128 per operand row) per k-step and wave
                 constexpr int SP = (G / 2) / NP > 0 ? (G / 2) / NP : 1;
                 static_assert(PR != 0 || (NP * SP <= G / 2 + SP - 1 && G / 2 + (NP - 1) * SP < G), "piece schedule does not fit the k-step");
-                if constexpr (DP) load_step_bl(1);          // operands of the second step, in flight across the first
+                // f32: the step is ROTATED -- its barrier stands in front of its last MFMA group, and that group runs over the next
+                // step's first fragment reads.  Every hand-over of the step has to sit in front of group G - 1 for that (the 128x128
+                // tile hands over in all of its last eight groups and keeps the barrier at the end of the step), and the chunk count
+                // is even, so the fragment set the last chunk does not use (set 0) is free for those reads.
+                constexpr bool ROT = PR == 0 && G / 2 + (NP - 1) * SP < G - 1;
+                static_assert(!ROT || (G / 2 + (NP - 1) * SP < G - 1 && NC % 2 == 0), "a rotated k-step hands over in front of its last MFMA group");
+                if constexpr (DP && !EARLY2) load_step_bl(1);          // operands of the second step, in flight across the first
+                f32x4 af[2][TM], bf[2][TN];
+                auto load_frags_of = [&](int rb, int cc, int fb) {      // chunk cc of LDS buffer rb -> fragment set fb
+                    const int u = (cc >> 2) * WK + kg, c = cc & 3;      // this wave group's sub-steps only
+                    const float* Ab = As + (rb * KS + u) * BM * 32;
+                    const float* Bb = Bs + (rb * KS + u) * BN * 32;
+                    const int ls = 2 * c + fh;
+#pragma unroll
+                    for (int i = 0; i < TM; ++i) {
+                        const int row = (wm * TM + i) * 32 + fr;
+                        af[fb][i] = *reinterpret_cast<const f32x4*>(Ab + row * 32 + ((ls ^ ((row >> 1) & 7)) << 2));
+                    }
+#pragma unroll
+                    for (int j = 0; j < TN; ++j) {
+                        const int row = (wn * TN + j) * 32 + fr;
+                        bf[fb][j] = *reinterpret_cast<const f32x4*>(Bb + row * 32 + ((ls ^ ((row >> 1) & 7)) << 2));
+                    }
+                };
+                if constexpr (ROT) load_frags_of(0, 0, 0);    // the tile's first step reads its own first fragments; every later one finds them read
                 // one k-step; PAR = parity of the step inside this K slice = LDS buffer it reads
                 auto kstep = [&](auto PAR) {
                     constexpr int buf = decltype(PAR)::value;
                     constexpr int FS = DP ? buf : 0;          // register set the fetches of this step fill
                     constexpr int SS = DP ? (buf ^ 1) : 0;    // register set handed to LDS buffer buf^1 in this step
-                    f32x4 af[2][TM], bf[2][TN];
-                    auto load_frags = [&](int cc, int fb) {
-                        const int u = (cc >> 2) * WK + kg, c = cc & 3;      // this wave group's sub-steps only
-                        const float* Ab = As + (buf * KS + u) * BM * 32;
-                        const float* Bb = Bs + (buf * KS + u) * BN * 32;
-                        const int ls = 2 * c + fh;
-#pragma unroll
-                        for (int i = 0; i < TM; ++i) {
-                            const int row = (wm * TM + i) * 32 + fr;
-                            af[fb][i] = *reinterpret_cast<const f32x4*>(Ab + row * 32 + ((ls ^ ((row >> 1) & 7)) << 2));
-                        }
-#pragma unroll
-                        for (int j = 0; j < TN; ++j) {
-                            const int row = (wn * TN + j) * 32 + fr;
-                            bf[fb][j] = *reinterpret_cast<const f32x4*>(Bb + row * 32 + ((ls ^ ((row >> 1) & 7)) << 2));
-                        }
-                    };
-                    load_frags(0, 0);
+                    auto load_frags = [&](int cc, int fb) { load_frags_of(buf, cc, fb); };
+                    if constexpr (!ROT) load_frags(0, 0);
                     if constexpr (PR != 0) {
                         // 16-bit operands: one MFMA per (chunk, tile) -- the gaps are counted per MFMA and may carry
                         // more than one piece (a 64-deep sub-step is a quarter of the f32 step's matrix time)
@@ -354,6 +368,17 @@ __global__ __launch_bounds__(64 * WM * WN * WK) void conv_igemm_f32(const ConvPa
                                 store_piece(SS, buf ^ 1, ((g - G / 2) / SP) / (AP + BP), ((g - G / 2) / SP) % (AP + BP));
                                 __builtin_amdgcn_sched_barrier(0);
                             }
+                            if (ROT && g == G - 1) {
+                                // the step's barrier, in front of its last MFMA group: buf^1 is complete and every wave has this
+                                // step's fragments in registers (the barrier's fence waits for the wave's own LDS reads), so buf may
+                                // be rewritten by the next step.  That step's first fragments are read here, behind the barrier and
+                                // under the last group; the last step of a K slice reads a buffer nobody filled, into registers
+                                // nobody uses.
+                                __builtin_amdgcn_sched_barrier(0);
+                                __syncthreads();
+                                load_frags_of(buf ^ 1, 0, 0);
+                                __builtin_amdgcn_sched_barrier(0);
+                            }
 #pragma unroll
                             for (int i = 0; i < TM; ++i)
 #pragma unroll
@@ -361,7 +386,7 @@ __global__ __launch_bounds__(64 * WM * WN * WK) void conv_igemm_f32(const ConvPa
                                     acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x2f32(af[cc & 1][i][k], bf[cc & 1][j][k], acc[i][j], 0, 0, 0);
                         }
                     }
-                    __syncthreads();
+                    if constexpr (!ROT) __syncthreads();
                 };
                 for (int sb = s_begin; sb < s_end; sb += 2) {
                     kstep(std::integral_constant<int, 0>{});
