@@ -161,6 +161,11 @@ def load():
         "apse_mots_overlaps": ([vp, i, vp, i, vp, i, vp, vp], i),
         "apse_mots_shift_overlaps": ([vp, i, vp, i, i, i, vp, vp], i),
         "apse_mots_render_idmap": ([vp, vp, i, i, i, vp, vp], i),
+        "apse_mots_crop_overlaps": ([vp, vp, i, i, i, vp, sz, vp, vp, vp], i),
+        "apse_mots_rle_workspace_bytes": ([vp, i, i, i], sz),
+        "apse_mots_bits_to_rle": ([vp, vp, i, i, i, vp, i, vp, vp, vp, sz, vp], i),
+        "apse_mots_rle_pack_workspace_bytes": ([i], sz),
+        "apse_mots_rle_pack": ([vp, vp, i, i, vp, i, vp, vp, vp, sz, vp], i),
         "apse_resize_normalize": ([vp, vp, vp, vp, vp, vp, i, vp, vp, i, i, i, i, i, i, i, i, C.POINTER(f * 3), vp], i),
         "apse_assoc_fc_workspace_bytes": ([i, i, i], sz),
         "apse_assoc_fc_forward": ([vp, vp, vp, i, i, i, vp, vp, vp, sz, vp], i),
@@ -212,6 +217,8 @@ EXPORTS = ["apse_create", "apse_destroy", "apse_last_error", "apse_version", "ap
            "apse_replay_step", "apse_replay_packed", "apse_replay_max_id", "apse_replay_next_id", "apse_render_workspace_bytes",
            "apse_render_instances", "apse_render_pack_mask", "apse_render_font_host", "apse_mots_split_workspace_bytes",
            "apse_mots_split_idmap", "apse_mots_rle_to_bits", "apse_mots_overlaps", "apse_mots_shift_overlaps", "apse_mots_render_idmap",
+           "apse_mots_crop_overlaps", "apse_mots_rle_workspace_bytes", "apse_mots_bits_to_rle",
+           "apse_mots_rle_pack_workspace_bytes", "apse_mots_rle_pack",
            "apse_assoc_fc_workspace_bytes", "apse_assoc_fc_forward", "apse_assoc_fc_backward", "apse_triplet_workspace_bytes",
            "apse_triplet_hard_forward", "apse_triplet_all_forward", "apse_triplet_hard_backward", "apse_triplet_all_backward",
            "apse_sgd_step", "apse_coco_box_iou", "apse_coco_poly_to_bits", "apse_coco_match",

@@ -27,6 +27,7 @@ from ..structures.window_mask import WindowMask
 from . import coco as cocomod
 from . import mots_eval as me
 from . import rle as rlemod
+from . import rle_device
 
 
 class Params:
@@ -416,7 +417,8 @@ def _xywh_f32(instances):
 
 def instances_to_coco_json(instances, img_id):
     """detectron2 0.1.2 ``instances_to_coco_json``: XYWH boxes computed in f32, f32 scores as Python floats, ``category_id`` =
-    the class index, masks as compressed RLE with ``counts`` decoded to str."""
+    the class index, masks as compressed RLE with ``counts`` decoded to str.  WindowMasks on a GPU are encoded there from their
+    windows (utils/rle_device.py); other masks through the dense host frame."""
     num_instance = len(instances)
     if num_instance == 0:
         return []
@@ -426,7 +428,13 @@ def instances_to_coco_json(instances, img_id):
     has_mask = instances.has("pred_masks")
     if has_mask:
         rles = []
-        for mask in instances.pred_masks:
+        masks = list(instances.pred_masks)
+        if rle_device.device_of(masks) is not None and len({tuple(m.frame_size) for m in masks}) == 1:
+            rles = rle_device.encode_masks(masks, masks[0].frame_size)     # on the GPU, from the windows
+            for r in rles:
+                r["counts"] = r["counts"].decode("utf-8")
+            masks = []
+        for mask in masks:
             dense = mask.dense() if isinstance(mask, WindowMask) else torch.as_tensor(mask)
             r = rlemod.encode(dense.cpu().numpy().astype(np.uint8))
             r["counts"] = r["counts"].decode("utf-8")

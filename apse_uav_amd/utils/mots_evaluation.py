@@ -8,13 +8,15 @@ windows (and, for the id map, the one u16 output image), never N dense frames.
  * ``result_image_from_objects``  (:58-77)  u16 id map, ``class*1000 + id``, later objects overwrite earlier ones
  * ``parse_mots_seqmap``          (:80-94)
  * ``crop_overlapping_masks``     (:97-117) the lower-score mask of every overlapping pair loses the overlap
+``file_lines_from_instances`` and ``crop_overlapping_masks`` run on the GPU (utils/rle_device.py) when every mask is a
+``WindowMask`` whose bits live there; the host code below serves every other input.
 Class relabelling as in the reference: 0 (person) -> 2, 2 (car) -> 1, every other class is skipped (:31-37).
 """
 import numpy as np
 import torch
 
 from ..structures.window_mask import WindowMask
-from . import rle
+from . import rle, rle_device
 
 
 def _mots_class(ob_class):
@@ -42,13 +44,19 @@ def _dense_np(m, image_size):
 
 
 def file_lines_from_instances(object_instances, frame_num, image_size):
+    """WindowMasks on a GPU are encoded there (utils/rle_device.encode_masks, the scored classes only, one call per frame);
+    any other mask goes through the dense host frame as before.  The lines are the same either way."""
     out_string = ""
+    scored = [k for k in range(len(object_instances)) if _mots_class(int(object_instances.pred_classes[k])) is not None]
+    on_gpu = bool(scored) and rle_device.device_of([object_instances.pred_masks[k] for k in scored]) is not None
+    if on_gpu:
+        rles = dict(zip(scored, rle_device.encode_masks([object_instances.pred_masks[k] for k in scored], image_size)))
     for obj_idx in range(len(object_instances)):
         ob_class = _mots_class(int(object_instances.pred_classes[obj_idx]))
         if ob_class is None:
             continue
         ob_id = object_instances.ids[obj_idx]
-        ob_rle = rle.encode(_dense_np(object_instances.pred_masks[obj_idx], image_size))
+        ob_rle = rles[obj_idx] if on_gpu else rle.encode(_dense_np(object_instances.pred_masks[obj_idx], image_size))
         object_id = ob_class * 1000 + ob_id
         out_string += "%d %d %d %d %d %s\n" % (frame_num, object_id, ob_class, image_size[0], image_size[1],
                                                ob_rle["counts"].decode("ascii"))
@@ -105,6 +113,13 @@ def crop_overlapping_masks(object_instances):
         return
     masks = object_instances.pred_masks
     scores = object_instances.scores
+    if rle_device.device_of(masks) is not None and n <= rle_device.MAX_OBJECTS and \
+            len({tuple(m.frame_size) for m in masks}) == 1:
+        cropped, changed = rle_device.crop_overlaps(object_instances, with_changed=True)   # on the words, on the GPU
+        for k in range(n):
+            if changed[k]:
+                masks[k] = cropped[k]
+        return
     wins = [None] * n
 
     def get(k):

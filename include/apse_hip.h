@@ -418,6 +418,47 @@ int apse_mots_shift_overlaps(const apse_mots_window* windows, int n_windows, con
 int apse_mots_render_idmap(const apse_mots_object* objects, const int* values_host, int n, int H, int W, uint16_t* idmap,
                            void* stream);
 
+/* ---- Result writers (csrc/rle_encode.hip): the masks of one frame -> the cropped windows of crop_overlapping_masks, COCO RLE run
+ * ends and pycocotools' compressed counts string, without a dense frame.  Stateless, integer only: enqueues on `stream`, no
+ * allocation, no synchronisation.  Every output position is a count followed by a scan (no atomics hand out positions), so two
+ * runs are bit-identical.  Windows and objects are the layouts above; here words_per_row may exceed
+ * ((x1 + 63) >> 6) - (x0 >> 6) (a row stride), and bits outside the rect's columns are ignored.
+ * Each entry takes its structs twice: on the device for the kernels and as a host copy (`*_host`, the same values; the bits
+ * pointers are only compared with NULL), from which the limits are checked before anything is launched.  APSE_E_INVALID, with no
+ * launch: a NULL pointer, n outside 0 .. APSE_MOTS_MAX_OBJECTS, a frame outside 1 <= h <= APSE_MAX_FRAME_H, 1 <= w <=
+ * APSE_MAX_FRAME_W, a non-empty rect that leaves the frame, words_per_row too small for the rect, a workspace smaller than its
+ * query.  n == 0 is a no-op.  A device struct that breaks these limits although its host copy keeps them is treated as empty.
+ * Capacity protocol (as apse_mots_split_idmap): info[0] = the elements needed, info[1] = 1 when they were written; when the
+ * need exceeds `cap` nothing is written to the data array, info[1] = 0, and the caller retries with more room.  The offsets
+ * array is written either way.  info[0] saturates at INT_MAX. */
+#define APSE_MOTS_RLE_SEG_ROWS 64 /* rows one lane walks: a window column is counted in segments of this many rows */
+/* crop_overlapping_masks on the words: a pixel stays with object k iff k is the (score, index)-lexicographic maximum among the
+ * objects whose mask holds it (the owner rule of apse_mots_render_idmap; equal to the reference's pair loop).  Object k's
+ * cropped window (same rect, same words_per_row, every word of it written, 0 outside the rect's columns) goes to pool + pool_off[k]
+ * (device int64 [n], in words); stats[k] (device int64 [n][4]) = {set pixels before, set pixels after, sum of (x + 1), sum of
+ * (y + 1)} over the cropped mask, from which the host takes the 1-based floor centroid.  An object with NULL bits or an empty
+ * rect has no pixels: it writes no words (the caller reserves none for it), its pool_off is not used beyond the range check, and
+ * its stats are 0.  An object whose window does not fit pool_words from its offset writes nothing and gets stats -1.  The
+ * regions [pool_off[k], pool_off[k] + rows * words_per_row) of the objects that have bits must not overlap. */
+int apse_mots_crop_overlaps(const apse_mots_object* objects, const apse_mots_object* objects_host, int n, int H, int W,
+                            uint64_t* pool, size_t pool_words, const long long* pool_off, long long* stats, void* stream);
+/* Workspace bytes of apse_mots_bits_to_rle for these windows (host copy); 0 for arguments it would refuse. */
+size_t apse_mots_rle_workspace_bytes(const apse_mots_window* windows_host, int n, int h, int w);
+/* Window bits -> run ends over an h x w image in column-major order: with v(p), p = x * h + y, the window's bit inside its rect
+ * and 0 elsewhere, object k's ends are every p in [1, h * w) with v(p) != v(p - 1), ascending, then h * w, preceded by 0 when
+ * v(0) = 1: the running sums of pycocotools' counts, the input format of apse_mots_rle_to_bits.  An empty or NULL-bits window
+ * gives the single end h * w.  ends [cap], ends_off [n + 1], info [2] are device int arrays. */
+int apse_mots_bits_to_rle(const apse_mots_window* windows, const apse_mots_window* windows_host, int n, int h, int w, int* ends,
+                          int cap, int* ends_off, int* info, void* ws, size_t ws_bytes, void* stream);
+/* Workspace bytes of apse_mots_rle_pack for up to max_ends run ends. */
+size_t apse_mots_rle_pack_workspace_bytes(int max_ends);
+/* Run ends -> the bytes of pycocotools' compressed counts string (rleToString): count c_i = end_i - end_(i-1), value c_i -
+ * c_(i-2) from the fourth count on, 5-bit groups low first with bit 0x20 as continuation, each byte + 48 (1 to 7 bytes per
+ * value).  Object k's string is chars[chars_off[k] .. chars_off[k + 1]).  max_ends is the capacity the ends were written with:
+ * ends_off[n] > max_ends (the ends were not written) gives info = {-1, 0} and chars_off all 0. */
+int apse_mots_rle_pack(const int* ends, const int* ends_off, int n, int max_ends, char* chars, int cap, int* chars_off,
+                       int* info, void* ws, size_t ws_bytes, void* stream);
+
 /* ---- COCO evaluation (csrc/coco_eval.hip): the per-pair and per-group arithmetic of pycocotools 2.0 COCOeval for iouType
  * 'bbox' and 'segm' (utils/coco_eval.py keeps the bookkeeping on the host).  Stateless: no context, enqueues on `stream` only, no
  * allocation, no synchronisation.  Every floating-point value is f64 as pycocotools computes it; no float atomics, every reduction

@@ -2,7 +2,7 @@
 """Track the sequences of a KITTI MOTS seqmap and write or score the results: the --mots_evaluation mode of the reference's
 standard_rcnn_tracker_test.py.
 
-    python tools/track_mots.py SEQMAP --images IMAGE_DIR [--output DIR] [--eval GT_DIR] [--no-write]
+    python tools/track_mots.py SEQMAP --images IMAGE_DIR [--output DIR] [--eval GT_DIR] [--no-write] [--txt]
                                [--detector-state FILE] [--association-state FILE] [--metric NAME]
 
 IMAGE_DIR holds one folder of PNG / JPEG / BMP frames per sequence (datasets/data_tracking_image_2/training/image_02 in the
@@ -11,6 +11,8 @@ result_image_from_objects(crop_overlapping_masks(objects)), rendered on the devi
 (default output/evaluation_results, as the reference).  --eval GT_DIR scores the tracker online against the ground truth
 (utils/mots_eval.MotsEvaluator) and prints eval.py's tables; --no-write skips the PNGs.  Without state files the tracker runs
 on the seeded synthetic weights (apse_uav_amd.weights), which exercises the pipeline but detects nothing meaningful.
+--txt also writes DIR/SEQ.txt, the MOTS text result format: per frame the file_lines_from_instances lines of the cropped
+objects (frame index frame_count - 1, as the reference's commented-out writer), encoded on the device from the mask windows.
 --metric mask_iou tracks without an association head (no --association-state needed): centroid-aligned mask IoU >= 0.7.
 """
 import argparse
@@ -29,6 +31,19 @@ def image_files(path):
     return [f for f in sorted(os.listdir(path)) if f.split(".")[-1].lower() in EXTENSIONS]
 
 
+def frame_txt_lines(objects, frame_idx, size):
+    """The MOTS .txt lines of one frame: file_lines_from_instances(crop_overlapping_masks(objects)); ``objects`` keeps its
+    masks (the crop works on a copy of the list)."""
+    from apse_uav_amd.structures.instances import Instances
+    from apse_uav_amd.structures.window_mask import MaskList
+    from apse_uav_amd.utils.mots_evaluation import crop_overlapping_masks, file_lines_from_instances
+    clone = Instances(tuple(size))
+    clone.pred_classes, clone.scores, clone.ids = objects.pred_classes, list(objects.scores), list(objects.ids)
+    clone.pred_masks = MaskList(objects.pred_masks)
+    crop_overlapping_masks(clone)
+    return file_lines_from_instances(clone, frame_idx, size)
+
+
 def main(argv=None):
     ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
     ap.add_argument("seqmap")
@@ -36,6 +51,7 @@ def main(argv=None):
     ap.add_argument("--output", default="output/evaluation_results")
     ap.add_argument("--eval", default="", help="ground-truth folder: score online")
     ap.add_argument("--no-write", action="store_true")
+    ap.add_argument("--txt", action="store_true", help="also write OUTPUT/SEQ.txt (MOTS text results)")
     ap.add_argument("--detector-state", default="", help="torch.load-able detector state dict")
     ap.add_argument("--association-state", default="", help="torch.load-able association head state dict")
     ap.add_argument("--metric", default="embeddings", choices=["embeddings", "mask_iou"], help="association metric")
@@ -67,6 +83,7 @@ def main(argv=None):
         out_dir = os.path.join(args.output, seq)
         if not args.no_write:
             os.makedirs(out_dir, exist_ok=True)
+        txt = []
         if evaluator is not None:
             evaluator.begin_sequence(seq)
         print("\nEvaluating sequence: ", seq)
@@ -80,6 +97,12 @@ def main(argv=None):
             if not args.no_write:
                 img = render_idmap(objects, size).cpu().numpy()
                 Image.fromarray(img).save(os.path.join(out_dir, "%06d.png" % frame_idx))
+            if args.txt:
+                txt.append(frame_txt_lines(objects, frame_idx, size) if len(objects) else "")
+        if args.txt:
+            os.makedirs(args.output, exist_ok=True)
+            with open(os.path.join(args.output, seq + ".txt"), "w") as fh:
+                fh.write("".join(txt))
         if evaluator is not None:
             evaluator.end_sequence()
     if evaluator is not None:
