@@ -77,6 +77,115 @@ class ConvDesc(C.Structure):
                                        "cfg", "splitk", "prec", "fuse_reduce", "x_st", "res_st", "y_st")]
 
 
+vp, i, f, sz = C.c_void_p, C.c_int, C.c_float, C.c_size_t
+# every entry of include/apse_hip.h: name -> (argtypes, restype)
+SIGNATURES = {
+    "apse_create": ([C.POINTER(Config), C.POINTER(vp)], i),
+    "apse_destroy": ([vp], None),
+    "apse_last_error": ([vp], C.c_char_p),
+    "apse_version": ([], C.c_char_p),
+    "apse_set_weight": ([vp, C.c_char_p, vp, C.POINTER(C.c_int64), i], i),
+    "apse_finalize_weights": ([vp], i),
+    "apse_set_resize_tables": ([vp, vp, vp, i, vp, vp, i], i),
+    "apse_set_camera": ([vp, C.POINTER(C.c_double), C.POINTER(C.c_double), i, vp, i, i], i),
+    "apse_preprocess_frames": ([vp, vp, i, vp], i),
+    "apse_preprocess_images": ([vp, vp, i, vp], i),
+    "apse_backbone": ([vp, i, vp], i),
+    "apse_rpn": ([vp, i, vp], i),
+    "apse_rpn_levels": ([vp, i, i, vp], i),
+    "apse_box_head": ([vp, i, vp], i),
+    "apse_set_detections": ([vp, vp, vp, vp, vp, i, vp], i),
+    "apse_mask_tail": ([vp, i, vp], i),
+    "apse_embed": ([vp, i, vp], i),
+    "apse_forward": ([vp, i, vp], i),
+    "apse_results_describe": ([vp, C.POINTER(ResultsLayout)], i),
+    "apse_read_results": ([vp, vp, sz, vp], i),
+    "apse_read_results_begin": ([vp, vp, sz, vp], i),
+    "apse_read_results_end": ([vp, vp], i),
+    "apse_lane_stats": ([vp, C.POINTER(C.c_longlong * 4)], i),
+    "apse_copy_mask_window": ([vp, i, i, i, i, i, vp, vp], i),
+    "apse_copy_mask_windows": ([vp, i, vp, vp, vp, vp, vp], i),
+    "apse_host_copy": ([vp, vp, sz, i], i),
+    "apse_feature_shape": ([vp, C.c_char_p, C.POINTER(C.c_int * 3)], i),
+    "apse_export_feature": ([vp, C.c_char_p, vp, i, vp], i),
+    "apse_debug_tensor": ([vp, C.c_char_p, vp, sz, C.POINTER(sz), vp], i),
+    "apse_flops": ([vp, i, C.c_double, C.c_double], C.c_double),
+    "apse_profile": ([vp, i], i),
+    "apse_profile_read": ([vp, C.POINTER(C.c_double * 42), i], i),
+    "apse_conv_packed_elems": ([C.POINTER(ConvDesc)], sz),
+    "apse_conv_pack_weight": ([C.POINTER(ConvDesc), vp, i, vp, vp], i),
+    "apse_conv2d": ([C.POINTER(ConvDesc), vp, vp, vp, vp, vp, vp, sz, vp], i),
+    "apse_winograd_pack_filter": ([vp, i, i, vp], i),
+    "apse_winograd_conv2d": ([C.POINTER(ConvDesc), vp, vp, vp, vp, vp], i),
+    "apse_maxpool3x3s2": ([vp, vp, i, i, i, i, vp], i),
+    "apse_maxpool3x3s2_typed": ([vp, vp, i, i, i, i, i, vp], i),
+    "apse_roi_align": ([C.POINTER(vp), C.POINTER(i), C.POINTER(i), vp, i, i, i, vp, vp], i),
+    "apse_roi_align_typed": ([C.POINTER(vp), C.POINTER(i), C.POINTER(i), vp, i, i, i, i, vp, vp], i),
+    "apse_roi_pool": ([vp, i, i, vp, vp, i, i, f, vp, vp], i),
+    "apse_roi_features": ([vp, i, vp, vp, i, i, vp, vp], i),
+    "apse_nms_rank": ([vp, vp, vp, i, i, i, i, f, i, vp, vp, vp, vp, vp], i),
+    "apse_mask_centroid_dense": ([vp, i, i, C.POINTER(C.c_int * 3), vp], i),
+    "apse_mask_closest_dense": ([vp, i, i, f, f, C.POINTER(C.c_int * 2), vp], i),
+    "apse_l2_normalize": ([vp, vp, i, i, vp], i),
+    "apse_sqdist": ([vp, vp, i, i, i, vp, vp], i),
+    "apse_undistort_gamma": ([vp, vp, i, i, i, C.POINTER(C.c_double), C.POINTER(C.c_double), i, vp, i, i, vp], i),
+    "apse_lab_tables_host": ([vp, vp, C.c_size_t], C.c_size_t),
+    "apse_replay_create": ([i, i, f, i], vp),
+    "apse_replay_destroy": ([vp], None),
+    "apse_replay_step": ([vp, i, i, vp, vp, vp, C.c_char_p, i, vp], i),
+    "apse_replay_packed": ([vp, vp, C.c_longlong, i, i, i, vp, C.c_longlong], C.c_longlong),
+    "apse_replay_max_id": ([vp], i),
+    "apse_replay_next_id": ([vp], i),
+    "apse_render_workspace_bytes": ([i, i, i], sz),
+    "apse_render_instances": ([vp, vp, i, i, i, i, vp, i, vp, sz, vp, i, vp, sz, vp], i),
+    "apse_render_pack_mask": ([vp, i, i, vp, vp], i),
+    "apse_render_font_host": ([vp, sz], sz),
+    "apse_mots_split_workspace_bytes": ([], sz),
+    "apse_mots_split_idmap": ([vp, i, i, i, vp, sz, vp, vp, vp, vp, sz, vp], i),
+    "apse_mots_rle_to_bits": ([vp, vp, i, i, i, vp, vp], i),
+    "apse_mots_overlaps": ([vp, i, vp, i, vp, i, vp, vp], i),
+    "apse_mots_shift_overlaps": ([vp, i, vp, i, i, i, vp, vp], i),
+    "apse_mots_render_idmap": ([vp, vp, i, i, i, vp, vp], i),
+    "apse_mots_crop_overlaps": ([vp, vp, i, i, i, vp, sz, vp, vp, vp], i),
+    "apse_mots_rle_workspace_bytes": ([vp, i, i, i], sz),
+    "apse_mots_bits_to_rle": ([vp, vp, i, i, i, vp, i, vp, vp, vp, sz, vp], i),
+    "apse_mots_rle_pack_workspace_bytes": ([i], sz),
+    "apse_mots_rle_pack": ([vp, vp, i, i, vp, i, vp, vp, vp, sz, vp], i),
+    "apse_resize_normalize": ([vp, vp, vp, vp, vp, vp, i, vp, vp, i, i, i, i, i, i, i, i, C.POINTER(f * 3), vp], i),
+    "apse_assoc_fc_workspace_bytes": ([i, i, i], sz),
+    "apse_assoc_fc_forward": ([vp, vp, vp, i, i, i, vp, vp, vp, sz, vp], i),
+    "apse_assoc_fc_backward": ([vp, vp, vp, vp, i, i, i, vp, vp, vp, sz, vp], i),
+    "apse_triplet_workspace_bytes": ([i], sz),
+    "apse_triplet_hard_forward": ([vp, vp, i, i, f, i, vp, vp, sz, vp], i),
+    "apse_triplet_all_forward": ([vp, vp, i, i, f, i, vp, vp, sz, vp], i),
+    "apse_triplet_hard_backward": ([vp, i, i, i, vp, vp, vp, vp], i),
+    "apse_triplet_all_backward": ([vp, i, i, i, vp, vp, vp, vp], i),
+    "apse_sgd_step": ([vp, vp, vp, C.c_longlong, f, f, f, f, i, i, vp], i),
+    "apse_coco_box_iou": ([vp, vp, vp, i, i, i, vp, vp, vp, vp, vp], i),
+    "apse_coco_poly_to_bits": ([vp, vp, i, vp, i, vp, vp, vp, i, vp, vp, vp, vp], i),
+    "apse_coco_match": ([vp, vp, vp, i, i, i, vp, vp, vp, i, vp, vp, vp, i, vp, i, vp, i, vp, vp, vp, vp, vp], i),
+    "apse_coco_accumulate_workspace_bytes": ([C.c_longlong], sz),
+    "apse_coco_sort_lists": ([vp, vp, i, vp, C.c_longlong, i, vp, vp, sz, vp], i),
+    "apse_coco_accumulate": ([vp, vp, vp, i, vp, i, vp, vp, vp, C.c_longlong, i, vp, i, i, i, i, i, vp, vp, vp, vp, sz,
+                              vp], i),
+    "apse_mask_roi_features": ([vp, i, vp, i, vp, vp], i),
+    "apse_mask_train_workspace_bytes": ([i, i], sz),
+    "apse_mask_pack_elems": ([i, i, i, i], sz),
+    "apse_mask_pack_weight": ([vp, vp, i, i, i, i, i, vp, vp, vp], i),
+    "apse_mask_conv_forward": ([vp, vp, vp, i, i, i, i, i, i, i, i, i, i, i, vp, vp, sz, vp], i),
+    "apse_mask_conv3x3": ([vp, vp, vp, i, i, vp, vp], i),
+    "apse_mask_relu_grad": ([vp, vp, C.c_longlong, vp, vp], i),
+    "apse_mask_bias_grad": ([vp, C.c_longlong, vp, vp, sz, vp], i),
+    "apse_mask_wgrad": ([vp, vp, i, i, vp, vp, sz, vp], i),
+    "apse_mask_loss_forward": ([vp, i, vp, vp, i, vp, vp, sz, vp], i),
+    "apse_mask_loss_backward": ([vp, i, vp, vp, i, vp, vp, vp], i),
+    "apse_mask_predictor_backward": ([vp, vp, vp, vp, i, i, vp, vp, vp, vp, sz, vp], i),
+    "apse_augment_u8": ([vp, i, i, i, vp, vp, vp, vp, vp], i),
+}
+del vp, i, f, sz
+EXPORTS = list(SIGNATURES)
+
+
 _lib = None
 
 
@@ -93,111 +202,7 @@ def load():
     # on its own copy afterwards (build() followed by smoke() in one process).  torch first, always.
     import torch  # noqa: F401
     lib = C.CDLL(LIB_PATH)
-    vp, i, f, sz = C.c_void_p, C.c_int, C.c_float, C.c_size_t
-    sig = {
-        "apse_create": ([C.POINTER(Config), C.POINTER(vp)], i),
-        "apse_destroy": ([vp], None),
-        "apse_last_error": ([vp], C.c_char_p),
-        "apse_version": ([], C.c_char_p),
-        "apse_set_weight": ([vp, C.c_char_p, vp, C.POINTER(C.c_int64), i], i),
-        "apse_finalize_weights": ([vp], i),
-        "apse_set_resize_tables": ([vp, vp, vp, i, vp, vp, i], i),
-        "apse_set_camera": ([vp, C.POINTER(C.c_double), C.POINTER(C.c_double), i, vp, i, i], i),
-        "apse_preprocess_frames": ([vp, vp, i, vp], i),
-        "apse_preprocess_images": ([vp, vp, i, vp], i),
-        "apse_backbone": ([vp, i, vp], i),
-        "apse_rpn": ([vp, i, vp], i),
-        "apse_rpn_levels": ([vp, i, i, vp], i),
-        "apse_box_head": ([vp, i, vp], i),
-        "apse_set_detections": ([vp, vp, vp, vp, vp, i, vp], i),
-        "apse_mask_tail": ([vp, i, vp], i),
-        "apse_embed": ([vp, i, vp], i),
-        "apse_forward": ([vp, i, vp], i),
-        "apse_results_describe": ([vp, C.POINTER(ResultsLayout)], i),
-        "apse_read_results": ([vp, vp, sz, vp], i),
-        "apse_read_results_begin": ([vp, vp, sz, vp], i),
-        "apse_read_results_end": ([vp, vp], i),
-        "apse_lane_stats": ([vp, C.POINTER(C.c_longlong * 4)], i),
-        "apse_copy_mask_window": ([vp, i, i, i, i, i, vp, vp], i),
-        "apse_copy_mask_windows": ([vp, i, vp, vp, vp, vp, vp], i),
-        "apse_host_copy": ([vp, vp, sz, i], i),
-        "apse_feature_shape": ([vp, C.c_char_p, C.POINTER(C.c_int * 3)], i),
-        "apse_export_feature": ([vp, C.c_char_p, vp, i, vp], i),
-        "apse_debug_tensor": ([vp, C.c_char_p, vp, sz, C.POINTER(sz), vp], i),
-        "apse_flops": ([vp, i, C.c_double, C.c_double], C.c_double),
-        "apse_profile": ([vp, i], i),
-        "apse_profile_read": ([vp, C.POINTER(C.c_double * 42), i], i),
-        "apse_conv_packed_elems": ([C.POINTER(ConvDesc)], sz),
-        "apse_conv_pack_weight": ([C.POINTER(ConvDesc), vp, i, vp, vp], i),
-        "apse_conv2d": ([C.POINTER(ConvDesc), vp, vp, vp, vp, vp, vp, sz, vp], i),
-        "apse_winograd_pack_filter": ([vp, i, i, vp], i),
-        "apse_winograd_conv2d": ([C.POINTER(ConvDesc), vp, vp, vp, vp, vp], i),
-        "apse_maxpool3x3s2": ([vp, vp, i, i, i, i, vp], i),
-        "apse_maxpool3x3s2_typed": ([vp, vp, i, i, i, i, i, vp], i),
-        "apse_roi_align": ([C.POINTER(vp), C.POINTER(i), C.POINTER(i), vp, i, i, i, vp, vp], i),
-        "apse_roi_align_typed": ([C.POINTER(vp), C.POINTER(i), C.POINTER(i), vp, i, i, i, i, vp, vp], i),
-        "apse_roi_pool": ([vp, i, i, vp, vp, i, i, f, vp, vp], i),
-        "apse_roi_features": ([vp, i, vp, vp, i, i, vp, vp], i),
-        "apse_nms_rank": ([vp, vp, vp, i, i, i, i, f, i, vp, vp, vp, vp, vp], i),
-        "apse_mask_centroid_dense": ([vp, i, i, C.POINTER(C.c_int * 3), vp], i),
-        "apse_mask_closest_dense": ([vp, i, i, f, f, C.POINTER(C.c_int * 2), vp], i),
-        "apse_l2_normalize": ([vp, vp, i, i, vp], i),
-        "apse_sqdist": ([vp, vp, i, i, i, vp, vp], i),
-        "apse_undistort_gamma": ([vp, vp, i, i, i, C.POINTER(C.c_double), C.POINTER(C.c_double), i, vp, i, i, vp], i),
-        "apse_lab_tables_host": ([vp, vp, C.c_size_t], C.c_size_t),
-        "apse_replay_create": ([i, i, f, i], vp),
-        "apse_replay_destroy": ([vp], None),
-        "apse_replay_step": ([vp, i, i, vp, vp, vp, C.c_char_p, i, vp], i),
-        "apse_replay_packed": ([vp, vp, C.c_longlong, i, i, i, vp, C.c_longlong], C.c_longlong),
-        "apse_replay_max_id": ([vp], i),
-        "apse_replay_next_id": ([vp], i),
-        "apse_render_workspace_bytes": ([i, i, i], sz),
-        "apse_render_instances": ([vp, vp, i, i, i, i, vp, i, vp, sz, vp, i, vp, sz, vp], i),
-        "apse_render_pack_mask": ([vp, i, i, vp, vp], i),
-        "apse_render_font_host": ([vp, sz], sz),
-        "apse_mots_split_workspace_bytes": ([], sz),
-        "apse_mots_split_idmap": ([vp, i, i, i, vp, sz, vp, vp, vp, vp, sz, vp], i),
-        "apse_mots_rle_to_bits": ([vp, vp, i, i, i, vp, vp], i),
-        "apse_mots_overlaps": ([vp, i, vp, i, vp, i, vp, vp], i),
-        "apse_mots_shift_overlaps": ([vp, i, vp, i, i, i, vp, vp], i),
-        "apse_mots_render_idmap": ([vp, vp, i, i, i, vp, vp], i),
-        "apse_mots_crop_overlaps": ([vp, vp, i, i, i, vp, sz, vp, vp, vp], i),
-        "apse_mots_rle_workspace_bytes": ([vp, i, i, i], sz),
-        "apse_mots_bits_to_rle": ([vp, vp, i, i, i, vp, i, vp, vp, vp, sz, vp], i),
-        "apse_mots_rle_pack_workspace_bytes": ([i], sz),
-        "apse_mots_rle_pack": ([vp, vp, i, i, vp, i, vp, vp, vp, sz, vp], i),
-        "apse_resize_normalize": ([vp, vp, vp, vp, vp, vp, i, vp, vp, i, i, i, i, i, i, i, i, C.POINTER(f * 3), vp], i),
-        "apse_assoc_fc_workspace_bytes": ([i, i, i], sz),
-        "apse_assoc_fc_forward": ([vp, vp, vp, i, i, i, vp, vp, vp, sz, vp], i),
-        "apse_assoc_fc_backward": ([vp, vp, vp, vp, i, i, i, vp, vp, vp, sz, vp], i),
-        "apse_triplet_workspace_bytes": ([i], sz),
-        "apse_triplet_hard_forward": ([vp, vp, i, i, f, i, vp, vp, sz, vp], i),
-        "apse_triplet_all_forward": ([vp, vp, i, i, f, i, vp, vp, sz, vp], i),
-        "apse_triplet_hard_backward": ([vp, i, i, i, vp, vp, vp, vp], i),
-        "apse_triplet_all_backward": ([vp, i, i, i, vp, vp, vp, vp], i),
-        "apse_sgd_step": ([vp, vp, vp, C.c_longlong, f, f, f, f, i, i, vp], i),
-        "apse_coco_box_iou": ([vp, vp, vp, i, i, i, vp, vp, vp, vp, vp], i),
-        "apse_coco_poly_to_bits": ([vp, vp, i, vp, i, vp, vp, vp, i, vp, vp, vp, vp], i),
-        "apse_coco_match": ([vp, vp, vp, i, i, i, vp, vp, vp, i, vp, vp, vp, i, vp, i, vp, i, vp, vp, vp, vp, vp], i),
-        "apse_coco_accumulate_workspace_bytes": ([C.c_longlong], sz),
-        "apse_coco_sort_lists": ([vp, vp, i, vp, C.c_longlong, i, vp, vp, sz, vp], i),
-        "apse_coco_accumulate": ([vp, vp, vp, i, vp, i, vp, vp, vp, C.c_longlong, i, vp, i, i, i, i, i, vp, vp, vp, vp, sz,
-                                  vp], i),
-        "apse_mask_roi_features": ([vp, i, vp, i, vp, vp], i),
-        "apse_mask_train_workspace_bytes": ([i, i], sz),
-        "apse_mask_pack_elems": ([i, i, i, i], sz),
-        "apse_mask_pack_weight": ([vp, vp, i, i, i, i, i, vp, vp, vp], i),
-        "apse_mask_conv_forward": ([vp, vp, vp, i, i, i, i, i, i, i, i, i, i, i, vp, vp, sz, vp], i),
-        "apse_mask_conv3x3": ([vp, vp, vp, i, i, vp, vp], i),
-        "apse_mask_relu_grad": ([vp, vp, C.c_longlong, vp, vp], i),
-        "apse_mask_bias_grad": ([vp, C.c_longlong, vp, vp, sz, vp], i),
-        "apse_mask_wgrad": ([vp, vp, i, i, vp, vp, sz, vp], i),
-        "apse_mask_loss_forward": ([vp, i, vp, vp, i, vp, vp, sz, vp], i),
-        "apse_mask_loss_backward": ([vp, i, vp, vp, i, vp, vp, vp], i),
-        "apse_mask_predictor_backward": ([vp, vp, vp, vp, i, i, vp, vp, vp, vp, sz, vp], i),
-        "apse_augment_u8": ([vp, i, i, i, vp, vp, vp, vp, vp], i),
-    }
-    for name, (args, ret) in sig.items():
+    for name, (args, ret) in SIGNATURES.items():
         if name in TOOL_ENTRIES and LIB_PATH != _TREE_LIB and not hasattr(lib, name):
             continue                       # an older build loaded through APSE_HIP_LIB for an A/B run
         fn = getattr(lib, name)            # AttributeError here = ABI drift between header and library
@@ -205,27 +210,6 @@ def load():
         fn.restype = ret
     _lib = lib
     return lib
-
-
-EXPORTS = ["apse_create", "apse_destroy", "apse_last_error", "apse_version", "apse_set_weight", "apse_finalize_weights",
-           "apse_set_resize_tables", "apse_set_camera", "apse_preprocess_frames", "apse_preprocess_images", "apse_backbone", "apse_rpn", "apse_rpn_levels",
-           "apse_box_head", "apse_set_detections", "apse_mask_tail", "apse_embed", "apse_forward", "apse_results_describe",
-           "apse_read_results", "apse_read_results_begin", "apse_read_results_end", "apse_lane_stats", "apse_copy_mask_window", "apse_copy_mask_windows", "apse_host_copy", "apse_feature_shape", "apse_export_feature", "apse_debug_tensor",
-           "apse_flops", "apse_profile", "apse_profile_read", "apse_conv_packed_elems", "apse_conv_pack_weight", "apse_conv2d", "apse_winograd_pack_filter", "apse_winograd_conv2d", "apse_maxpool3x3s2",
-           "apse_maxpool3x3s2_typed", "apse_roi_align", "apse_roi_align_typed", "apse_roi_pool", "apse_roi_features", "apse_nms_rank", "apse_mask_centroid_dense", "apse_mask_closest_dense",
-           "apse_l2_normalize", "apse_sqdist", "apse_undistort_gamma", "apse_lab_tables_host", "apse_resize_normalize", "apse_replay_create", "apse_replay_destroy",
-           "apse_replay_step", "apse_replay_packed", "apse_replay_max_id", "apse_replay_next_id", "apse_render_workspace_bytes",
-           "apse_render_instances", "apse_render_pack_mask", "apse_render_font_host", "apse_mots_split_workspace_bytes",
-           "apse_mots_split_idmap", "apse_mots_rle_to_bits", "apse_mots_overlaps", "apse_mots_shift_overlaps", "apse_mots_render_idmap",
-           "apse_mots_crop_overlaps", "apse_mots_rle_workspace_bytes", "apse_mots_bits_to_rle",
-           "apse_mots_rle_pack_workspace_bytes", "apse_mots_rle_pack",
-           "apse_assoc_fc_workspace_bytes", "apse_assoc_fc_forward", "apse_assoc_fc_backward", "apse_triplet_workspace_bytes",
-           "apse_triplet_hard_forward", "apse_triplet_all_forward", "apse_triplet_hard_backward", "apse_triplet_all_backward",
-           "apse_sgd_step", "apse_coco_box_iou", "apse_coco_poly_to_bits", "apse_coco_match",
-           "apse_coco_accumulate_workspace_bytes", "apse_coco_sort_lists", "apse_coco_accumulate",
-           "apse_mask_roi_features", "apse_mask_train_workspace_bytes", "apse_mask_pack_elems", "apse_mask_pack_weight",
-           "apse_mask_conv_forward", "apse_mask_conv3x3", "apse_mask_relu_grad", "apse_mask_bias_grad", "apse_mask_wgrad", "apse_mask_loss_forward",
-           "apse_mask_loss_backward", "apse_mask_predictor_backward", "apse_augment_u8"]
 
 
 def stream_ptr():

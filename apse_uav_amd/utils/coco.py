@@ -23,12 +23,11 @@ import numpy as np
 import torch
 
 from .. import _lib
+from ..structures import device_windows as dw
 from ..structures.window_mask import WindowMask
 from . import mots_eval as me
 from . import rle as rlemod
 
-WIN_DTYPE = np.dtype([("rect", "<i4", (4,)), ("words_per_row", "<i4"), ("area", "<i4"), ("bits", "<u8")])
-assert WIN_DTYPE.itemsize == C.sizeof(_lib.MotsWindow)
 MAX_POLY_OBJECTS = 1 << 20
 _COORD_MAX = 2.0 ** 31 / 5.0 - 1.0
 
@@ -145,36 +144,19 @@ def poly_layout(objs):
     return dict(xy=xy, part_vert_off=part_vert_off, obj_part_off=obj_part_off, hw=hw, edge_off=edge_off, rects=rects)
 
 
-def _windows_for_rects(rects, dev):
-    """rects [n, 4] -> (window array [n] host, pool): one pooled buffer, windows pointing into it."""
-    n = len(rects)
-    rects = np.asarray(rects, np.int64).reshape(n, 4)
-    live = (rects[:, 2] > rects[:, 0]) & (rects[:, 3] > rects[:, 1])
-    wpr = np.where(live, ((rects[:, 2] + 63) >> 6) - (rects[:, 0] >> 6), 0)
-    words = wpr * np.where(live, rects[:, 3] - rects[:, 1], 0)
-    off = np.zeros(n + 1, np.int64)
-    np.cumsum(words, out=off[1:])
-    pool = torch.empty(max(int(off[-1]), 1), dtype=torch.int64, device=dev)
-    arr = np.zeros(n, WIN_DTYPE)
-    arr["rect"] = np.where(live[:, None], rects, 0)
-    arr["words_per_row"] = wpr
-    arr["bits"] = np.where(live, pool.data_ptr() + 8 * off[:-1], 0).astype(np.uint64)
-    return arr, pool
-
-
 def polygons_to_windows(objs, dev):
     """[(parts, h, w)] -> (windows uint8 [n, 32] on the device, buffers to keep alive).  Raises when the device's edge counts
     disagree with the host's (a bug, never data)."""
     lib = _lib.load()
     n = len(objs)
     if n == 0:
-        return torch.empty((0, WIN_DTYPE.itemsize), dtype=torch.uint8, device=dev), ()
+        return dw.no_windows(dev), ()
     if n > MAX_POLY_OBJECTS:
         parts = [polygons_to_windows(objs[i:i + MAX_POLY_OBJECTS], dev) for i in range(0, n, MAX_POLY_OBJECTS)]
         return torch.cat([p[0] for p in parts]), tuple(p[1] for p in parts)
     L = poly_layout(objs)
-    arr, pool = _windows_for_rects(L["rects"], dev)
-    windows = torch.from_numpy(arr.view(np.uint8).reshape(n, WIN_DTYPE.itemsize).copy()).to(dev)
+    arr, pool = dw.pooled_windows(L["rects"], dev)
+    windows = dw.upload(arr, dev)
     i32 = lambda a: torch.from_numpy(np.ascontiguousarray(a, np.int32)).to(dev)
     xy = torch.from_numpy(np.ascontiguousarray(L["xy"]).reshape(-1)).to(dev)
     pvo, opo, eo = i32(L["part_vert_off"]), i32(L["obj_part_off"]), i32(L["edge_off"])
@@ -192,30 +174,15 @@ def polygons_to_windows(objs, dev):
 
 def window_masks_to_windows(masks, dev):
     """WindowMask list -> (windows uint8 [n, 32] on the device, buffers to keep alive); the bits are used in place."""
-    n = len(masks)
-    arr = np.zeros(n, WIN_DTYPE)
-    keep = []
-    for k, m in enumerate(masks):
-        x0, y0, x1, y1 = m.rect
-        bits = m.bits
-        if bits is None or x1 <= x0 or y1 <= y0:
-            continue
-        bits = bits.to(dev).contiguous()
-        if bits.dim() != 2 or bits.shape[0] < y1 - y0:
-            raise ValueError("mask %d: %s bit words for a window of %d rows" % (k, tuple(bits.shape), y1 - y0))
-        arr[k]["rect"] = (x0, y0, x1, y1)
-        arr[k]["words_per_row"] = int(bits.shape[1])
-        arr[k]["bits"] = bits.data_ptr()
-        keep.append(bits)
-    windows = torch.from_numpy(arr.view(np.uint8).reshape(n, WIN_DTYPE.itemsize).copy()).to(dev)
-    return windows, keep
+    rects, wprs, ptrs, keep, _ = dw.masks_words(masks, None, dev)            # (no dense masks here: no frame size)
+    return dw.upload(dw.fill_windows(rects, wprs, ptrs), dev), keep
 
 
 def segm_to_windows(items, dev):
     """items: [(segmentation, h, w)] where h, w is the image size (used by polygons) -> (windows uint8 [n, 32] device, sizes
     [(h, w)], keep).  A segmentation is a polygon list, an RLE dict (compressed or plain counts) or a WindowMask."""
     n = len(items)
-    windows = torch.zeros((n, WIN_DTYPE.itemsize), dtype=torch.uint8, device=dev)
+    windows = torch.zeros((n, dw.STRUCT_BYTES), dtype=torch.uint8, device=dev)
     sizes = [None] * n
     keep = []
     polys, rles, wms = [], defaultdict(list), []
@@ -253,9 +220,9 @@ def windows_to_dense(windows, h, w):
     """Device windows -> host bool [n, h, w] (tests and ``annToMask``): each window drawn alone by ``apse_mots_render_idmap``
     (an apse_mots_object has the window's layout, with the score where the area is)."""
     lib = _lib.load()
-    arr = np.frombuffer(windows.cpu().numpy().tobytes(), WIN_DTYPE).copy()
-    arr["area"] = 0
-    objs = torch.from_numpy(arr.view(np.uint8).reshape(len(arr), WIN_DTYPE.itemsize).copy()).to(windows.device)
+    arr = dw.read_back(windows).view(dw.OBJ_DTYPE)
+    arr["score"] = 0
+    objs = dw.upload(arr, windows.device)
     out = np.zeros((len(arr), h, w), bool)
     idmap = torch.empty((h, w), dtype=torch.uint16, device=windows.device)
     one = (C.c_int * 1)(1)
@@ -429,7 +396,6 @@ class COCO:
 
     def annToMask(self, ann, device=None):
         t = self.imgs[ann["image_id"]]
-        dev = torch.device(device) if device is not None else torch.device("cuda", torch.cuda.current_device())
-        windows, sizes, keep = segm_to_windows([(ann["segmentation"], t["height"], t["width"])], dev)
+        windows, sizes, keep = segm_to_windows([(ann["segmentation"], t["height"], t["width"])], dw.default_device(device))
         h, w = sizes[0]
         return windows_to_dense(windows, h, w)[0].astype(np.uint8)

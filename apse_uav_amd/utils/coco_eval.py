@@ -23,6 +23,7 @@ import numpy as np
 import torch
 
 from .. import _lib
+from ..structures.device_windows import default_device
 from ..structures.window_mask import WindowMask
 from . import coco as cocomod
 from . import mots_eval as me
@@ -52,10 +53,6 @@ class Params:
             raise Exception("iouType not supported")
         self.iouType = iouType
         self.useSegm = None
-
-
-def _device(device=None):
-    return torch.device(device) if device is not None else torch.device("cuda", torch.cuda.current_device())
 
 
 def _to_dev(a, dtype, dev):
@@ -119,7 +116,7 @@ class COCOeval:
     def _run(self, gts, dts):
         """Groups on the host, IoU and matching on the device; the outputs stay there."""
         p = self.params
-        dev = _device(self.device)
+        dev = default_device(self.device)
         lib = _lib.load()
         I, K = len(p.imgIds), len(p.catIds)
         img_ix = {int(v): n for n, v in enumerate(p.imgIds)}
@@ -197,7 +194,7 @@ class COCOeval:
     def _mask_ious(self, gts, dts, gt_off, dt_off, iou_off, gt_crowd, n_pairs):
         """maskApi rleIou on the device windows: |a & b|, |a|, |b| by popcounts, IoU = i / (|a| + |b| - i) (i / |a| against
         crowd), 0 when i == 0, an f64 division of exact integers."""
-        dev = _device(self.device)
+        dev = default_device(self.device)
         out = np.zeros(n_pairs, np.float64)
         if n_pairs == 0:
             return out
@@ -308,7 +305,7 @@ class COCOeval:
                              "evaluate()'s; run evaluate() again")
         s = self._state
         lib = _lib.load()
-        dev = _device(self.device)
+        dev = default_device(self.device)
         T, R, K, A, M = len(p.iouThrs), len(p.recThrs), len(p.catIds), len(p.areaRng), len(p.maxDets)
         I = s["I"]
         keys = s["keys"]

@@ -20,6 +20,8 @@ import numpy as np
 import torch
 
 from .. import _lib
+from ..structures import device_windows as dw
+from ..structures.device_windows import MAX_PAIRS          # noqa: F401  (read and patched here by tests and tools)
 from ..structures.window_mask import WindowMask
 
 
@@ -55,10 +57,6 @@ def compute_closest_point(mask, the_point):
 
 
 # ---------------------------------------------------------------- mask IoU (mask_utils.py:41-77)
-MAX_PAIRS = 65536                      # APSE_MOTS_MAX_PAIRS
-_WIN_BYTES = C.sizeof(_lib.MotsWindow)
-
-
 def translate_and_crop_mask(mask, translation_vector):
     """Dense bool device tensor [H, W]: pixel (x, y) of ``mask`` lands on (x + int(dx), y + int(dy)); zero fill, cropped to the
     frame.  API compatibility (device slicing); the association uses the bit-window kernel instead."""
@@ -84,43 +82,17 @@ def _device_of(masks):
                 return m.bits.device
         elif m.is_cuda:
             return m.device
-    return torch.device("cuda", torch.cuda.current_device())
+    return dw.default_device()
 
 
-def _windows(masks, frame, dev):
+def frame_windows(masks, frame, dev):
     """Masks of one frame size -> (apse_mots_window array uint8 [n, 32] on the device, buffers it points into).  A WindowMask
-    is used in place; a dense device tensor is packed with apse_render_pack_mask (the whole frame is its window)."""
-    lib = _lib.load()
-    H, W = frame
-    rects, wprs, ptrs, keep = [], [], [], []
-    for k, m in enumerate(masks):
+    is used in place; a dense device tensor is packed (structures/device_windows.py).  Nothing is moved from the host."""
+    for m in masks:
         if _frame_size(m) != frame:
             raise ValueError("masks of different sizes: %s and %s" % (_frame_size(m), frame))
-        if isinstance(m, WindowMask):
-            rect, bits = m.rect, m.bits
-            if bits is not None:
-                if not bits.is_cuda:
-                    raise _lib.ApseError("mask_utils needs the mask on the GPU (no CPU fallback)")
-                bits = bits.contiguous()
-                if bits.dim() != 2 or bits.shape[0] < rect[3] - rect[1]:
-                    raise ValueError("mask %d: %s bit words for a window of %d rows" % (k, tuple(bits.shape), rect[3] - rect[1]))
-        else:
-            rect = (0, 0, W, H)
-            dense = _dense_u8(m)
-            bits = torch.empty((H, (W + 63) >> 6), dtype=torch.int64, device=dev)
-            _lib.check(lib.apse_render_pack_mask(_lib.ptr(dense), H, W, _lib.ptr(bits), _lib.stream_ptr()), None,
-                       "apse_render_pack_mask")
-            keep.append(dense)
-        rects.append(rect)
-        wprs.append(int(bits.shape[1]) if bits is not None else 0)
-        ptrs.append(bits.data_ptr() if bits is not None and bits.numel() else 0)
-        keep.append(bits)
-    # apse_mots_window: int rect[4], int words_per_row, int area, uint64_t* bits -- filled column by column, not struct by struct
-    host = np.zeros((len(masks), _WIN_BYTES // 4), np.int32)
-    host[:, 0:4] = np.asarray(rects, np.int32).reshape(-1, 4)
-    host[:, 4] = wprs
-    host.view(np.int64)[:, _lib.MotsWindow.bits.offset // 8] = ptrs
-    return torch.from_numpy(host.view(np.uint8)).to(dev), keep
+    rects, wprs, ptrs, *keep = dw.masks_words(masks, frame, dev, host_bits="refuse")
+    return dw.upload(dw.fill_windows(rects, wprs, ptrs), dev), keep
 
 
 def shift_overlaps(windows, quads, frame):
@@ -160,7 +132,7 @@ def masks_iou_matrix(det_masks, obj_masks, det_centroids=None):
         return iou
     frame = _frame_size(det_masks[0])
     dev = _device_of(det_masks + obj_masks)
-    windows, keep = _windows(det_masks + obj_masks, frame, dev)
+    windows, keep = frame_windows(det_masks + obj_masks, frame, dev)
     dc = list(det_centroids) if det_centroids is not None else [get_mask_centroid(m) for m in det_masks]
     oc = [get_mask_centroid(m) for m in obj_masks]
     # (dx, dy) = int(object centroid - detection centroid) for every pair; a nan (an empty mask on either side) leaves 0.0

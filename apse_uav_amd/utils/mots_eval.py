@@ -24,19 +24,14 @@ import torch
 from PIL import Image
 
 from .. import _lib
+from ..structures import device_windows as dw
+from ..structures.device_windows import MAX_OBJECTS, MAX_PAIRS          # noqa: F401  (tests and coco.py read them here)
 from ..structures.window_mask import WindowMask
 from . import mots_metrics as mm
 from . import rle
 from .mots_evaluation import _mots_class
 
-MAX_OBJECTS = 1024
-MAX_PAIRS = 65536
-_WIN_BYTES = C.sizeof(_lib.MotsWindow)
 _ws_cache = {}
-
-
-def _device(device=None):
-    return torch.device(device) if device is not None else torch.device("cuda", torch.cuda.current_device())
 
 
 def _workspace(dev):
@@ -44,13 +39,6 @@ def _workspace(dev):
     if key not in _ws_cache:
         _ws_cache[key] = torch.empty(_lib.load().apse_mots_split_workspace_bytes(), dtype=torch.uint8, device=dev)
     return _ws_cache[key]
-
-
-def _structs_to_device(arr, dev):
-    n = len(arr)
-    host = np.frombuffer(bytes(arr), dtype=np.uint8).reshape(n, C.sizeof(arr._type_)) if n else \
-        np.zeros((0, C.sizeof(arr._type_)), np.uint8)
-    return torch.from_numpy(host.copy()).to(dev)
 
 
 class FrameMasks:
@@ -74,10 +62,10 @@ def split_idmap(idmap, max_values=MAX_OBJECTS, pool_words=None):
     H, W = idmap.shape
     idmap = idmap.contiguous()
     values = torch.empty(max_values, dtype=torch.int32, device=dev)
-    windows = torch.empty((max_values, _WIN_BYTES), dtype=torch.uint8, device=dev)
+    windows = torch.empty((max_values, dw.STRUCT_BYTES), dtype=torch.uint8, device=dev)
     info = torch.empty(3, dtype=torch.int32, device=dev)
     ws = _workspace(dev)
-    words = pool_words if pool_words is not None else H * ((W + 63) >> 6)
+    words = pool_words if pool_words is not None else H * dw.words_per_row((0, 0, W, H))
     for _ in range(2):
         pool = torch.empty(max(int(words), 1), dtype=torch.int64, device=dev)
         _lib.check(lib.apse_mots_split_idmap(_lib.ptr(idmap), H, W, max_values, _lib.ptr(pool), pool.numel(), _lib.ptr(values),
@@ -121,7 +109,6 @@ def rle_masks(items, h, w, dev):
     if n > MAX_OBJECTS:
         raise ValueError("%d masks in one frame, more than %d" % (n, MAX_OBJECTS))
     rects, ends, offs = [], [], [0]
-    words = 0
     for counts in items:
         if sum(int(c) for c in counts) != h * w:
             raise ValueError("run lengths do not cover the %d x %d image" % (h, w))
@@ -130,18 +117,8 @@ def rle_masks(items, h, w, dev):
         e = np.cumsum(np.asarray(counts, np.int64))
         ends.append(e)
         offs.append(offs[-1] + len(e))
-        words += (r[3] - r[1]) * ((((r[2] + 63) >> 6) - (r[0] >> 6)) if r[2] > r[0] else 0)
-    pool = torch.empty(max(words, 1), dtype=torch.int64, device=dev)
-    arr = (_lib.MotsWindow * n)()
-    off = 0
-    for k, r in enumerate(rects):
-        wpr = (((r[2] + 63) >> 6) - (r[0] >> 6)) if r[2] > r[0] else 0
-        arr[k].rect[:] = list(r)
-        arr[k].words_per_row = wpr
-        arr[k].area = 0
-        arr[k].bits = pool.data_ptr() + 8 * off
-        off += (r[3] - r[1]) * wpr
-    windows = _structs_to_device(arr, dev)
+    arr, pool = dw.pooled_windows(rects, dev)
+    windows = dw.upload(arr, dev)
     ends_t = torch.from_numpy(np.concatenate(ends).astype(np.int32) if n else np.zeros(1, np.int32)).to(dev)
     offs_t = torch.from_numpy(np.asarray(offs, np.int32)).to(dev)
     _lib.check(lib.apse_mots_rle_to_bits(_lib.ptr(ends_t), _lib.ptr(offs_t), n, h, w, _lib.ptr(windows), _lib.stream_ptr()),
@@ -180,7 +157,6 @@ def check_idmap_values(items):
 
 def _object_structs(objects, image_size, dev):
     """ObjectInstances -> (apse_mots_object array on the device, host values, buffers to keep alive)."""
-    lib = _lib.load()
     n = len(objects)
     if n > MAX_OBJECTS:
         raise ValueError("%d objects in one frame, more than %d" % (n, MAX_OBJECTS))
@@ -188,44 +164,20 @@ def _object_structs(objects, image_size, dev):
     classes = [_mots_class(int(objects.pred_classes[k])) for k in range(n)]
     ids = [int(objects.ids[k]) for k in range(n)]
     scores = [float(objects.scores[k]) for k in range(n)]
-    arr = (_lib.MotsObject * n)()
-    keep = []
-    items = []
-    rank = {s: float(r) for r, s in enumerate(sorted(set(scores)))}   # exact order of the host's f64 comparisons
-    for k in range(n):
-        m = objects.pred_masks[k]
-        if isinstance(m, WindowMask):
-            rect = m.rect
-            bits = m.bits
-            if bits is not None:
-                bits = bits.to(dev).contiguous()
-            wpr = int(bits.shape[1]) if bits is not None and bits.dim() == 2 else 0
-            if bits is not None and rect[3] > rect[1] and (bits.dim() != 2 or bits.shape[0] < rect[3] - rect[1]):
-                raise ValueError("mask %d: %s bit words for a window of %d rows" % (k, tuple(bits.shape), rect[3] - rect[1]))
-        else:                                            # a dense mask: the whole frame is its window
-            dense = torch.as_tensor(m).to(dev).to(torch.uint8).contiguous()
-            rect = (0, 0, W, H)
-            wpr = (W + 63) >> 6
-            bits = torch.empty((H, wpr), dtype=torch.int64, device=dev)
-            _lib.check(lib.apse_render_pack_mask(_lib.ptr(dense), H, W, _lib.ptr(bits), _lib.stream_ptr()), None, "pack")
-            keep.append(dense)
-        nonempty = rect[2] > rect[0] and rect[3] > rect[1]
-        items.append((classes[k], ids[k], nonempty))
-        arr[k].rect[:] = list(rect)
-        arr[k].words_per_row = wpr
-        arr[k].score = rank[scores[k]]
-        arr[k].bits = bits.data_ptr() if bits is not None and bits.numel() else None
-        keep.append(bits)
+    rects, wprs, ptrs, *keep = dw.masks_words([objects.pred_masks[k] for k in range(n)], (H, W), dev)
+    items = [(classes[k], ids[k], rects[k][2] > rects[k][0] and rects[k][3] > rects[k][1]) for k in range(n)]
     check_idmap_values(items)
     values = [classes[k] * 1000 + ids[k] if classes[k] is not None and items[k][2] else 0 for k in range(n)]
-    return _structs_to_device(arr, dev), values, keep
+    rank = dw.score_ranks(scores)
+    arr = dw.fill_objects(rects, wprs, ptrs, [rank[v] for v in scores])
+    return dw.upload(arr, dev), values, keep
 
 
 def render_idmap(objects, image_size, device=None, out=None):
     """Device u16 [H, W] id map of ``objects`` (ObjectInstances), byte-identical to
     result_image_from_objects(crop_overlapping_masks(objects), image_size); the objects are not changed."""
     lib = _lib.load()
-    dev = _device(device)
+    dev = dw.default_device(device)
     H, W = (int(v) for v in image_size)
     objs, values, keep = _object_structs(objects, (H, W), dev)
     if out is None:
@@ -307,7 +259,7 @@ def _txt_frame(objs, dev):
         raise ValueError("masks of different sizes in one frame: %s" % sorted(sizes))
     h, w = sizes.pop() if sizes else (0, 0)
     if not objs:
-        return FrameMasks(torch.empty((0, _WIN_BYTES), dtype=torch.uint8, device=dev), [], [], None, None)
+        return FrameMasks(dw.no_windows(dev), [], [], None, None)
     windows, keep = rle_masks([o[4] for o in objs], h, w, dev)
     return FrameMasks(windows, [o[0] for o in objs], [o[1] for o in objs], (h, w), keep)
 
@@ -382,7 +334,7 @@ def _score(tables, max_frames, out):
 def evaluate_mots(results_dir, gt_dir, seqmap_path, out=print, device=None):
     """eval.py's run_eval on the GPU: {1: (per-sequence, all), 2: (...)} of utils/mots_metrics.MOTSResults (1 cars, 2
     pedestrians).  ``out`` receives the lines eval.py prints (None: silent)."""
-    dev = _device(device)
+    dev = dw.default_device(device)
     say = out if out is not None else (lambda s: None)
     seqs, max_frames = mm.load_seqmap(seqmap_path, out=out)
     say("Loading ground truth...")
@@ -408,7 +360,7 @@ class MotsEvaluator:
 
     def __init__(self, gt_dir, seqmap_path, device=None):
         self.gt_dir = gt_dir
-        self.device = _device(device)
+        self.device = dw.default_device(device)
         self.seqs, self.max_frames = mm.load_seqmap(seqmap_path, out=None)
         self.tables = OrderedDict()
         self._seq = None
@@ -466,4 +418,4 @@ def _pool_bound(objects, image_size):
         v = cls * 1000 + int(objects.ids[k])
         b = boxes.get(v)
         boxes[v] = rect if b is None else (min(b[0], rect[0]), min(b[1], rect[1]), max(b[2], rect[2]), max(b[3], rect[3]))
-    return sum((r[3] - r[1]) * (((r[2] + 63) >> 6) - (r[0] >> 6)) for r in boxes.values())
+    return sum((r[3] - r[1]) * dw.words_per_row(r) for r in boxes.values())

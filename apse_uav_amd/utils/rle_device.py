@@ -12,17 +12,13 @@ no dense frame is built on either side.
 Limits: frames as include/apse_hip.h; any number of masks (calls are cut at APSE_MOTS_MAX_OBJECTS).  There is no dense fallback:
 a mask that is no ``WindowMask`` is refused.
 """
-import ctypes as C
-
 import numpy as np
 import torch
 
 from .. import _lib
+from ..structures import device_windows as dw
+from ..structures.device_windows import MAX_OBJECTS, SEG_ROWS          # noqa: F401  (tests and tools read them here)
 from ..structures.window_mask import WindowMask
-
-MAX_OBJECTS = 1024                  # APSE_MOTS_MAX_OBJECTS      (tests/test_rle_ref.py holds both copies to the header)
-SEG_ROWS = 64                       # APSE_MOTS_RLE_SEG_ROWS
-_WIN_BYTES = C.sizeof(_lib.MotsWindow)
 
 
 def device_of(masks):
@@ -38,27 +34,8 @@ def device_of(masks):
             return None
         dev = m.bits.device
     if dev is None and torch.cuda.is_available():
-        dev = torch.device("cuda", torch.cuda.current_device())
+        dev = dw.default_device()
     return dev
-
-
-def _to_device(arr, n, dev):
-    host = np.frombuffer(bytes(arr), dtype=np.uint8).reshape(n, C.sizeof(arr._type_))
-    return torch.from_numpy(host.copy()).to(dev)
-
-
-def _mask_fields(m, k, dev):
-    """rect, words per row and the contiguous device words (or None) of one WindowMask."""
-    if not isinstance(m, WindowMask):
-        raise TypeError("mask %d is %s: the device writers take WindowMask only" % (k, type(m).__name__))
-    x0, y0, x1, y1 = m.rect
-    bits = m.bits
-    if bits is None or x1 <= x0 or y1 <= y0 or bits.numel() == 0:
-        return m.rect, (((x1 + 63) >> 6) - (x0 >> 6)) if x1 > x0 and y1 > y0 else 0, None
-    bits = bits.to(dev).contiguous()
-    if bits.dim() != 2 or bits.dtype != torch.int64 or bits.shape[0] < y1 - y0:
-        raise ValueError("mask %d: %s %s bit words for a window of %d rows" % (k, tuple(bits.shape), bits.dtype, y1 - y0))
-    return m.rect, int(bits.shape[1]), bits
 
 
 def _value_bytes(hw):
@@ -70,20 +47,20 @@ def _value_bytes(hw):
 
 
 def _encode_chunk(arr, windows, keep, n, h, w, compressed):
-    """One call's worth (n <= MAX_OBJECTS).  ``keep`` is not read: it holds the tensors the windows point into until the copy
-    back has synchronised."""
+    """One call's worth (n <= MAX_OBJECTS): the host windows ``arr`` (WIN_DTYPE) and their device copy.  ``keep`` is not read: it
+    holds the tensors the windows point into until the copy back has synchronised."""
     lib = _lib.load()
     dev = windows.device
-    ws_bytes = lib.apse_mots_rle_workspace_bytes(arr, n, h, w)
+    arr_ptr = _lib.ptr(arr)
+    ws_bytes = lib.apse_mots_rle_workspace_bytes(arr_ptr, n, h, w)
     if ws_bytes == 0:
         raise ValueError("a mask window leaves the %d x %d frame, or the frame is outside the library's limits" % (h, w))
     ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev)
     per_value = _value_bytes(h * w)
     cap = 1024                                               # blobs have a run or two per column: 8 ends per column is roomy
-    for k in range(n):
-        r = arr[k].rect
-        if r[2] > r[0] and r[3] > r[1]:
-            cap += 8 * (r[2] - r[0] + 1) + 2
+    for x0, y0, x1, y1 in arr["rect"].tolist():
+        if x1 > x0 and y1 > y0:
+            cap += 8 * (x1 - x0 + 1) + 2
     stream = _lib.stream_ptr()
     for _ in range(2):
         data_cap = cap * per_value if compressed else cap
@@ -97,8 +74,9 @@ def _encode_chunk(arr, windows, keep, n, h, w, compressed):
             ends_off = torch.empty(n + 1, dtype=torch.int32, device=dev)
         else:
             ends, ends_off = data, off
-        _lib.check(lib.apse_mots_bits_to_rle(_lib.ptr(windows), arr, n, h, w, _lib.ptr(ends), cap, _lib.ptr(ends_off),
-                                             _lib.ptr(info), _lib.ptr(ws), ws_bytes, stream), None, "apse_mots_bits_to_rle")
+        _lib.check(lib.apse_mots_bits_to_rle(_lib.ptr(windows), arr_ptr, n, h, w, _lib.ptr(ends), cap,
+                                             _lib.ptr(ends_off), _lib.ptr(info), _lib.ptr(ws), ws_bytes, stream), None,
+                   "apse_mots_bits_to_rle")
         if compressed:
             pws_bytes = lib.apse_mots_rle_pack_workspace_bytes(cap)
             pws = torch.empty(pws_bytes, dtype=torch.uint8, device=dev)
@@ -136,14 +114,14 @@ def encode_masks(masks, image_size, compressed=True, count=None):
         n = int(masks.shape[0]) if count is None else int(count)
         if n == 0:
             return res
-        if masks.dtype != torch.uint8 or masks.dim() != 2 or masks.shape[1] != _WIN_BYTES or masks.device.type != "cuda":
-            raise ValueError("a device window array is uint8 [n, %d] on a GPU" % _WIN_BYTES)
+        if masks.dtype != torch.uint8 or masks.dim() != 2 or masks.shape[1] != dw.STRUCT_BYTES or \
+                masks.device.type != "cuda":
+            raise ValueError("a device window array is uint8 [n, %d] on a GPU" % dw.STRUCT_BYTES)
         windows = masks[:n].contiguous()
-        host = windows.cpu().numpy()
+        host = dw.read_back(windows)
         for k0 in range(0, n, MAX_OBJECTS):
             m = min(MAX_OBJECTS, n - k0)
-            arr = (_lib.MotsWindow * m).from_buffer_copy(host[k0:k0 + m].tobytes())
-            res += _encode_chunk(arr, windows[k0:k0 + m], None, m, h, w, compressed)
+            res += _encode_chunk(host[k0:k0 + m], windows[k0:k0 + m], None, m, h, w, compressed)
         return res
     masks = list(masks)
     if not masks:
@@ -153,17 +131,9 @@ def encode_masks(masks, image_size, compressed=True, count=None):
         raise ValueError("encode_masks takes WindowMasks whose bits are on one GPU")
     for k0 in range(0, len(masks), MAX_OBJECTS):
         chunk = masks[k0:k0 + MAX_OBJECTS]
-        n = len(chunk)
-        arr = (_lib.MotsWindow * n)()
-        keep = []
-        for k, m in enumerate(chunk):
-            rect, wpr, bits = _mask_fields(m, k0 + k, dev)
-            arr[k].rect[:] = list(rect)
-            arr[k].words_per_row = wpr
-            arr[k].area = 0
-            arr[k].bits = bits.data_ptr() if bits is not None else None
-            keep.append(bits)
-        res += _encode_chunk(arr, _to_device(arr, n, dev), keep, n, h, w, compressed)
+        rects, wprs, ptrs, keep, _ = dw.masks_words(chunk, (h, w), dev, k0, windows_only=True)
+        arr = dw.fill_windows(rects, wprs, ptrs)
+        res += _encode_chunk(arr, dw.upload(arr, dev), keep, len(chunk), h, w, compressed)
     return res
 
 
@@ -183,41 +153,29 @@ def crop_overlaps(objects, with_changed=False):
     if dev is None:
         raise ValueError("crop_overlaps takes WindowMasks whose bits are on one GPU")
     H, W = (int(v) for v in masks[0].frame_size)
+    if any(tuple(m.frame_size) != (H, W) for m in masks):
+        raise ValueError("masks of different frame sizes in one frame")
+    rects, wprs, ptrs, keep, _ = dw.masks_words(masks, (H, W), dev, windows_only=True)
     scores = [float(objects.scores[k]) for k in range(n)]
-    rank = {s: float(r) for r, s in enumerate(sorted(set(scores)))}   # exact order of the host's f64 comparisons
-    arr = (_lib.MotsObject * n)()
-    keep, offs, shapes = [], [], []
-    words = 0
-    for k, m in enumerate(masks):
-        if tuple(m.frame_size) != (H, W):
-            raise ValueError("masks of different frame sizes in one frame")
-        rect, wpr, bits = _mask_fields(m, k, dev)
-        arr[k].rect[:] = list(rect)
-        arr[k].words_per_row = wpr
-        arr[k].score = rank[scores[k]]
-        arr[k].bits = bits.data_ptr() if bits is not None else None
-        keep.append(bits)
-        offs.append(words)
-        shapes.append((rect[3] - rect[1], wpr) if bits is not None else None)
-        if bits is not None:
-            words += (rect[3] - rect[1]) * wpr
+    rank = dw.score_ranks(scores)
+    arr = dw.fill_objects(rects, wprs, ptrs, [rank[s] for s in scores])
+    # an object without words gets no room in the pool: the kernel writes nothing for it
+    strides, offs, words = dw.pool_layout(rects, [wpr if bits is not None else 0 for wpr, bits in zip(wprs, keep)])
     pool = torch.empty(max(words, 1), dtype=torch.int64, device=dev)
-    off_t = torch.from_numpy(np.asarray(offs, np.int64)).to(dev)
+    objs, off_t = dw.upload(arr, dev), torch.from_numpy(offs[:-1]).to(dev)
     stats = torch.empty((n, 4), dtype=torch.int64, device=dev)
-    _lib.check(lib.apse_mots_crop_overlaps(_lib.ptr(_to_device(arr, n, dev)), arr, n, H, W, _lib.ptr(pool), words,
+    _lib.check(lib.apse_mots_crop_overlaps(_lib.ptr(objs), _lib.ptr(arr), n, H, W, _lib.ptr(pool), words,
                                            _lib.ptr(off_t), _lib.ptr(stats), _lib.stream_ptr()), None,
                "apse_mots_crop_overlaps")
     st = stats.cpu().numpy()
-    del keep
     out, changed = [], []
     for k, m in enumerate(masks):
-        if shapes[k] is None:
+        if keep[k] is None:
             out.append(WindowMask(None, m.rect, m.frame_size, (-1, -1), 0))
             changed.append(False)
             continue
         before, mass, sx, sy = (int(v) for v in st[k])
-        rows, wpr = shapes[k]
-        bits = pool[offs[k]:offs[k] + rows * wpr].view(rows, wpr)
+        bits = pool[offs[k]:offs[k + 1]].view(-1, int(strides[k]))
         out.append(WindowMask(bits, m.rect, m.frame_size, (sx // mass, sy // mass) if mass else (-1, -1), mass))
         changed.append(mass != before)
     return (out, changed) if with_changed else out

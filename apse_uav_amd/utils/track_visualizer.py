@@ -14,6 +14,7 @@ import numpy as np
 import torch
 
 from .. import _lib
+from ..structures import device_windows as dw
 
 MAX_ITEMS_PER_IMAGE = 100
 _GOLDEN = 0.6180339887498949
@@ -115,7 +116,7 @@ class TrackVisualizer:
             raise NotImplementedError("ColorMode.IMAGE_BW (grayscale background) is not implemented by the HIP renderer")
         self.metadata = metadata
         self._instance_mode = instance_mode
-        self.device = torch.device(device) if device is not None else torch.device("cuda", torch.cuda.current_device())
+        self.device = dw.default_device(device)
         self._uploader = None
         self._breaks = {}
 
@@ -202,35 +203,15 @@ class TrackVisualizer:
             it.label_off, it.label_len = off, len(text)
             labels.append(text)
             off += len(text)
-            bits, rect, wpr = self._mask_words(masks[k] if masks is not None else None, H, W)
-            if bits is not None:
+            if masks is None or masks[k] is None:
+                continue
+            rect, wpr, bits, _ = dw.mask_words(masks[k], k, (H, W), self.device, dense_hw_only=True)
+            if bits is not None:                             # an empty mask is left out: the item's bits stay NULL
                 keep.append(bits)
                 it.bits = bits.data_ptr()
                 it.rect[:] = list(rect)
                 it.words_per_row = wpr
         return items, labels, keep
-
-    def _mask_words(self, m, H, W):
-        """-> (int64 words on the device or None, rect, words per row) of one pred_masks entry."""
-        from ..structures.window_mask import WindowMask
-        if m is None:
-            return None, None, 0
-        if isinstance(m, WindowMask):
-            x0, y0, x1, y1 = m.rect
-            if m.bits is None or x1 <= x0 or y1 <= y0:
-                return None, None, 0
-            bits = m.bits.to(self.device).contiguous()
-            return bits, m.rect, int(bits.shape[1])
-        if not torch.is_tensor(m) or tuple(m.shape) != (H, W):
-            raise ValueError("pred_masks entries must be WindowMask or dense [H, W] bool tensors")
-        dense = m.to(self.device).contiguous()
-        if dense.dtype != torch.uint8:
-            dense = dense.to(torch.uint8) if dense.dtype != torch.bool else dense.view(torch.uint8)
-        wpr = (W + 63) >> 6
-        words = torch.empty((H, wpr), dtype=torch.int64, device=self.device)
-        _lib.check(_lib.load().apse_render_pack_mask(_lib.ptr(dense), H, W, _lib.ptr(words), _lib.stream_ptr()), None,
-                   "apse_render_pack_mask")
-        return words, (0, 0, W, H), wpr
 
 
 def visualize_tracks(frame_bgr, objects, visualizer):

@@ -63,11 +63,17 @@ def test_pack_words_round_trip():
 
 
 def test_python_limits_equal_the_header():
-    """utils/rle_device.py copies two header constants by hand, and the GPU tests size their cases from the copies."""
-    from apse_uav_amd.utils import mots_eval, rle_device
+    """structures/device_windows.py copies three header constants by hand, the GPU tests size their cases from them, and the
+    modules that used to hold copies of their own re-export the same objects."""
+    from apse_uav_amd.structures import device_windows as dw
+    from apse_uav_amd.utils import mask_utils, mots_eval, rle_device
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     with open(os.path.join(root, "include", "apse_hip.h")) as fh:
         text = fh.read()
     value = lambda name: int(re.search(r"#define %s (\d+)" % name, text).group(1))      # noqa: E731
-    assert rle_device.MAX_OBJECTS == mots_eval.MAX_OBJECTS == value("APSE_MOTS_MAX_OBJECTS")
-    assert rle_device.SEG_ROWS == value("APSE_MOTS_RLE_SEG_ROWS")
+    assert dw.MAX_OBJECTS == value("APSE_MOTS_MAX_OBJECTS")
+    assert dw.SEG_ROWS == value("APSE_MOTS_RLE_SEG_ROWS")
+    assert dw.MAX_PAIRS == value("APSE_MOTS_MAX_PAIRS")
+    assert rle_device.MAX_OBJECTS is dw.MAX_OBJECTS and mots_eval.MAX_OBJECTS is dw.MAX_OBJECTS
+    assert rle_device.SEG_ROWS is dw.SEG_ROWS
+    assert mask_utils.MAX_PAIRS is dw.MAX_PAIRS and mots_eval.MAX_PAIRS is dw.MAX_PAIRS

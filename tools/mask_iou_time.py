@@ -68,7 +68,7 @@ def main(argv=None):
             wall.append((time.perf_counter() - t0) * 1e3)
             call.append((e0, e1))
         # the launch alone: the same windows and pairs, resident on the device
-        windows, keep = mask_utils._windows(det + obj, (H, W), dev)
+        windows, keep = mask_utils.frame_windows(det + obj, (H, W), dev)
         quads = [(n, N + o, int(obj[o].centroid[0] - det[n].centroid[0]), int(obj[o].centroid[1] - det[n].centroid[1]))
                  for n in range(N) for o in range(O)]
         kernel = []
