@@ -180,6 +180,17 @@ SIGNATURES = {
     "apse_mask_loss_forward": ([vp, i, vp, vp, i, vp, vp, sz, vp], i),
     "apse_mask_loss_backward": ([vp, i, vp, vp, i, vp, vp, vp], i),
     "apse_mask_predictor_backward": ([vp, vp, vp, vp, i, i, vp, vp, vp, vp, sz, vp], i),
+    "apse_box_roi_features": ([vp, i, vp, i, vp, vp], i),
+    "apse_proposals": ([vp, i, vp, vp, vp], i),
+    "apse_box_train_workspace_bytes": ([i, i], sz),
+    "apse_box_match": ([vp, i, vp, vp, i, i, f, vp, vp, vp, vp], i),
+    "apse_box_permute_features": ([vp, i, vp, vp], i),
+    "apse_box_fc_forward": ([vp, vp, vp, i, i, i, i, vp, vp, sz, vp], i),
+    "apse_box_fc_dgrad": ([vp, vp, i, i, i, i, vp, vp], i),
+    "apse_box_fc_wgrad": ([vp, vp, i, i, i, vp, vp], i),
+    "apse_box_bias_grad": ([vp, i, i, vp, vp, sz, vp], i),
+    "apse_box_loss_forward": ([vp, vp, vp, vp, vp, i, i, C.POINTER(f * 4), f, vp, vp, sz, vp], i),
+    "apse_box_loss_backward": ([vp, vp, vp, vp, vp, i, i, C.POINTER(f * 4), f, vp, vp, vp, vp, vp], i),
     "apse_augment_u8": ([vp, i, i, i, vp, vp, vp, vp, vp], i),
 }
 del vp, i, f, sz

@@ -869,12 +869,13 @@ int apse_roi_features(apse_ctx* c, int image, const float* rois, const uint8_t* 
     return rc ? fail(c, rc, "masked roi_align launch failed") : APSE_OK;
 }
 
-int apse_mask_roi_features(apse_ctx* c, int image, const float* rois, int n, float* out, void* stream) {
+// ROIAlign R x R of n caller-given boxes over p2..p5 of one image: apse_mask_roi_features (R = 14) and apse_box_roi_features (R = 7)
+static int pyramid_roi_features(apse_ctx* c, int image, const float* rois, int n, int R, float* out, void* stream, const char* who) {
     if (!c || !c->finalized) return fail(c, APSE_E_STATE, "not finalized");
     const apse_config& g = c->cfg;
     if (image < 0 || image >= g.max_batch || n < 0 || n > (1 << 20) || (n > 0 && (!rois || !out)))
-        return fail(c, APSE_E_INVALID, "bad mask_roi_features arguments (image inside the batch, 0 <= n <= 2^20)");
-    if (c->c4) return fail(c, APSE_E_INVALID, "apse_mask_roi_features pools p2..p5: not available under C4 (arch 1)");
+        return fail(c, APSE_E_INVALID, std::string("bad ") + who + " arguments (image inside the batch, 0 <= n <= 2^20)");
+    if (c->c4) return fail(c, APSE_E_INVALID, std::string("apse_") + who + " pools p2..p5: not available under C4 (arch 1)");
     if (n == 0) return APSE_OK;
     hipStream_t s = (hipStream_t)stream;
     if ((size_t)n + 1 > c->mrf_cap) {
@@ -893,8 +894,31 @@ int apse_mask_roi_features(apse_ctx* c, int image, const float* rois, int n, flo
     if (rc) return rc;
     rc = apse_k_mask_roi_index(c->mrf_idx, n, s);
     if (rc) return fail(c, rc, "mask_roi_features index launch failed");
-    rc = apse_k_roi_align(&fm, rois, c->mrf_idx, nullptr, c->mrf_idx + n, 0, n, 14, out, 0, s);
-    return rc ? fail(c, rc, "roi_align(14) launch failed") : APSE_OK;
+    rc = apse_k_roi_align(&fm, rois, c->mrf_idx, nullptr, c->mrf_idx + n, 0, n, R, out, 0, s);
+    return rc ? fail(c, rc, R == 14 ? "roi_align(14) launch failed" : "roi_align(7) launch failed") : APSE_OK;
+}
+
+int apse_mask_roi_features(apse_ctx* c, int image, const float* rois, int n, float* out, void* stream) {
+    return pyramid_roi_features(c, image, rois, n, 14, out, stream, "mask_roi_features");
+}
+
+int apse_box_roi_features(apse_ctx* c, int image, const float* rois, int n, float* out, void* stream) {
+    return pyramid_roi_features(c, image, rois, n, 7, out, stream, "box_roi_features");
+}
+
+int apse_proposals(apse_ctx* c, int image, float* boxes, int* count, void* stream) {
+    if (!c || !c->finalized) return fail(c, APSE_E_STATE, "not finalized");
+    const apse_config& g = c->cfg;
+    if (image < 0 || image >= g.max_batch || !boxes || !count)
+        return fail(c, APSE_E_INVALID, "bad proposals arguments (image inside the batch, boxes and count not NULL)");
+    hipStream_t s = (hipStream_t)stream;
+    int rc = lane_join(c, s);          // the selection of apse_rpn runs on the tail lane
+    if (rc) return rc;
+    const int* propcnt = reinterpret_cast<const int*>(c->res + c->lay.prop_count);
+    HIPCHK(c, hipMemcpyAsync(boxes, c->props + (size_t)image * g.rpn_post_topk * 4, (size_t)g.rpn_post_topk * 4 * sizeof(float),
+                             hipMemcpyDeviceToDevice, s));
+    HIPCHK(c, hipMemcpyAsync(count, propcnt + image, sizeof(int), hipMemcpyDeviceToDevice, s));
+    return lane_follow(c, s);
 }
 
 int apse_debug_tensor(apse_ctx* c, const char* name, void* dst, size_t max_bytes, size_t* bytes, void* stream) {

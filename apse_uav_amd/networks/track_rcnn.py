@@ -396,6 +396,48 @@ class TrackRCNN:
         self._call("apse_mask_roi_features", int(image), _lib.ptr(b), b.shape[0], _lib.ptr(out), _lib.stream_ptr())
         return out
 
+    def box_roi_features(self, boxes, image=0):
+        """ROIAlign 7x7 of ``boxes`` ([n][4] x1,y1,x2,y2 in resized-image pixels, any n) over p2..p5 of image ``image`` of the last
+        ``apse_backbone`` run: f32 [n][7][7][256], the values the box branch pools for the same boxes (apse_box_roi_features;
+        FPN models only -- the box-head training input, networks/box_head.py)."""
+        if self.c4:
+            raise NotImplementedError("box_roi_features pools p2..p5: not available for C4 (Res5ROIHeads) models")
+        b = torch.as_tensor(boxes, dtype=torch.float32).reshape(-1, 4).to(self.device).contiguous()
+        out = torch.empty((b.shape[0], 7, 7, 256), dtype=torch.float32, device=self.device)
+        self._call("apse_box_roi_features", int(image), _lib.ptr(b), b.shape[0], _lib.ptr(out), _lib.stream_ptr())
+        return out
+
+    def rpn_proposals(self, frames=None, images=None, frame_hw=None):
+        """Preprocess (uint8 CUDA ``frames`` [B, H, W, 3], or already-resized f32 CHW ``images`` [B, 3, h, w] of frames of size
+        ``frame_hw``), run ``apse_backbone`` and ``apse_rpn`` only, and return per image the f32 device tensor [count][4] of the
+        context's proposals in resized-image pixels (apse_proposals; FPN models only).  The FPN maps stay in place for
+        ``box_roi_features``."""
+        if self.c4:
+            raise NotImplementedError("rpn_proposals feeds box-head training, which pools p2..p5: not available for C4 "
+                                      "(Res5ROIHeads) models")
+        if (frames is None) == (images is None):
+            raise ValueError("rpn_proposals takes frames or images (with frame_hw)")
+        B = self.backbone_frames(frames) if frames is not None else self.backbone_images(images, frame_hw)
+        return self.proposals_after_backbone(B)
+
+    def proposals_after_backbone(self, batch):
+        """``apse_rpn`` on the FPN maps of the last ``backbone_frames`` / ``backbone_images`` run of ``batch`` images, and its
+        proposals per image (see ``rpn_proposals``)."""
+        if self.c4:
+            raise NotImplementedError("rpn_proposals feeds box-head training, which pools p2..p5: not available for C4 "
+                                      "(Res5ROIHeads) models")
+        B = int(batch)
+        self._running_tag = None
+        s = _lib.stream_ptr()
+        self._call("apse_rpn", B, s)
+        post = int(self._cfg_c.rpn_post_topk)
+        boxes = torch.empty((B, post, 4), dtype=torch.float32, device=self.device)
+        counts = torch.empty(B, dtype=torch.int32, device=self.device)
+        for b in range(B):
+            self._call("apse_proposals", b, _lib.ptr(boxes[b]), C.c_void_p(counts[b:].data_ptr()), s)
+        host = counts.cpu()
+        return [boxes[b, :int(host[b])] for b in range(B)]
+
     def flops(self, batch, proposals, detections):
         return float(_lib.load().apse_flops(self._ctx, batch, proposals, detections))
 

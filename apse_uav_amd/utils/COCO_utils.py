@@ -195,12 +195,9 @@ class MaskTrainLoader:
         self.rng.bit_generator.state = sd["rng"]
         self._order = list(sd["order"])
 
-    def image_item(self, d, flipped=False):
-        """One image through the frozen backbone: (features, classes, targets) of its ground-truth boxes."""
+    def prepare_image(self, d, flipped=False):
+        """One image through the frozen backbone at the test size: (boxes f64 [G][4] in resized-image pixels, polygons, classes)."""
         from PIL import Image
-        key = d["image_id"]
-        if self.cache is not None and key in self.cache:
-            return self.cache[key]
         model = self.model
         frame = np.asarray(Image.open(d["file_name"]).convert("RGB"))[:, :, ::-1].copy()
         H, W = frame.shape[:2]
@@ -218,6 +215,15 @@ class MaskTrainLoader:
         boxes = boxes * np.array([sx, sy, sx, sy])
         polys = [[np.array(p, np.float64) * np.tile([sx, sy], len(p) // 2) for p in ps] for ps in polys]
         model.backbone_frames(torch.from_numpy(frame[None]).to(model.device))
+        return boxes, polys, classes
+
+    def image_item(self, d, flipped=False):
+        """One image through the frozen backbone: (features, classes, targets) of its ground-truth boxes."""
+        key = d["image_id"]
+        if self.cache is not None and key in self.cache:
+            return self.cache[key]
+        model = self.model
+        boxes, polys, classes = self.prepare_image(d, flipped)
         feats = model.mask_roi_features(boxes.astype(np.float32))
         targets = mask_targets(polys, boxes, model.device)
         item = (feats, classes, targets)
@@ -225,9 +231,9 @@ class MaskTrainLoader:
             self.cache[key] = item
         return item
 
-    def augmented_item(self, d, size, params):
+    def prepare_augmented(self, d, size, params):
         """One image down the device path: resized to short edge ``size``, augmented with ``params`` (utils.augment.AugmentParams),
-        through the frozen backbone: (features, classes, targets) of its transformed ground-truth boxes."""
+        through the frozen backbone: (transformed boxes f64 [G][4], polygons, classes)."""
         from PIL import Image
         from . import augment as aug
         model = self.model
@@ -244,8 +250,13 @@ class MaskTrainLoader:
         resized = aug.resize_frames(torch.from_numpy(frame[None]).to(model.device), ih, iw)
         _, chw, _ = aug.augment_images(resized, [params], want_u8=False)
         model.backbone_images(chw, (H, W))
-        feats = model.mask_roi_features(boxes.astype(np.float32))
-        return feats, classes, mask_targets(polys, boxes, model.device)
+        return boxes, polys, classes
+
+    def augmented_item(self, d, size, params):
+        """``prepare_augmented``, then (features, classes, targets) of the transformed ground-truth boxes."""
+        boxes, polys, classes = self.prepare_augmented(d, size, params)
+        feats = self.model.mask_roi_features(boxes.astype(np.float32))
+        return feats, classes, mask_targets(polys, boxes, self.model.device)
 
     def __iter__(self):
         return self

@@ -157,7 +157,7 @@ int apse_set_camera(apse_ctx* ctx, const double* m9, const double* dist, int ndi
  * the same bits.  What a caller must know:
  *   - synchronising `stream` does NOT wait for the heads of a forward that ran ahead: results are complete when apse_read_results(_end) returns,
  *     and every other entry that touches the context (apse_copy_mask_window(s), apse_export_feature, apse_debug_tensor,
- *     apse_roi_features, apse_mask_roi_features, apse_profile, apse_set_camera) first makes `stream` (or the host) wait for the lane;
+ *     apse_roi_features, apse_mask_roi_features, apse_box_roi_features, apse_proposals, apse_profile, apse_set_camera) first makes `stream` (or the host) wait for the lane;
  *   - use one `stream` per context for the calls of one forward.
  * The lane is off -- every launch on `stream`, in the order of the calls -- with apse_config.tail_lane < 0, APSE_TAIL_LANE=0,
  * under C4 and while apse_profile is enabled. */
@@ -631,6 +631,65 @@ int apse_mask_loss_backward(const float* logits_dev, int K, const int* classes_d
  * pre-activation), dw [K][256] and db [K] (classes without a RoI: exactly 0).  a5 = the deconvolution's output. */
 int apse_mask_predictor_backward(const float* d_dev, const float* a5_dev, const int* classes_dev, const float* w_pred_dev, int n, int K,
                                  float* g5_dev, float* dw_dev, float* db_dev, float* ws, size_t ws_bytes, void* stream);
+
+/* ---- Box-head training (csrc/box_train.hip): the f32 steps of fine-tuning roi_heads.box_head.fc1 / fc2 and
+ * roi_heads.box_predictor.cls_score / bbox_pred of a frozen FPN detector (dcnn/scripts/train/finetune_uav.py): proposal labelling,
+ * the FC layers forward and backward, FastRCNNOutputs.losses of detectron2 0.1.2 (loss_cls, loss_box_reg).  DESIGN.md "Box-head
+ * training" has the rules.  Apart from the two entries that read a context, every entry is stateless, enqueues on `stream` only
+ * and allocates nothing; the caller passes the workspace (apse_box_train_workspace_bytes covers every entry below).
+ * Deterministic: no float atomics, every sum has an order fixed by the shapes, max / argmax ties go to the lowest index.  Errors:
+ * APSE_E_INVALID outside the limits, checked before anything is launched, with the text in apse_last_error(NULL).  Limits:
+ * 1 <= n <= APSE_BOX_TRAIN_MAX_N sampled RoIs per call (the loss entries also take n = 0 and then enqueue nothing),
+ * 1 <= K <= APSE_MAX_CLASSES foreground classes, at most 4096 ground truths per image. */
+#define APSE_BOX_TRAIN_MAX_N 1024
+/* ROIAlignV2 7x7 (aligned, sampling ratio 0) of `n` boxes over p2..p5 of image `image`, detectron2's level assignment: the launch
+ * apse_box_head runs on its proposals, so for the context's own proposals the values equal the `box_pooled` tensor bit for bit.
+ * To be called after apse_backbone (FPN only).  rois_dev [n][4] x1,y1,x2,y2 in RESIZED-image pixels; out_dev f32 [n][7][7][256].
+ * 0 <= n <= 2^20. */
+int apse_box_roi_features(apse_ctx* ctx, int image, const float* rois_dev, int n, float* out_dev, void* stream);
+/* The proposals of the last apse_rpn run for image `image`: boxes_dev f32 [rpn_post_topk][4] in resized-image pixels (rows past
+ * the count are not meaningful) and count_dev (one int), both device side.  Joins the tail lane first. */
+int apse_proposals(apse_ctx* ctx, int image, float* boxes_dev, int* count_dev, void* stream);
+/* Workspace bytes for n RoIs and K classes (0 outside the limits). */
+size_t apse_box_train_workspace_bytes(int n, int K);
+/* pairwise_iou + Matcher([iou_thresh], [0, 1], allow_low_quality_matches = False) + the class assignment of
+ * ROIHeads._sample_proposals.  IoU = inter > 0 ? inter / (area_gt + area_proposal - inter) : 0 in f32.  Per proposal: the ground
+ * truth of highest IoU (lowest index on ties) -> matched_idx, matched_iou; labels = that ground truth's class when
+ * IoU >= iou_thresh, else K (background).  G = 0: every label K, index 0, IoU 0.  0 <= N <= 2^20, 0 <= G <= 4096. */
+int apse_box_match(const float* proposals_dev, int N, const float* gt_boxes_dev, const int* gt_classes_dev, int G, int K,
+                   float iou_thresh, int* matched_idx_dev, float* matched_iou_dev, int* labels_dev, void* stream);
+/* out [n][12544] = x [n][7][7][256] with every row reordered from (h, w, c) to fc1's (c, h, w): done once per step, so that the
+ * GEMM entries below read and write roi_heads.box_head.fc1.weight in the checkpoint's own layout.  Not in place. */
+int apse_box_permute_features(const float* x_dev, int n, float* out_dev, void* stream);
+/* The FC layers on the exact-f32 MFMA (v_mfma_f32_32x32x2_f32), 128 x 128 output tiles that own their outputs over the whole
+ * reduction (the gradients need no split), the reduction summed in chains of 64; rows and columns outside the shapes are masked at the loads.
+ * x [n][K], w [O][K] (the checkpoint tensor), dy / y [n][O]; 1 <= O <= 1024, 1 <= K <= 16384.
+ *   forward: y = x w^T + bias (bias may be NULL) (+ ReLU); a layer with K >= 4096 (fc1) runs as 8 chunks of the reduction whose
+ *            sums (8 n O floats of workspace) a second kernel adds in chunk order -- the rule reads K only, so a row of y does
+ *            not depend on n
+ *   dgrad:   dx [n][K] = dy w, added to the dx already there when accumulate != 0
+ *   wgrad:   dw [O][K] = sum over the rows m = 0 .. n - 1 of dy[m][o] x[m][k] */
+int apse_box_fc_forward(const float* x_dev, const float* w_dev, const float* bias_dev, int n, int O, int K, int relu, float* y_dev,
+                        float* ws, size_t ws_bytes, void* stream);
+int apse_box_fc_dgrad(const float* dy_dev, const float* w_dev, int n, int O, int K, int accumulate, float* dx_dev, void* stream);
+int apse_box_fc_wgrad(const float* dy_dev, const float* x_dev, int n, int O, int K, float* dw_dev, void* stream);
+/* db [O] = column sums of dy [n][O]: rows in ascending order inside slices of 64 rows, slices in ascending order, summed in
+ * f64 and rounded once. */
+int apse_box_bias_grad(const float* dy_dev, int n, int O, float* db_dev, void* ws, size_t ws_bytes, void* stream);
+/* FastRCNNOutputs.losses: logits [n][K + 1], deltas [n][4 K], labels [n] (K = background), the sampled boxes and their matched
+ * ground-truth boxes [n][4]; weights4 (HOST, read before the call returns) = the Box2BoxTransform weights, (10, 10, 5, 5).
+ * loss_cls = mean cross-entropy over the n rows; loss_box_reg = smooth_l1 (beta < 1e-5: L1) on the four columns of the label's
+ * class of the foreground rows, summed and divided by n.
+ * out8 = {loss_cls, loss_box_reg, cls_accuracy, fg_cls_accuracy, false_negative, num_fg, num_bg, 0}. */
+int apse_box_loss_forward(const float* logits_dev, const float* deltas_dev, const int* labels_dev, const float* prop_boxes_dev,
+                          const float* gt_boxes_dev, int n, int K, const float* weights4, float smooth_l1_beta, float* out8_dev,
+                          void* ws, size_t ws_bytes, void* stream);
+/* dlogits [n][K + 1] = (softmax - onehot) / n x grad_cls[0]; ddeltas [n][4 K] = d smooth_l1 / n x grad_box[0] on the four columns
+ * of the foreground rows and exactly 0 elsewhere.  grad_cls / grad_box: device scalars (NULL: 1). */
+int apse_box_loss_backward(const float* logits_dev, const float* deltas_dev, const int* labels_dev, const float* prop_boxes_dev,
+                           const float* gt_boxes_dev, int n, int K, const float* weights4, float smooth_l1_beta,
+                           const float* grad_cls_dev, const float* grad_box_dev, float* dlogits_dev, float* ddeltas_dev,
+                           void* stream);
 
 /* ---- Training augmentation (csrc/augment.hip): the transforms the reference's DatasetMapper applies after ResizeShortestEdge
  * (dcnn/utils/UAV_utils.py:311-449) -- RandomFlip, RandomBrightness, RandomSaturation, RandomContrast, RandomLighting of
