@@ -16,8 +16,10 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 # default is the in-tree library
 _TREE_LIB = os.path.join(_HERE, "libapse_hip.so")
 LIB_PATH = os.environ.get("APSE_HIP_LIB") or _TREE_LIB
-# entries that only tools/ use: a build from before they existed may still be loaded through APSE_HIP_LIB (load())
-TOOL_ENTRIES = ("apse_winograd_pack_filter", "apse_winograd_conv2d", "apse_lane_stats")
+# entries that only tools/ and the operator tests use: a build from before they existed may still be loaded through
+# APSE_HIP_LIB (load())
+TOOL_ENTRIES = ("apse_winograd_pack_filter", "apse_winograd_conv2d", "apse_lane_stats", "apse_rpn_select", "apse_box_inference",
+                "apse_c4_rpn_select")
 
 APSE_OK = 0
 
@@ -124,6 +126,9 @@ SIGNATURES = {
     "apse_roi_pool": ([vp, i, i, vp, vp, i, i, f, vp, vp], i),
     "apse_roi_features": ([vp, i, vp, vp, i, i, vp, vp], i),
     "apse_nms_rank": ([vp, vp, vp, i, i, i, i, f, i, vp, vp, vp, vp, vp], i),
+    "apse_rpn_select": ([C.POINTER(vp), C.POINTER(i), C.POINTER(i), i, i, i, i, i, i, f, i, vp, vp, vp, vp, vp, vp, vp, vp, vp], i),
+    "apse_box_inference": ([vp, i, i, vp, vp, i, i, i, i, f, f, i, i] + [vp] * 16, i),
+    "apse_c4_rpn_select": ([vp, i, i, i, i, i, i, i, f, vp, vp, vp, vp, vp, vp, vp, vp], i),
     "apse_mask_centroid_dense": ([vp, i, i, C.POINTER(C.c_int * 3), vp], i),
     "apse_mask_closest_dense": ([vp, i, i, f, f, C.POINTER(C.c_int * 2), vp], i),
     "apse_l2_normalize": ([vp, vp, i, i, vp], i),

@@ -105,7 +105,7 @@ int apse_k_rpn_decode(const RpnLevels* L_dev, int pre_topk, const uint64_t* list
                       int level_mask, int B, hipStream_t s);
 size_t apse_nms_scratch_bytes(int slots);
 int apse_k_nms_percat(const float* boxes, const float* scores, const int* valid, int n_total, int cat_div, int cat_mod,
-                      const uint32_t* maxc, float thr, int* keep_idx, int* keep_cnt, int ncat, void* scratch, int cat_shift,
+                      const uint32_t* maxc, float thr, int* keep_idx, int* keep_cnt, int ncat, void* scratch, int cat_mask,
                       int B, int presorted, hipStream_t s);
 int apse_k_rank_final(const float* boxes, const float* scores, int n_total, const int* keep_idx, const int* keep_cnt,
                       int ncat, int K, float* out_boxes, float* out_scores, int* out_entry, int* out_count,

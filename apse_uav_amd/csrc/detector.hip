@@ -408,8 +408,6 @@ int apse_rpn_levels(apse_ctx* c, int batch, int level_mask, void* stream) {
     NEED_READY(c, batch);
     level_mask &= 31;
     if (!level_mask) return fail(c, APSE_E_INVALID, "empty RPN level mask");
-    int first_level = 0;
-    while (!((level_mask >> first_level) & 1)) ++first_level;
     hipStream_t s = (hipStream_t)stream;
     const apse_config& g = c->cfg;
     if (c->c4 && level_mask != 31) return fail(c, APSE_E_INVALID, "C4 (arch 1) has one RPN level: level_mask must be 31");
@@ -442,7 +440,7 @@ int apse_rpn_levels(apse_ctx* c, int batch, int level_mask, void* stream) {
                            (float)log(1000.0 / 16.0), c->dec_boxes, c->dec_scores, c->dec_valid, c->maxc, level_mask, batch, s);
     if (rc) return fail(c, rc, "rpn decode launch failed");
     rc = apse_k_nms_percat(c->dec_boxes, c->dec_scores, c->dec_valid, 5 * g.rpn_pre_topk, g.rpn_pre_topk, 0, c->maxc, g.rpn_nms,
-                           c->keep_idx, c->keep_cnt, 5, c->nms_scratch, first_level, batch, 1, s);
+                           c->keep_idx, c->keep_cnt, 5, c->nms_scratch, level_mask, batch, 1, s);
     if (rc) return fail(c, rc, "rpn nms launch failed");
     int* propcnt = reinterpret_cast<int*>(c->res + c->lay.prop_count);
     rc = apse_k_rank_final(c->dec_boxes, c->dec_scores, 5 * g.rpn_pre_topk, c->keep_idx, c->keep_cnt, 5, g.rpn_post_topk, c->props,

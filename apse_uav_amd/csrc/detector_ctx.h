@@ -143,6 +143,18 @@ static inline int pow2_at_least(int v) { int p = 4; while (p < v) p <<= 1; retur
 // plan.hip
 void pack_oihw(const float* w, int Cout, int Cin, int KH, int KW, int cin_p, const float* scale, float* out, int KWCp);
 std::vector<float> winograd_filters(const float* oihw, int Cout, int Cin, int cin_p);
+// The FPN RPN selection plan: the five levels (head rows, cell anchors, k), the top-k tournament (4096-key sort jobs, then
+// merges of up to four lists per job until one list per level is left), the number of 1024-key list slots and each level's
+// final slot.  The context (build_plan) and the stateless apse_rpn_select both run the plan this function makes.
+struct RpnSelectPlan {
+    RpnLevels levels;
+    std::vector<std::vector<TopkJob>> stages;
+    int nslots;
+    int final_slot[5];
+};
+void rpn_select_plan(const float* const head[5], const int H[5], const int W[5], int head_ld, int pre_topk, RpnSelectPlan* out);
+// The C4 RPN descriptor: head rows, the 15 cell anchors (sizes outer, ratios inner), n and k
+void c4_rpn_desc(const float* head, int H, int W, int ld, int pre_topk, C4Rpn* R);
 int build_plan(apse_ctx* c);        // FPN (cfg.arch 0)
 int build_plan_c4(apse_ctx* c);     // C4 (cfg.arch 1)
 // detector.hip (apse_set_camera)

@@ -2,11 +2,25 @@
 // tests and tools.  None of them touches a context; of the host code they share the weight packing (plan.hip) and fill_camera.
 #include "detector_ctx.h"
 
+#include <math.h>
 #include <string.h>
 
 #include <map>
 #include <mutex>
 #include <vector>
+
+namespace {
+struct DevBuf {                      // device scratch of one call
+    void* p = nullptr;
+    ~DevBuf() { if (p) hipFree(p); }
+    bool alloc(size_t bytes, bool zero = false) {
+        if (hipMalloc(&p, bytes ? bytes : 16) != hipSuccess) { p = nullptr; return false; }
+        if (zero) hipMemset(p, 0, bytes ? bytes : 16);
+        return true;
+    }
+    template <typename T> T* as() const { return reinterpret_cast<T*>(p); }
+};
+}  // namespace
 
 extern "C" {
 
@@ -176,6 +190,134 @@ int apse_nms_rank(const float* boxes, const float* scores, const int* valid, int
     if (!rc) rc = apse_k_rank_final(boxes, scores, n, keep_idx, keep_cnt, ncat, topk, out_boxes, out_scores, out_index, out_count, nullptr, 1, s);
     hipStreamSynchronize(s);
     hipFree(keep_idx); hipFree(keep_cnt); hipFree(maxc); hipFree(scratch);
+    return rc;
+}
+
+// ---- the decision kernels on injected inputs: the launchers of apse_rpn_levels / apse_box_head, in their order, on scratch of
+// this call (select_nms.hip).  Test / tool entries: every call allocates, synchronises and frees.
+int apse_rpn_select(const float* const* heads_dev, const int* H, const int* W, int head_ld, int B, int image_h, int image_w,
+                    int pre_topk, int post_topk, float nms_thr, int level_mask, unsigned long long* keys_dev, float* dec_boxes_dev,
+                    float* dec_scores_dev, int* dec_valid_dev, float* props_dev, float* prop_scores_dev, int* prop_entry_dev,
+                    int* prop_count_dev, void* stream) {
+    if (!heads_dev || !H || !W || !dec_boxes_dev || !dec_scores_dev || !dec_valid_dev || !props_dev || !prop_scores_dev ||
+        !prop_entry_dev || !prop_count_dev)
+        return APSE_E_INVALID;
+    level_mask &= 31;
+    if (!level_mask || B < 1 || B > 64 || head_ld < 15 || pre_topk < 1 || pre_topk > 1000 || post_topk < 1) return APSE_E_INVALID;
+    for (int l = 0; l < 5; ++l)
+        if (!heads_dev[l] || H[l] < 1 || W[l] < 1 || (long long)H[l] * W[l] * 3 > (1ll << 30)) return APSE_E_INVALID;
+    hipStream_t s = (hipStream_t)stream;
+    RpnSelectPlan sel;
+    rpn_select_plan(heads_dev, H, W, head_ld, pre_topk, &sel);
+    DevBuf rl, fs, lists, maxc, keep_idx, keep_cnt, scratch;
+    std::vector<DevBuf> stage_dev(sel.stages.size());
+    if (!rl.alloc(sizeof(RpnLevels)) || !fs.alloc(5 * sizeof(int)) || !lists.alloc((size_t)B * sel.nslots * 1024 * 8) ||
+        !maxc.alloc((size_t)2 * B * 4, true) || !keep_idx.alloc((size_t)B * 8 * APSE_NMS_SLOT * 4) ||
+        !keep_cnt.alloc((size_t)B * 8 * 4, true) || !scratch.alloc(apse_nms_scratch_bytes(8 * B)))
+        return APSE_E_NOMEM;
+    hipMemcpy(rl.p, &sel.levels, sizeof(RpnLevels), hipMemcpyHostToDevice);
+    hipMemcpy(fs.p, sel.final_slot, 5 * sizeof(int), hipMemcpyHostToDevice);
+    for (size_t i = 0; i < sel.stages.size(); ++i) {
+        if (!stage_dev[i].alloc(sel.stages[i].size() * sizeof(TopkJob))) return APSE_E_NOMEM;
+        hipMemcpy(stage_dev[i].p, sel.stages[i].data(), sel.stages[i].size() * sizeof(TopkJob), hipMemcpyHostToDevice);
+    }
+    const float clamp = (float)log(1000.0 / 16.0);
+    int rc = APSE_OK;
+    for (size_t i = 0; i < sel.stages.size() && !rc; ++i)
+        rc = apse_k_rpn_topk_stage(rl.as<RpnLevels>(), stage_dev[i].as<TopkJob>(), (int)sel.stages[i].size(), lists.as<uint64_t>(),
+                                   sel.nslots, B, i == 0 ? maxc.as<uint32_t>() : nullptr, s);
+    if (!rc) rc = apse_k_rpn_decode(rl.as<RpnLevels>(), pre_topk, lists.as<uint64_t>(), sel.nslots, fs.as<int>(), (float)image_h,
+                                    (float)image_w, clamp, dec_boxes_dev, dec_scores_dev, dec_valid_dev, maxc.as<uint32_t>(),
+                                    level_mask, B, s);
+    if (!rc) rc = apse_k_nms_percat(dec_boxes_dev, dec_scores_dev, dec_valid_dev, 5 * pre_topk, pre_topk, 0, maxc.as<uint32_t>(),
+                                    nms_thr, keep_idx.as<int>(), keep_cnt.as<int>(), 5, scratch.p, level_mask, B, 1, s);
+    if (!rc) rc = apse_k_rank_final(dec_boxes_dev, dec_scores_dev, 5 * pre_topk, keep_idx.as<int>(), keep_cnt.as<int>(), 5, post_topk,
+                                    props_dev, prop_scores_dev, prop_entry_dev, prop_count_dev, maxc.as<uint32_t>() + B, B, s);
+    if (!rc && keys_dev) {
+        hipMemsetAsync(keys_dev, 0xff, (size_t)B * 5 * pre_topk * 8, s);
+        for (int b = 0; b < B; ++b)
+            for (int l = 0; l < 5; ++l)
+                hipMemcpyAsync(keys_dev + ((size_t)b * 5 + l) * pre_topk,
+                               lists.as<uint64_t>() + ((size_t)b * sel.nslots + sel.final_slot[l]) * 1024,
+                               (size_t)sel.levels.lv[l].k * 8, hipMemcpyDeviceToDevice, s);
+    }
+    if (hipStreamSynchronize(s) != hipSuccess && !rc) rc = APSE_E_HIP;
+    return rc;
+}
+
+int apse_box_inference(const float* pred_dev, int ld, int K, const float* props_dev, const int* prop_cnt_dev, int P, int B,
+                       int image_h, int image_w, float score_thresh, float nms_thr, int dets_per_image, int wide,
+                       float* probs_dev, float* cand_boxes_dev, float* cand_scores_dev, int* cand_valid_dev, float* det_boxes_dev,
+                       float* det_scores_dev, int* det_entry_dev, int* det_cnt_dev, float* pk_boxes_dev, float* pk_scores_dev,
+                       int* pk_cls_dev, int* pk_img_dev, int* pk_roi_dev, int* pk_total_dev, int* pk_offset_dev, void* stream) {
+    if (!pred_dev || !props_dev || !prop_cnt_dev || !probs_dev || !cand_boxes_dev || !cand_scores_dev || !cand_valid_dev ||
+        !det_boxes_dev || !det_scores_dev || !det_entry_dev || !det_cnt_dev || !pk_boxes_dev || !pk_scores_dev || !pk_cls_dev ||
+        !pk_img_dev || !pk_roi_dev || !pk_total_dev || !pk_offset_dev)
+        return APSE_E_INVALID;
+    if (K < 1 || K > 127 || (!wide && K > 7) || ld < 5 * K + 1 || P < 1 || P > APSE_NMS_SLOT || B < 1 || B > 64 ||
+        dets_per_image < 1)
+        return APSE_E_INVALID;
+    hipStream_t s = (hipStream_t)stream;
+    const int KD = dets_per_image, ncat = K > 8 ? K : 8;
+    DevBuf maxc, keep_idx, keep_cnt, scratch, sums, clist;
+    if (!maxc.alloc((size_t)B * 4) || !keep_idx.alloc((size_t)B * ncat * APSE_NMS_SLOT * 4) || !keep_cnt.alloc((size_t)B * ncat * 4, true) ||
+        !scratch.alloc(apse_nms_scratch_bytes(ncat * B)) || !sums.alloc((size_t)B * KD * 3 * 8))
+        return APSE_E_NOMEM;
+    // the class counts live across calls, as a context's do: zero when allocated, and nms_prepare_list leaves them zero
+    static int* ccnt = nullptr;
+    static size_t ccnt_cap = 0;
+    if (wide) {
+        if (!clist.alloc((size_t)B * K * P * 4)) return APSE_E_NOMEM;
+        if ((size_t)B * K > ccnt_cap) {
+            hipDeviceSynchronize();
+            if (ccnt) hipFree(ccnt);
+            ccnt = nullptr; ccnt_cap = 0;
+            if (hipMalloc(reinterpret_cast<void**>(&ccnt), (size_t)B * K * 4) != hipSuccess) return APSE_E_NOMEM;
+            hipMemset(ccnt, 0, (size_t)B * K * 4);
+            ccnt_cap = (size_t)B * K;
+        }
+    }
+    const float wts[4] = {10.f, 10.f, 5.f, 5.f};
+    const float clamp = (float)log(1000.0 / 16.0);
+    hipMemsetAsync(maxc.p, 0, sizeof(uint32_t) * B, s);
+    int rc;
+    if (wide) {
+        rc = apse_k_box_candidates_wide(pred_dev, ld, K, props_dev, prop_cnt_dev, P, (float)image_h, (float)image_w, score_thresh, wts,
+                                        clamp, cand_boxes_dev, cand_scores_dev, cand_valid_dev, maxc.as<uint32_t>(), probs_dev,
+                                        clist.as<int>(), ccnt, B, s);
+        if (!rc) rc = apse_k_nms_lists(cand_boxes_dev, cand_scores_dev, P * K, clist.as<int>(), ccnt, P, maxc.as<uint32_t>(), nms_thr,
+                                       keep_idx.as<int>(), keep_cnt.as<int>(), K, scratch.p, B, s);
+        if (!rc) rc = apse_k_rank_wide(cand_boxes_dev, cand_scores_dev, P * K, keep_idx.as<int>(), keep_cnt.as<int>(), K, KD,
+                                       det_boxes_dev, det_scores_dev, det_entry_dev, det_cnt_dev, B, s);
+    } else {
+        rc = apse_k_box_candidates(pred_dev, ld, K, props_dev, prop_cnt_dev, P, (float)image_h, (float)image_w, score_thresh, wts, clamp,
+                                   cand_boxes_dev, cand_scores_dev, cand_valid_dev, maxc.as<uint32_t>(), probs_dev, B, s);
+        if (!rc) rc = apse_k_nms_percat(cand_boxes_dev, cand_scores_dev, cand_valid_dev, P * K, 0, K, maxc.as<uint32_t>(), nms_thr,
+                                        keep_idx.as<int>(), keep_cnt.as<int>(), K, scratch.p, 0, B, 0, s);
+        if (!rc) rc = apse_k_rank_final(cand_boxes_dev, cand_scores_dev, P * K, keep_idx.as<int>(), keep_cnt.as<int>(), K, KD,
+                                        det_boxes_dev, det_scores_dev, det_entry_dev, det_cnt_dev, nullptr, B, s);
+    }
+    if (!rc) rc = apse_k_pack_detections(det_boxes_dev, det_scores_dev, det_entry_dev, det_cnt_dev, B, KD, K, pk_boxes_dev, pk_scores_dev,
+                                         pk_cls_dev, pk_img_dev, pk_roi_dev, pk_total_dev, pk_offset_dev,
+                                         sums.as<unsigned long long>(), s);
+    if (hipStreamSynchronize(s) != hipSuccess && !rc) rc = APSE_E_HIP;
+    return rc;
+}
+
+int apse_c4_rpn_select(const float* head_dev, int H, int W, int B, int image_h, int image_w, int pre, int post, float nms_thr,
+                       float* dec_boxes_dev, float* dec_scores_dev, int* dec_valid_dev, float* props_dev, float* prop_scores_dev,
+                       int* prop_entry_dev, int* prop_count_dev, void* stream) {
+    if (!head_dev || !dec_boxes_dev || !dec_scores_dev || !dec_valid_dev || !props_dev || !prop_scores_dev || !prop_entry_dev ||
+        !prop_count_dev || H < 1 || W < 1 || (long long)H * W * 15 > (1ll << 30) || B < 1 || B > 64)
+        return APSE_E_INVALID;
+    hipStream_t s = (hipStream_t)stream;
+    C4Rpn R;
+    c4_rpn_desc(head_dev, H, W, 80, pre, &R);
+    DevBuf scratch;
+    if (!scratch.alloc(apse_c4_nms_scratch_bytes(B))) return APSE_E_NOMEM;
+    int rc = apse_k_c4_rpn(&R, pre, post, (float)image_h, (float)image_w, (float)log(1000.0 / 16.0), nms_thr, dec_boxes_dev,
+                           dec_scores_dev, dec_valid_dev, scratch.p, props_dev, prop_scores_dev, prop_entry_dev, prop_count_dev, B, s);
+    if (hipStreamSynchronize(s) != hipSuccess && !rc) rc = APSE_E_HIP;
     return rc;
 }
 

@@ -468,6 +468,82 @@ static int add_box_predictor(apse_ctx* c, const Tens& in) {
     return APSE_OK;
 }
 
+// ------------------------------------------------------------------------------------------------ RPN selection plans
+static void cell_anchors3(int size, float (*base)[4]) {          // DefaultAnchorGenerator.generate_cell_anchors: doubles -> f32
+    static const double ratios[3] = {0.5, 1.0, 2.0};
+    for (int a = 0; a < 3; ++a) {
+        const double area = (double)size * size;
+        const double w = sqrt(area / ratios[a]), h = ratios[a] * w;
+        base[a][0] = (float)(-w / 2.0); base[a][1] = (float)(-h / 2.0);
+        base[a][2] = (float)(w / 2.0); base[a][3] = (float)(h / 2.0);
+    }
+}
+
+void rpn_select_plan(const float* const head[5], const int H[5], const int W[5], int head_ld, int pre_topk, RpnSelectPlan* out) {
+    static const int sizes[5] = {32, 64, 128, 256, 512};
+    static const int strides[5] = {4, 8, 16, 32, 64};
+    memset(&out->levels, 0, sizeof(out->levels));
+    out->levels.head_ld = head_ld;
+    out->levels.pre_topk = pre_topk;
+    for (int l = 0; l < 5; ++l) {
+        RpnLevel& L = out->levels.lv[l];
+        L.head = head[l]; L.H = H[l]; L.W = W[l]; L.stride = strides[l];
+        L.n = H[l] * W[l] * 3;
+        L.k = L.n < pre_topk ? L.n : pre_topk;
+        cell_anchors3(sizes[l], L.base);
+    }
+    // top-k tournament plan
+    out->stages.clear();
+    int slot = 0;
+    std::vector<std::vector<int>> cur_slots(5), cur_counts(5);
+    std::vector<TopkJob> st0;
+    for (int l = 0; l < 5; ++l) {
+        const int n = out->levels.lv[l].n;
+        for (int beg = 0; beg < n; beg += 4096) {
+            TopkJob j; memset(&j, 0, sizeof j);
+            j.kind = 0; j.level = l; j.begin = beg; j.count = (n - beg) < 4096 ? (n - beg) : 4096;
+            j.dst = slot++; j.dst_count = j.count < pre_topk ? j.count : pre_topk;
+            cur_slots[l].push_back(j.dst); cur_counts[l].push_back(j.dst_count);
+            st0.push_back(j);
+        }
+    }
+    out->stages.push_back(st0);
+    for (;;) {
+        std::vector<TopkJob> stn;
+        bool any = false;
+        for (int l = 0; l < 5; ++l) {
+            if (cur_slots[l].size() <= 1) continue;
+            any = true;
+            std::vector<int> ns, nc;
+            for (size_t i = 0; i < cur_slots[l].size(); i += 4) {
+                TopkJob j; memset(&j, 0, sizeof j);
+                j.kind = 1; j.level = l; int tot = 0;
+                for (size_t k = i; k < i + 4 && k < cur_slots[l].size(); ++k) {
+                    j.src[j.nsrc] = cur_slots[l][k]; j.src_count[j.nsrc] = cur_counts[l][k]; tot += cur_counts[l][k]; ++j.nsrc;
+                }
+                j.dst = slot++; j.dst_count = tot < pre_topk ? tot : pre_topk;
+                ns.push_back(j.dst); nc.push_back(j.dst_count);
+                stn.push_back(j);
+            }
+            cur_slots[l] = ns; cur_counts[l] = nc;
+        }
+        if (!any) break;
+        out->stages.push_back(stn);
+    }
+    out->nslots = slot;
+    for (int l = 0; l < 5; ++l) out->final_slot[l] = cur_slots[l][0];
+}
+
+void c4_rpn_desc(const float* head, int H, int W, int ld, int pre_topk, C4Rpn* Rp) {
+    C4Rpn& R = *Rp;
+    memset(&R, 0, sizeof R);
+    R.head = head; R.H = H; R.W = W; R.ld = ld; R.stride = 16;
+    R.n = H * W * 15;
+    R.k = R.n < pre_topk ? R.n : pre_topk;
+    static const int sizes[5] = {32, 64, 128, 256, 512};
+    for (int si = 0; si < 5; ++si) cell_anchors3(sizes[si], R.base + 3 * si);          // sizes outer, ratios inner
+}
+
 int build_plan(apse_ctx* c) {
     const apse_config& g = c->cfg;
     const int B = g.max_batch;
@@ -553,11 +629,7 @@ int build_plan(apse_ctx* c) {
         c->backbone.push_back(st);
     }
     // ---- RPN head per level: conv3x3+relu, fused 1x1 (3 objectness + 12 deltas) -> ld 16
-    static const int sizes[5] = {32, 64, 128, 256, 512};
     static const int strides[5] = {4, 8, 16, 32, 64};
-    memset(&c->rl_host, 0, sizeof(c->rl_host));
-    c->rl_host.head_ld = 16;
-    c->rl_host.pre_topk = g.rpn_pre_topk;
     // The 3x3 convolution runs per level; its outputs are slices of ONE buffer ([level][max_batch][H][W][256]) so that the
     // fused 1x1 head (objectness + deltas, shared weights) is a single launch over all rows of all levels
     // (five launches of 10-20 us, four of them with a handful of blocks, become one).
@@ -592,71 +664,30 @@ int build_plan(apse_ctx* c) {
         hs.fixed_items = 1;                        // all rows of all levels, whatever the batch of this forward
         hs.flops_per_item /= (double)B;            // profile accounting is per image
     }
-    for (int l = 0; l < 5; ++l) {
-        char hn[32];
-        snprintf(hn, sizeof hn, "rpn_head%d", l + 2);
-        Tens hh = h_all;
-        hh.p = h_all.p + row_off[l] * 16;
-        hh.H = pl[l].H; hh.W = pl[l].W; hh.C = 16;
-        c->t[hn] = hh;
-        RpnLevel& L = c->rl_host.lv[l];
-        L.head = hh.p; L.H = hh.H; L.W = hh.W; L.stride = strides[l];
-        L.n = hh.H * hh.W * 3;
-        L.k = L.n < g.rpn_pre_topk ? L.n : g.rpn_pre_topk;
-        static const double ratios[3] = {0.5, 1.0, 2.0};
-        for (int a = 0; a < 3; ++a) {
-            const double area = (double)sizes[l] * sizes[l];
-            const double w = sqrt(area / ratios[a]), h = ratios[a] * w;
-            L.base[a][0] = (float)(-w / 2.0); L.base[a][1] = (float)(-h / 2.0);
-            L.base[a][2] = (float)(w / 2.0); L.base[a][3] = (float)(h / 2.0);
-        }
-    }
-    c->rl_dev = dalloc<RpnLevels>(c, 1);
-    hipMemcpy(c->rl_dev, &c->rl_host, sizeof(RpnLevels), hipMemcpyHostToDevice);
-    // top-k tournament plan
     {
-        int slot = 0;
-        std::vector<std::vector<int>> cur_slots(5), cur_counts(5);
-        std::vector<TopkJob> st0;
+        const float* heads[5];
+        int hH[5], hW[5];
         for (int l = 0; l < 5; ++l) {
-            const int n = c->rl_host.lv[l].n;
-            for (int beg = 0; beg < n; beg += 4096) {
-                TopkJob j; memset(&j, 0, sizeof j);
-                j.kind = 0; j.level = l; j.begin = beg; j.count = (n - beg) < 4096 ? (n - beg) : 4096;
-                j.dst = slot++; j.dst_count = j.count < g.rpn_pre_topk ? j.count : g.rpn_pre_topk;
-                cur_slots[l].push_back(j.dst); cur_counts[l].push_back(j.dst_count);
-                st0.push_back(j);
-            }
+            char hn[32];
+            snprintf(hn, sizeof hn, "rpn_head%d", l + 2);
+            Tens hh = h_all;
+            hh.p = h_all.p + row_off[l] * 16;
+            hh.H = pl[l].H; hh.W = pl[l].W; hh.C = 16;
+            c->t[hn] = hh;
+            heads[l] = hh.p; hH[l] = hh.H; hW[l] = hh.W;
         }
-        c->stages.push_back(st0);
-        for (;;) {
-            std::vector<TopkJob> stn;
-            bool any = false;
-            for (int l = 0; l < 5; ++l) {
-                if (cur_slots[l].size() <= 1) continue;
-                any = true;
-                std::vector<int> ns, nc;
-                for (size_t i = 0; i < cur_slots[l].size(); i += 4) {
-                    TopkJob j; memset(&j, 0, sizeof j);
-                    j.kind = 1; j.level = l; int tot = 0;
-                    for (size_t k = i; k < i + 4 && k < cur_slots[l].size(); ++k) {
-                        j.src[j.nsrc] = cur_slots[l][k]; j.src_count[j.nsrc] = cur_counts[l][k]; tot += cur_counts[l][k]; ++j.nsrc;
-                    }
-                    j.dst = slot++; j.dst_count = tot < g.rpn_pre_topk ? tot : g.rpn_pre_topk;
-                    ns.push_back(j.dst); nc.push_back(j.dst_count);
-                    stn.push_back(j);
-                }
-                cur_slots[l] = ns; cur_counts[l] = nc;
-            }
-            if (!any) break;
-            c->stages.push_back(stn);
-        }
-        c->nslots = slot;
-        for (int l = 0; l < 5; ++l) c->final_slot_host[l] = cur_slots[l][0];
+        RpnSelectPlan sel;
+        rpn_select_plan(heads, hH, hW, 16, g.rpn_pre_topk, &sel);
+        c->rl_host = sel.levels;
+        c->rl_dev = dalloc<RpnLevels>(c, 1);
+        hipMemcpy(c->rl_dev, &c->rl_host, sizeof(RpnLevels), hipMemcpyHostToDevice);
+        c->stages = sel.stages;
+        c->nslots = sel.nslots;
+        for (int l = 0; l < 5; ++l) c->final_slot_host[l] = sel.final_slot[l];
         for (auto& sv : c->stages) c->stage_dev.push_back(dupload(c, sv));
         std::vector<int> fs(c->final_slot_host, c->final_slot_host + 5);
         c->final_slot_dev = dupload(c, fs);
-        c->lists = dalloc<uint64_t>(c, (size_t)B * slot * 1024);
+        c->lists = dalloc<uint64_t>(c, (size_t)B * sel.nslots * 1024);
     }
     if ((rc = alloc_proposals(c, 5))) return rc;
     const int POST = g.rpn_post_topk, KD = g.dets_per_image;
@@ -752,20 +783,7 @@ int build_plan_c4(apse_ctx* c) {
         rc = add_conv(c, c->rpnhead, sp, t, &h);
         if (rc) return rc;
         if (c->rpnhead.back().c.p.Cout != 75) return fail(c, APSE_E_INVALID, "C4 RPN head: expected 15 objectness + 60 delta channels");
-        C4Rpn& R = c->c4r;
-        memset(&R, 0, sizeof R);
-        R.head = h.p; R.H = h.H; R.W = h.W; R.ld = 80; R.stride = 16;
-        R.n = h.H * h.W * 15;
-        R.k = R.n < g.rpn_pre_topk ? R.n : g.rpn_pre_topk;
-        static const int sizes[5] = {32, 64, 128, 256, 512};
-        static const double ratios[3] = {0.5, 1.0, 2.0};
-        for (int si = 0; si < 5; ++si)
-            for (int a = 0; a < 3; ++a) {          // DefaultAnchorGenerator: sizes outer, ratios inner
-                const double area = (double)sizes[si] * sizes[si];
-                const double w = sqrt(area / ratios[a]), hh = ratios[a] * w;
-                float* bb = R.base[3 * si + a];
-                bb[0] = (float)(-w / 2.0); bb[1] = (float)(-hh / 2.0); bb[2] = (float)(w / 2.0); bb[3] = (float)(hh / 2.0);
-            }
+        c4_rpn_desc(h.p, h.H, h.W, 80, g.rpn_pre_topk, &c->c4r);
     }
     if ((rc = alloc_proposals(c, 1))) return rc;
     const int POST = g.rpn_post_topk, KD = g.dets_per_image;

@@ -23,8 +23,10 @@ __device__ __forceinline__ float mono_inv(uint32_t k) {
     uint32_t u = (k & 0x80000000u) ? (k & 0x7fffffffu) : ~k;
     return __uint_as_float(u);
 }
-// ascending sort of this composite = score descending, index ascending
+// ascending sort of this composite = score descending, index ascending.  The two zeros are one score (-0.0 == +0.0, as a
+// stable sort of the floats has it): the key carries +0, so a tie between them goes by index and comp_score returns +0.
 __device__ __forceinline__ uint64_t comp_key(float score, uint32_t idx) {
+    score = score == 0.f ? 0.f : score;
     return ((uint64_t)(~mono_key(score)) << 32) | idx;
 }
 __device__ __forceinline__ float comp_score(uint64_t k) { return mono_inv(~(uint32_t)(k >> 32)); }
@@ -154,7 +156,7 @@ __global__ __launch_bounds__(1024) void rpn_topk_stage(const RpnLevels* __restri
 
 // Decode the selected anchors of every level: Box2BoxTransform.apply_deltas (weights 1,1,1,1),
 // clip to the image, nonempty flag, and the running max coordinate of the kept boxes.
-// out arrays are [B][5*pre_topk].
+// out arrays are [B][5*pre_topk].  scores: the logit as the sort key carries it (a zero is +0 whatever its sign).
 __global__ __launch_bounds__(256) void rpn_decode(const RpnLevels* __restrict__ Lp, const uint64_t* __restrict__ lists, int nslots,
                                                   const int* __restrict__ final_slot, float img_h, float img_w,
                                                   float scale_clamp, float* __restrict__ boxes, float* __restrict__ scores,
@@ -201,7 +203,8 @@ __global__ __launch_bounds__(256) void rpn_decode(const RpnLevels* __restrict__ 
 // Entries: boxes/scores/valid are [B][n_total]; the category of entry e is
 // cat_div ? e / cat_div : e % cat_mod.  Within a category, entries are ordered by (score desc,
 // entry index asc); IoU is evaluated on boxes shifted by cat * (max_coord + 1) in f32 (torchvision
-// batched_nms); `iou > thr` suppresses.  Three launches:
+// batched_nms); `iou > thr` suppresses.  torchvision numbers the categories the call is given: with cat_mask != 0 (the RPN's
+// level mask) category c counts as the number of mask bits below c, with cat_mask == 0 as c itself.  Three launches:
 //   nms_prepare : one block per (category, image): ordered compaction + sort -> sorted shifted boxes
 //   nms_matrix  : 64x64 tiles of the upper-triangular suppression bit matrix, one wave each
 //   nms_scan    : one block per (category, image): greedy scan, 64 rows at a time
@@ -211,7 +214,7 @@ struct NmsScratch {
 };
 
 // Sorted keys -> the category's slot of the NMS scratch: boxes shifted by cat * (max_coord + 1) in f32 (torchvision batched_nms
-// numbers the categories that are present in the call: `cat` counts from the first one), their areas, entry ids, count.
+// numbers the categories that are present in the call: `cat` is the slot's rank among them), their areas, entry ids, count.
 __device__ __forceinline__ void nms_store_sorted(const uint64_t* keys, int n, int cat, uint32_t maxc_bits,
                                                  const float* __restrict__ boxes, NmsScratch S, size_t slot, int tid) {
     const float off = (float)cat * (__uint_as_float(maxc_bits) + 1.0f);
@@ -229,7 +232,7 @@ __device__ __forceinline__ void nms_store_sorted(const uint64_t* keys, int n, in
 
 __global__ __launch_bounds__(1024) void nms_prepare(const float* __restrict__ boxes, const float* __restrict__ scores,
                                                     const int* __restrict__ valid, int n_total, int cat_div, int cat_mod,
-                                                    const uint32_t* __restrict__ maxc, NmsScratch S, int ncat, int cat_shift,
+                                                    const uint32_t* __restrict__ maxc, NmsScratch S, int ncat, int cat_mask,
                                                     int presorted) {
     __shared__ uint64_t keys[NMS_MAX];
     __shared__ int wsum[17];
@@ -265,7 +268,7 @@ __global__ __launch_bounds__(1024) void nms_prepare(const float* __restrict__ bo
     // l * pre_topk + i is rank i of level l's top-k list (sorted by the same key; ties by anchor index = by i) -- so the ordered
     // compaction above IS the sorted list and the 55 barrier steps of the bitonic network are skipped
     if (!presorted) block_bitonic_sort<NMS_MAX / 1024>(keys, tid);
-    nms_store_sorted(keys, n, c - cat_shift, maxc[b], boxes, S, slot, tid);
+    nms_store_sorted(keys, n, cat_mask ? __popc(cat_mask & ((1 << c) - 1)) : c, maxc[b], boxes, S, slot, tid);
 }
 
 // Wide box inference (K > 8): the same as nms_prepare, but category c of image b reads only its own candidate list
@@ -914,7 +917,7 @@ static NmsScratch carve(void* scratch, int slots) {
     return S;
 }
 int apse_k_nms_percat(const float* boxes, const float* scores, const int* valid, int n_total, int cat_div, int cat_mod,
-                      const uint32_t* maxc, float thr, int* keep_idx, int* keep_cnt, int ncat, void* scratch, int cat_shift,
+                      const uint32_t* maxc, float thr, int* keep_idx, int* keep_cnt, int ncat, void* scratch, int cat_mask,
                       int B, int presorted, hipStream_t s) {
     static bool done = false;
     if (!done) {
@@ -924,7 +927,7 @@ int apse_k_nms_percat(const float* boxes, const float* scores, const int* valid,
     }
     NmsScratch S = carve(scratch, ncat * B);
     hipLaunchKernelGGL(nms_prepare, dim3(ncat, B), dim3(1024), 0, s, boxes, scores, valid, n_total, cat_div, cat_mod, maxc, S,
-                       ncat, cat_shift, presorted);
+                       ncat, cat_mask, presorted);
     hipLaunchKernelGGL(nms_matrix, dim3(16, 16, ncat * B), dim3(64), 0, s, S, thr);
     hipLaunchKernelGGL(nms_scan, dim3(ncat, B), dim3(1024), NMS_MAX * 16 * 8, s, S, keep_idx, keep_cnt);
     return hipGetLastError() == hipSuccess ? APSE_OK : APSE_E_HIP;

@@ -284,6 +284,41 @@ int apse_roi_pool(const float* feat_dev, int H, int W, const float* rois_dev, co
 int apse_nms_rank(const float* boxes_dev, const float* scores_dev, const int* valid_dev, int n, int cat_div, int cat_mod,
                   int ncat, float thr, int topk, float* out_boxes_dev, float* out_scores_dev, int* out_index_dev,
                   int* out_count_dev, void* stream);
+/* The decision kernels on injected inputs.  Each entry runs the launchers of apse_rpn_levels / apse_box_head, in their order
+ * and with their arguments, on scratch of its own, and synchronises `stream` before it returns.  All pointers but heads_dev,
+ * H and W are device pointers.
+ *
+ * apse_rpn_select: the FPN RPN selection (top-k tournament, decode, per-level NMS, rank merge).  heads_dev: five device
+ * pointers (a host array), level l [B][H[l]*W[l]][head_ld] f32 with the objectness of anchor a at channel a and its deltas
+ * at 3 + 4 a; head_ld >= 15, 1 <= pre_topk <= 1000, level_mask as in apse_rpn_levels.  keys_dev (may be NULL): the final
+ * sorted list of every level, [B][5][pre_topk] u64, entries past min(pre_topk, 3 H W) all ones; a key is
+ * (~m << 32) | anchor with m = score bits ^ 0x80000000 for a score >= 0 and ~(score bits) below, so that ascending keys are
+ * score descending, anchor ascending.  dec_boxes_dev [B][5*pre_topk][4], dec_scores_dev, dec_valid_dev [B][5*pre_topk]
+ * (a zero score is +0 whatever the logit's sign); props_dev [B][post_topk][4], prop_scores_dev, prop_entry_dev
+ * [B][post_topk] (entry = level * pre_topk + rank; zeros and -1 past the count), prop_count_dev [B]. */
+int apse_rpn_select(const float* const* heads_dev, const int* H, const int* W, int head_ld, int B, int image_h, int image_w,
+                    int pre_topk, int post_topk, float nms_thr, int level_mask, unsigned long long* keys_dev, float* dec_boxes_dev,
+                    float* dec_scores_dev, int* dec_valid_dev, float* props_dev, float* prop_scores_dev, int* prop_entry_dev,
+                    int* prop_count_dev, void* stream);
+/* Box inference: candidates (softmax, decode with weights 10, 10, 5, 5, clip, score filter), per-class NMS, top
+ * dets_per_image, pack.  wide = 0: the one-thread-per-ROI kernels (K <= 7); wide != 0: the wave-per-ROI kernels, list-fed NMS
+ * and the rank sort (1 <= K <= 127, K * dets_per_image <= 8192).  pred_dev [B*P][ld]: K + 1 logits (background last), then
+ * 4 K deltas; ld >= 5 K + 1; P <= 1024; props_dev [B*P][4], prop_cnt_dev [B].  Out: probs_dev [B*P][K+1]; cand_boxes_dev
+ * [B*P*K][4], cand_scores_dev, cand_valid_dev [B*P*K] (entry = roi * K + class); det_boxes_dev [B][dets][4], det_scores_dev,
+ * det_entry_dev [B][dets], det_cnt_dev [B]; pk_boxes_dev [B*dets][4], pk_scores_dev, pk_cls_dev, pk_img_dev, pk_roi_dev
+ * [B*dets] (the first pk_total entries are written), pk_total_dev [1], pk_offset_dev [B+1]. */
+int apse_box_inference(const float* pred_dev, int ld, int K, const float* props_dev, const int* prop_cnt_dev, int P, int B,
+                       int image_h, int image_w, float score_thresh, float nms_thr, int dets_per_image, int wide,
+                       float* probs_dev, float* cand_boxes_dev, float* cand_scores_dev, int* cand_valid_dev, float* det_boxes_dev,
+                       float* det_scores_dev, int* det_entry_dev, int* det_cnt_dev, float* pk_boxes_dev, float* pk_scores_dev,
+                       int* pk_cls_dev, int* pk_img_dev, int* pk_roi_dev, int* pk_total_dev, int* pk_offset_dev, void* stream);
+/* The C4 proposal path (radix select, decode, long NMS, early-exit scan) on a head [B][H*W][80]: objectness of anchor a at
+ * channel a, deltas at 15 + 4 a.  1 <= pre <= 6000, 1 <= post <= 1000.  dec_boxes_dev [B][pre][4], dec_scores_dev,
+ * dec_valid_dev [B][pre]; props_dev [B][post][4], prop_scores_dev, prop_entry_dev [B][post] (entry = rank in the decoded
+ * list), prop_count_dev [B]. */
+int apse_c4_rpn_select(const float* head_dev, int H, int W, int B, int image_h, int image_w, int pre, int post, float nms_thr,
+                       float* dec_boxes_dev, float* dec_scores_dev, int* dec_valid_dev, float* props_dev, float* prop_scores_dev,
+                       int* prop_entry_dev, int* prop_count_dev, void* stream);
 /* mask_utils on a dense bool frame (uint8 0/1): centroid (1-based floor) and closest point to (px, py). */
 int apse_mask_centroid_dense(const uint8_t* mask_dev, int H, int W, int* out_xy_mass_host3, void* stream);
 int apse_mask_closest_dense(const uint8_t* mask_dev, int H, int W, float px, float py, int* out_xy_host2, void* stream);
