@@ -58,8 +58,12 @@ def emulate(x_hwc, w_oihw, bias, relu):
     v = _input_transform(d)                                       # [th][tw][16][C]
     u = filter_transform(w_oihw)                                  # [16][Cout][C]
     m = np.zeros((th, tw, 16, u.shape[1]), np.float32)
-    for c in range(C):                                            # channels ascending, one f32 rounding per product and per add
-        m += v[..., c:c + 1] * u[None, None, :, :, c]
+    uc = np.ascontiguousarray(u.transpose(2, 0, 1))               # [C][16][Cout]
+    rows = max(1, (1 << 18) // (tw * 16 * u.shape[1]))            # tile rows per pass: about 1 MiB of m, so the channel loop stays in cache
+    for r0 in range(0, th, rows):                                 # (tiles are independent: the same arithmetic as one pass over the image)
+        vr, mr = v[r0:r0 + rows], m[r0:r0 + rows]
+        for c in range(C):                                        # channels ascending, one f32 rounding per product and per add
+            mr += vr[..., c:c + 1] * uc[c]
     y = _output_transform(m) + np.asarray(bias, np.float32)      # [th][tw][2][2][Cout]
     if relu:
         y = np.maximum(y, 0)

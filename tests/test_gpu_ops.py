@@ -738,3 +738,89 @@ def test_c_abi_rejects_bad_arguments():
     assert lib.apse_create(C.byref(cfg), C.byref(ctx)) < 0 and not ctx.value
     assert b"storage16" in lib.apse_last_error(None)
     torch.cuda.synchronize()
+
+
+# ---------------------------------------------------------------------------------------------- the direct kernels on an integer lattice
+LATTICE_ROWS = 8192          # B * OH * OW up to which a case is taken (leaves out the big-map variants only)
+
+
+def _out_rows(B, H, W, K, stride, pad):
+    return B * ((H + 2 * pad - K) // stride + 1) * ((W + 2 * pad - K) // stride + 1)
+
+
+def _lattice_params():
+    """(id, kind, case, prec) for every CONV / STREAM / SKINNY case of at most LATTICE_ROWS output rows, in the storage types the
+    parity tests above run it in (their skip rules, restated): test_conv2d_parity (f32, not cfg 11), test_conv2d_16bit_storage
+    (Cin >= 8), test_conv1x1_stream, test_conv_skinny16 (prec = the storage type of x; f32 arithmetic)."""
+    out = []
+    for c in CONV_CASES:
+        name, B, Cin, H, W, Cout, K, stride, pad, relu, res_mode, cfg, splitk = c
+        if _out_rows(B, H, W, K, stride, pad) > LATTICE_ROWS:
+            continue
+        for prec in (0, 1, 2):
+            if (prec == 0 and cfg == 11) or (prec != 0 and Cin < 8):
+                continue
+            out.append(("conv-%s-%s" % (name, ("f32", "bf16", "f16")[prec]), "conv", c, prec))
+    for c in STREAM_CASES:
+        name, B, Cin, H, W, Cout, stride, relu, res_mode = c
+        if _out_rows(B, H, W, 1, stride, 0) > LATTICE_ROWS:
+            continue
+        for prec in (0, 1, 2):
+            if (prec != 0 and Cout % 128) or (prec == 0 and Cin == 256 and (stride != 1 or (H // stride) * (W // stride) < 32768)):
+                continue
+            out.append(("stream-%s-%s" % (name, ("f32", "bf16", "f16")[prec]), "stream", c, prec))
+    for c in SKINNY_CASES:
+        name, B, H, W, Cout, relu = c
+        if B * H * W <= LATTICE_ROWS:
+            out += [("skinny-%s-%s" % (name, ("x_f32", "x_bf16", "x_f16")[xst]), "skinny", c, xst) for xst in (0, 1, 2)]
+    return out
+
+
+_LATTICE = _lattice_params()
+
+
+@pytest.mark.parametrize("kind,case,prec", [p[1:] for p in _LATTICE], ids=[p[0] for p in _LATTICE])
+def test_conv2d_exact_on_lattice(kind, case, prec):
+    """x, w integers in [-2, 2], bias and residual integers in [-8, 8]: every product and partial sum is an integer below 2^24, so
+    the f32 accumulators hold the float64 result whatever the tile, the k order or the split.  f32 output: equal to float64 at
+    every element; 16-bit output: equal to the float64 result rounded once to the storage type.  (Integers up to 8 are exact in
+    bf16 and f16, so the 16-bit operand paths see the same lattice.)"""
+    from hip_helpers import hip_conv2d
+    import zlib
+    if kind == "conv":
+        name, B, Cin, H, W, Cout, K, stride, pad, relu, res_mode, cfg, splitk = case
+        kw = dict(prec=prec, x_st=prec, y_st=prec)
+    elif kind == "stream":
+        (name, B, Cin, H, W, Cout, stride, relu, res_mode), K, pad, cfg, splitk = case, 1, 0, 9, 0
+        kw = dict(prec=prec, x_st=prec, y_st=prec)
+    else:
+        (name, B, H, W, Cout, relu), Cin, K, stride, pad, res_mode, cfg, splitk = case, 256, 1, 1, 0, 0, 13, 0
+        kw = dict(prec=0, x_st=prec, y_st=0)
+    g = torch.Generator().manual_seed(zlib.crc32(name.encode()) % 10000 + 1)
+    x = torch.randint(-2, 3, (B, Cin, H, W), generator=g).float()
+    w = torch.randint(-2, 3, (Cout, Cin, K, K), generator=g).float()
+    b = torch.randint(-8, 9, (Cout,), generator=g).float()
+    ref = F.conv2d(x.double(), w.double(), b.double(), stride=stride, padding=pad)
+    cap = F.conv2d(x.double().abs(), w.double().abs(), b.double().abs(), stride=stride, padding=pad)     # sum of |terms|
+    res = None
+    if res_mode == 1:
+        res = torch.randint(-8, 9, ref.shape, generator=g).float()
+        ref, cap = ref + res.double(), cap + res.double().abs()
+    elif res_mode == 2:
+        res = torch.randint(-8, 9, (B, Cout, ref.shape[2] // 2, ref.shape[3] // 2), generator=g).float()
+        up = F.interpolate(res.double(), scale_factor=2, mode="nearest")
+        ref, cap = ref + up, cap + up.abs()
+    if relu:
+        ref = F.relu(ref)
+    assert float(cap.max()) < 2.0 ** 24 and float(ref.abs().max()) < 60000 and torch.equal(ref, ref.round())
+    if res is not None:
+        kw["res_st"] = kw["x_st"] if kind != "skinny" else 0
+    out = hip_conv2d(x, w, b, stride, pad, relu, res, res_mode, cfg, splitk, **kw)
+    want = ref if kw["y_st"] == 0 else ref.to({1: torch.bfloat16, 2: torch.float16}[kw["y_st"]]).double()
+    bad = (out.double() != want).nonzero()
+    assert torch.equal(out.double(), want), (int(bad.shape[0]), bad[:6].tolist())
+    if kind == "conv" and splitk > 0 and prec == 0:
+        # the in-launch reduction of the split as well (f32 only: the 16-bit operand kernels keep the separate reduce pass)
+        assert torch.equal(hip_conv2d(x, w, b, stride, pad, relu, res, res_mode, cfg, splitk, fuse=1, **kw).double(), want)
+    if kind == "conv" and prec != 0 and cfg in (-1, 2) and res_mode == 0:      # f32 kernel reading 16-bit activations
+        assert torch.equal(hip_conv2d(x, w, b, stride, pad, relu, None, 0, cfg, splitk, prec=0, x_st=prec).double(), ref)
