@@ -91,6 +91,13 @@ typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
 #ifdef __HIPCC__
 typedef _Float16 f16x4_t __attribute__((ext_vector_type(4)));
 typedef __bf16 bf16x4_t __attribute__((ext_vector_type(4)));
+// XCD-aware block order.  The hardware deals the workgroups of a launch round-robin over the 8 XCDs, each with an L2 of its own:
+// workgroup wg runs on XCD wg & 7.  This maps wg to a work item so that every XCD gets one contiguous range of the nwg items,
+// and neighbours that share operands share an L2.  Bijective on 0..nwg-1 for any nwg (the first nwg & 7 XCDs take one more).
+__device__ __forceinline__ int apse_xcd_remap(int wg, int nwg) {
+    const int q = nwg >> 3, r = nwg & 7, xcd = wg & 7, idx = wg >> 3;
+    return (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + idx;
+}
 __device__ __forceinline__ f32x4 apse_ld4(const void* base, size_t idx, int st) {
     if (st == 0) return *reinterpret_cast<const f32x4*>(reinterpret_cast<const float*>(base) + idx);
     f32x4 r;

@@ -145,12 +145,7 @@ __global__ __launch_bounds__(256, 2) void bottleneck64_fused16(const BneckParams
         int fr = fr0, fh = fh0;
         asm volatile("" : "+v"(fr), "+v"(fh));
         // XCD-aware order: the blocks of one XCD (blockIdx & 7) walk a contiguous range of tiles (they share halos in its L2)
-        int tile;
-        {
-            const int wg = blockIdx.x + it * gridDim.x;
-            const int q = tiles >> 3, r = tiles & 7, xcd = wg & 7, idx = wg >> 3;
-            tile = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + idx;
-        }
+        const int tile = apse_xcd_remap(blockIdx.x + it * gridDim.x, tiles);
         const int b = tile / tiles_img;
         const int tr = tile - b * tiles_img;
         const int tyi = tr / p.tiles_x, txi = tr - tyi * p.tiles_x;

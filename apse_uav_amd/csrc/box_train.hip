@@ -14,13 +14,15 @@
 //                   wgrad     dW = dY^T X                    A = dY [m][o] major,  B = X  [m][k] major
 //                 A tile owns its outputs over the whole reduction: the gradients need no split and write no partial tiles; only
 //                 the forward of a layer 4096 inputs wide or more (fc1) runs as 8 chunks of the reduction that a second kernel
-//                 adds in chunk order.  Rows and columns outside the shapes are masked at the loads (exact zeros), never read.  The MFMA chain runs over 64 reduction steps, then
-//                 joins the running total, as in mask_train.hip.
+//                 adds in chunk order.  Rows and columns outside the shapes are masked at the loads (exact zeros), never read.
+//                 The tile, its constants and the summation order (MFMA chains of 64 reduction steps that join a running
+//                 total) are described once, in train_tile.h; mask_train.hip's two MFMA kernels follow the same rule.
 //   bias          db = column sums in f64, rows in ascending order inside slices of 64, slices in ascending order.
 //   loss          cross_entropy (mean over the n rows) + smooth_l1 on the four columns of the ground-truth class of the
 //                 foreground rows (sum / n), the logged ratios, and both gradients.
 // Determinism: no float atomics; every sum has a fixed order that depends on the shapes only.
 #include "apse_kernels.h"
+#include "train_tile.h"
 #include "../../include/apse_hip.h"
 #include <math.h>
 #include <stdint.h>
@@ -89,13 +91,11 @@ __global__ __launch_bounds__(256) void permute_hwc_chw(const float* __restrict__
 
 // ---------------------------------------------------------------------------------------------------------------- gemm
 // The f32 MFMA takes A[i = lane & 31][k = lane >> 5] and B[k = lane >> 5][j = lane & 31] in one register each.  A reduction-major
-// operand sits in LDS as [32 k][160] rows (a lane's 32 neighbours read consecutive floats, the two k rows of one instruction fall
-// into different bank halves); a reduction-minor one as [128 i][33] (consecutive i are 33 floats apart: conflict-free again).
-constexpr int kKT = 32;                  // reduction steps per stage
-constexpr int kLdMajor = 160, kLdMinor = 33;
-constexpr int kOpFloats = kKT * kLdMajor;                          // 5120 >= 128 * 33
+// operand sits in LDS as train_tile.h lays it out ([32 k][160]); a reduction-minor one as [128 i][33] (consecutive i are 33 floats
+// apart: conflict-free again).
+constexpr int kLdMinor = 33;
+constexpr int kOpFloats = kMajorFloats;                            // 5120 >= 128 * 33
 constexpr int kGemmLds = 2 * 2 * kOpFloats * (int)sizeof(float);   // double buffer x (A, B)
-constexpr int kFlush = 2;                // stages per MFMA chain before it joins the running total
 
 // four floats row[col .. col + 3] of a row with `lim` valid columns (row == nullptr: none); vec: 16-byte aligned rows
 __device__ __forceinline__ f32x4 ld_masked(const float* __restrict__ row, int col, int lim, bool vec) {
@@ -136,14 +136,12 @@ __device__ __forceinline__ void stage_op(float* __restrict__ s, int t, const f32
 #pragma unroll
             for (int e = 0; e < 4; ++e) s[(row + 32 * i) * kLdMinor + 4 * k4 + e] = reg[i][e];
     } else {
-        const int row = t >> 5, c4 = t & 31;
-#pragma unroll
-        for (int i = 0; i < 4; ++i) *reinterpret_cast<f32x4*>(s + (row + 8 * i) * kLdMajor + c4 * 4) = reg[i];
+        stage_major(s, t, reg);
     }
 }
 template <bool MINOR>
 __device__ __forceinline__ float read_op(const float* __restrict__ s, int idx, int k) {
-    return MINOR ? s[idx * kLdMinor + k] : s[k * kLdMajor + idx];
+    return MINOR ? s[idx * kLdMinor + k] : read_major(s, idx, k);
 }
 
 // C[i][j] = (accumulate ? C[i][j] : 0) + relu?(bias[j] + sum_{r < R} A(i, r) B(r, j)), i < I, j < J.  With `part` the reduction is
@@ -154,14 +152,8 @@ __global__ __launch_bounds__(256, 2) void fc_gemm(const float* __restrict__ A, i
                                                float* __restrict__ C, int ldc, int spc, float* __restrict__ part) {
     extern __shared__ __align__(16) float lds[];
     const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
-    // XCD-aware order (blocks are dealt round-robin over 8 XCDs): each XCD gets a contiguous range of tiles, i fastest, so the
-    // tiles that read the same columns of B share an L2
-    const int nwg = gridDim.x;
-    int bid;
-    {
-        const int wg = blockIdx.x, q = nwg >> 3, r = nwg & 7, xcd = wg & 7, idx = wg >> 3;
-        bid = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + idx;
-    }
+    // XCD-aware order, i fastest: the tiles that read the same columns of B share an L2
+    const int bid = apse_xcd_remap(blockIdx.x, gridDim.x);
     const int tiles_i = (I + 127) >> 7;
     const int i0 = (bid % tiles_i) * 128, j0 = (bid / tiles_i) * 128;
     const bool avec = !(lda & 3) && !(reinterpret_cast<uintptr_t>(A) & 15);
@@ -320,18 +312,6 @@ __device__ __forceinline__ float delta_target(const float* __restrict__ p, const
         return wt.w[j] * (gc - pc) / ps;
     }
     return wt.w[j] * logf(gs / ps);
-}
-__device__ __forceinline__ double block_sum_d(double v, double* red) {       // fixed-shape tree over 256 threads
-    const int t = threadIdx.x;
-    red[t] = v;
-    __syncthreads();
-    for (int s = 128; s > 0; s >>= 1) {
-        if (t < s) red[t] = red[t] + red[t + s];
-        __syncthreads();
-    }
-    const double r = red[0];
-    __syncthreads();
-    return r;
 }
 constexpr int kLossCols = 6;
 // One thread per row: part[r] = {cross-entropy term, smooth-L1 term, argmax == label, foreground, foreground and argmax == label,

@@ -62,12 +62,7 @@ __global__ __launch_bounds__(512) void conv_glds16(const ConvParams p) {
     const int tiles_n = (p.Cout + GL_BN - 1) / GL_BN;
     const int tiles_m = (M + GL_BM - 1) / GL_BM;
     const int nwg = tiles_m * tiles_n;
-    int bid;
-    {   // XCD-aware bijective remap (blocks are dealt round-robin over the 8 XCDs): contiguous tile ranges per XCD
-        const int wg = blockIdx.x;
-        const int q = nwg >> 3, r = nwg & 7, xcd = wg & 7, idx = wg >> 3;
-        bid = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + idx;
-    }
+    const int bid = apse_xcd_remap(blockIdx.x, nwg);            // contiguous tile ranges per XCD
     const int tile_m = bid / tiles_n, tile_n = bid - tile_m * tiles_n;
     const int m0 = tile_m * GL_BM, n0 = tile_n * GL_BN;
     const int ohw = p.OH * p.OW;

@@ -102,13 +102,8 @@ __global__ __launch_bounds__(64 * WM * WN * WK) void conv_igemm_f32(const ConvPa
     // Persistent over tiles: the grid is min(tiles, cap); count-limited launches (packed detection
     // lists) therefore spend nothing on tiles past the device-side count.
     for (int wg = blockIdx.x; wg < nwg; wg += gridDim.x) {
-        // XCD-aware remap (blocks are dealt round-robin over 8 XCDs): give each XCD a contiguous
-        // range of tiles so neighbours that share an activation tile share an L2.  Bijective form.
-        int bid;
-        {
-            const int q = nwg >> 3, r = nwg & 7, xcd = wg & 7, idx = wg >> 3;
-            bid = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + idx;
-        }
+        // XCD-aware order: neighbours that share an activation tile share an L2
+        const int bid = apse_xcd_remap(wg, nwg);
         const int tile_m = bid / tiles_n, tile_n = bid - tile_m * tiles_n;
         const int m0 = tile_m * BM, n0 = tile_n * BN;
 

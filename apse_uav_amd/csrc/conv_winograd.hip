@@ -55,17 +55,11 @@ __global__ __launch_bounds__(NTHR) void conv_winograd_f32(const ConvParams p) {
     const int lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int fr = lane & 31, fh = lane >> 5;
 
-    // block -> (image, tile strip, N tile); blocks are dealt round-robin over 8 XCDs: give each XCD a contiguous range so
-    // the four N tiles of one input patch run on the same L2
+    // block -> (image, tile strip, N tile) in XCD-aware order: the four N tiles of one input patch run on the same L2
     const int tiles_y = (p.OH + 2 * WTR - 1) / (2 * WTR), tiles_x = (p.OW + 2 * WTC - 1) / (2 * WTC);
     const int nblk = p.Cout / WN;
     const int nwg = p.B * tiles_y * tiles_x * nblk;
-    int bid;
-    {
-        const int wg = blockIdx.x;
-        const int q = nwg >> 3, r = nwg & 7, xcd = wg & 7, idx = wg >> 3;
-        bid = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + idx;
-    }
+    const int bid = apse_xcd_remap(blockIdx.x, nwg);
     const int nb = bid % nblk;
     int rest = bid / nblk;
     const int bx = rest % tiles_x; rest /= tiles_x;

@@ -21,8 +21,11 @@
 //                 ratios, and d = (sigmoid(x) - t) / (n x 784) for that channel only.
 //   predictor     dX = d W[class] under the deconvolution's ReLU mask, dW[class] and db[class]: per-RoI sums, then RoIs in
 //                 ascending order per class.
+// conv3x3 and wgrad run the 128 x 128 MFMA tile and the chain-of-64 summation rule that train_tile.h describes once, for them and
+// for box_train.hip's fc_gemm.
 // Determinism: no float atomics; every sum has a fixed order that depends on the shapes only.
 #include "apse_kernels.h"
+#include "train_tile.h"
 #include "../../include/apse_hip.h"
 #include <math.h>
 #include <string.h>
@@ -70,14 +73,11 @@ __global__ void pack_bias(const float* __restrict__ b, int n, int n_p, float* __
 // out[m][tap][c] = sum_p A[p][m] * Bt(p, tap)[c], m and c in 0..255, p over the n * 196 pixels of the 14 x 14 RoI grids.
 //   MODE 0 (3x3 convolution, 9 taps):  A = dY [n][14][14][256], Bt(p, (kh, kw)) = X[r][y + kh - 1][x + kw - 1][:] (zero outside)
 //   MODE 1 (deconvolution, 4 taps):    A = X  [n][14][14][256], Bt(p, (a, b))  = dY[r][2 y + a][2 x + b][:]   (dY on 28 x 28)
-// Block = 128 (m) x 128 (c) of one tap and one chunk of the reduction; 4 waves as 2 x 2, each 2 x 2 MFMA tiles of 32 x 32.
+// Block = train_tile.h's tile on 128 (m) x 128 (c) of one tap and one chunk of the reduction, a stage = 32 pixels.
 // The f32 MFMA takes A[i = lane & 31][k = lane >> 5] and B[k = lane >> 5][j = lane & 31] in one register each: both operand
-// tiles sit in LDS as [k][128 + pad] rows, so a lane's operand is one ds_read_b32 and the 32 lanes of a k read consecutive
-// floats (row stride 160 floats: the two k rows of one instruction fall into different bank halves).
-constexpr int kKT = 32;                  // pixels per step
-constexpr int kLd = 160;                 // LDS row stride (floats)
-constexpr int kWgLds = 2 * 2 * kKT * kLd * (int)sizeof(float);    // double buffer x (A, B)
-constexpr int kFlush = 2;                // steps per MFMA chain before it joins the running total
+// tiles sit in LDS reduction-major (train_tile.h), so a lane's operand is one ds_read_b32.
+constexpr int kLd = kLdMajor;
+constexpr int kWgLds = 2 * 2 * kMajorFloats * (int)sizeof(float);    // double buffer x (A, B)
 
 template <int MODE>
 __global__ __launch_bounds__(256) void wgrad_mfma(const float* __restrict__ A, const float* __restrict__ B, int P,
@@ -86,14 +86,8 @@ __global__ __launch_bounds__(256) void wgrad_mfma(const float* __restrict__ A, c
     constexpr int TILES = 2 * NTAP * 2;
     extern __shared__ __align__(16) float lds[];
     const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
-    // XCD-aware order (blocks are dealt round-robin over 8 XCDs): each XCD gets a contiguous range of (chunk, tile) pairs, so the
-    // tiles that read the same pixels share an L2
-    const int nwg = TILES * nchunks;
-    int bid;
-    {
-        const int wg = blockIdx.x, q = nwg >> 3, r = nwg & 7, xcd = wg & 7, idx = wg >> 3;
-        bid = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + idx;
-    }
+    // XCD-aware order over (chunk, tile) pairs: the tiles that read the same pixels share an L2
+    const int bid = apse_xcd_remap(blockIdx.x, TILES * nchunks);
     const int chunk = bid / TILES, tile = bid - chunk * TILES;
     const int tile_m = tile / (NTAP * 2), rem = tile - tile_m * (NTAP * 2);
     const int tap = rem >> 1, m0 = tile_m * 128, c0 = (rem & 1) * 128;
@@ -128,7 +122,7 @@ __global__ __launch_bounds__(256) void wgrad_mfma(const float* __restrict__ A, c
         float* as = lds + buf * (2 * kKT * kLd);
         float* bs = as + kKT * kLd;
 #pragma unroll
-        for (int i = 0; i < 4; ++i) {
+        for (int i = 0; i < 4; ++i) {              // stage_major's layout, A and B rows interleaved
             *reinterpret_cast<f32x4*>(as + (srow + 8 * i) * kLd + c4 * 4) = ra[i];
             *reinterpret_cast<f32x4*>(bs + (srow + 8 * i) * kLd + c4 * 4) = rb[i];
         }
@@ -203,12 +197,7 @@ __global__ __launch_bounds__(256) void conv3x3_mfma(const float* __restrict__ X,
                                                     const float* __restrict__ bias, int P, int relu, float* __restrict__ Y) {
     extern __shared__ __align__(16) float lds[];
     const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
-    const int nwg = gridDim.x;
-    int bid;
-    {
-        const int wg = blockIdx.x, q = nwg >> 3, r = nwg & 7, xcd = wg & 7, idx = wg >> 3;
-        bid = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + idx;
-    }
+    const int bid = apse_xcd_remap(blockIdx.x, gridDim.x);
     const int m0 = (bid >> 1) * 128, n0 = (bid & 1) * 128;
     const int srow = t >> 3, k4 = t & 7;            // staging: rows srow + 32 i, float4 at k = 4 k4
     int py[4], px[4], pp[4];
@@ -350,18 +339,6 @@ __device__ __forceinline__ int roi_class(const int* cls, int r, int K) {
     if (K == 1) return 0;
     const int k = cls[r];
     return k < 0 ? 0 : (k >= K ? K - 1 : k);           // the caller checks the range on the host; never index outside the row
-}
-__device__ __forceinline__ double block_sum_d(double v, double* red) {       // fixed-shape tree over 256 threads
-    const int t = threadIdx.x;
-    red[t] = v;
-    __syncthreads();
-    for (int s = 128; s > 0; s >>= 1) {
-        if (t < s) red[t] = red[t] + red[t + s];
-        __syncthreads();
-    }
-    const double r = red[0];
-    __syncthreads();
-    return r;
 }
 // One block per RoI: part[r] = {sum of the 784 loss terms, wrong pixels, positives, wrong negatives (fp), wrong positives (fn)}.
 // A thread adds its pixels t, t + 256, ... in that order in f32 (at most 4 terms), the tree and everything above it run in f64.
