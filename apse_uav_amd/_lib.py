@@ -196,6 +196,11 @@ SIGNATURES = {
     "apse_box_bias_grad": ([vp, i, i, vp, vp, sz, vp], i),
     "apse_box_loss_forward": ([vp, vp, vp, vp, vp, i, i, C.POINTER(f * 4), f, vp, vp, sz, vp], i),
     "apse_box_loss_backward": ([vp, vp, vp, vp, vp, i, i, C.POINTER(f * 4), f, vp, vp, vp, vp, vp], i),
+    "apse_rpn_train_workspace_bytes": ([i, i, i], sz),
+    "apse_rpn_anchor_labels": ([C.POINTER(i * 5), C.POINTER(i * 5), vp, i, f, f, vp, vp, vp, vp, sz, vp], i),
+    "apse_rpn_patches": ([vp, i, vp, i, vp, vp, vp, vp, vp], i),
+    "apse_rpn_loss_forward": ([vp, vp, vp, vp, vp, vp, i, i, f, vp, vp, sz, vp], i),
+    "apse_rpn_loss_backward": ([vp, vp, vp, vp, vp, vp, i, i, f, vp, vp, vp, vp, vp], i),
     "apse_augment_u8": ([vp, i, i, i, vp, vp, vp, vp, vp], i),
 }
 del vp, i, f, sz

@@ -76,6 +76,20 @@ struct AugmentImage {
 struct AugmentBatch {
     AugmentImage im[64];                 // APSE_AUGMENT_MAX_BATCH; a kernel argument (3.5 KiB)
 };
+// ---------------------------------------------------------------- RPN-head training (rpn_train.hip)
+// The anchors of the five levels in (level, y, x, a) order as a kernel argument: level l holds elements off[l] .. off[l + 1] - 1,
+// element e of it is pixel e / 3, anchor e % 3, at (x stride, y stride) + base[l][a] -- the boxes rpn_decode computes
+struct RpnAnchorGrid {
+    int H[5], W[5], stride[5];
+    int off[6];
+    float base[5][3][4];   // cell anchors (x0,y0,x1,y1) per level: apse_cell_anchors3
+};
+struct RpnGatherMaps {
+    const float* p[5];     // p2..p6 of ONE image, each [H][W][256] f32
+};
+// DefaultAnchorGenerator.generate_cell_anchors for one size and the ratios (0.5, 1, 2): Python doubles -> f32 (plan.hip; the one
+// definition behind the inference plan and the training anchors)
+void apse_cell_anchors3(int size, float (*base)[4]);
 
 extern "C" {
 // ---- elementwise.hip
@@ -163,4 +177,7 @@ int apse_k_mask_roi_index(int* idx, int n, hipStream_t s);
 // ---- augment.hip
 int apse_k_augment(const uint8_t* src, int B, int H, int W, const AugmentBatch* P_host, uint8_t* out_u8, float* out_chw,
                    unsigned long long* sums, hipStream_t s);
+// ---- rpn_train.hip
+int apse_k_rpn_gather(const RpnAnchorGrid* grid, const RpnGatherMaps* maps, const int* anchor_idx, int S, float* x, int* slots,
+                      float* anchor_boxes, int* levels, hipStream_t s);
 }

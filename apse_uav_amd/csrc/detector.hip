@@ -919,6 +919,37 @@ int apse_proposals(apse_ctx* c, int image, float* boxes, int* count, void* strea
     return lane_follow(c, s);
 }
 
+int apse_rpn_patches(apse_ctx* c, int image, const int* anchor_idx, int S, float* x, int* slots, float* anchor_boxes, int* levels,
+                     void* stream) {
+    if (!c || !c->finalized) return fail(c, APSE_E_STATE, "not finalized");
+    const apse_config& g = c->cfg;
+    if (c->c4) return fail(c, APSE_E_INVALID, "apse_rpn_patches reads p2..p6: not available under C4 (arch 1)");
+    if (image < 0 || image >= g.max_batch || S < 0 || S > (1 << 20) || (S > 0 && (!anchor_idx || !x || !slots || !anchor_boxes || !levels)))
+        return fail(c, APSE_E_INVALID, "bad apse_rpn_patches arguments (image inside the batch, 0 <= S <= 2^20, no NULL pointer)");
+    RpnAnchorGrid grid;
+    RpnGatherMaps maps;
+    int off = 0;
+    for (int l = 0; l < 5; ++l) {
+        char pn[8];
+        snprintf(pn, sizeof pn, "p%d", l + 2);
+        const Tens& t = c->t[pn];
+        const RpnLevel& lv = c->rl_host.lv[l];
+        if (t.st != 0 || !t.p) return fail(c, APSE_E_INVALID, "apse_rpn_patches needs a context that stores f32 maps (compute_dtype 0)");
+        if (t.H != lv.H || t.W != lv.W || t.C != 256) return fail(c, APSE_E_STATE, "apse_rpn_patches: FPN maps and RPN levels disagree");
+        maps.p[l] = t.p + (size_t)image * t.H * t.W * 256;
+        grid.H[l] = lv.H; grid.W[l] = lv.W; grid.stride[l] = lv.stride; grid.off[l] = off;
+        off += lv.n;
+        memcpy(grid.base[l], lv.base, sizeof lv.base);
+    }
+    grid.off[5] = off;
+    if (S == 0) return APSE_OK;
+    hipStream_t s = (hipStream_t)stream;
+    int rc = lane_join(c, s);          // reads p2..p6 only (written on the caller's stream): nothing for the lane to follow
+    if (rc) return rc;
+    rc = apse_k_rpn_gather(&grid, &maps, anchor_idx, S, x, slots, anchor_boxes, levels, s);
+    return rc ? fail(c, rc, "apse_rpn_patches: gather launch failed") : APSE_OK;
+}
+
 int apse_debug_tensor(apse_ctx* c, const char* name, void* dst, size_t max_bytes, size_t* bytes, void* stream) {
     if (!c || !c->finalized) return fail(c, APSE_E_STATE, "not finalized");
     const apse_config& g = c->cfg;

@@ -469,7 +469,7 @@ static int add_box_predictor(apse_ctx* c, const Tens& in) {
 }
 
 // ------------------------------------------------------------------------------------------------ RPN selection plans
-static void cell_anchors3(int size, float (*base)[4]) {          // DefaultAnchorGenerator.generate_cell_anchors: doubles -> f32
+void apse_cell_anchors3(int size, float (*base)[4]) {          // DefaultAnchorGenerator.generate_cell_anchors: doubles -> f32
     static const double ratios[3] = {0.5, 1.0, 2.0};
     for (int a = 0; a < 3; ++a) {
         const double area = (double)size * size;
@@ -490,7 +490,7 @@ void rpn_select_plan(const float* const head[5], const int H[5], const int W[5],
         L.head = head[l]; L.H = H[l]; L.W = W[l]; L.stride = strides[l];
         L.n = H[l] * W[l] * 3;
         L.k = L.n < pre_topk ? L.n : pre_topk;
-        cell_anchors3(sizes[l], L.base);
+        apse_cell_anchors3(sizes[l], L.base);
     }
     // top-k tournament plan
     out->stages.clear();
@@ -541,7 +541,7 @@ void c4_rpn_desc(const float* head, int H, int W, int ld, int pre_topk, C4Rpn* R
     R.n = H * W * 15;
     R.k = R.n < pre_topk ? R.n : pre_topk;
     static const int sizes[5] = {32, 64, 128, 256, 512};
-    for (int si = 0; si < 5; ++si) cell_anchors3(sizes[si], R.base + 3 * si);          // sizes outer, ratios inner
+    for (int si = 0; si < 5; ++si) apse_cell_anchors3(sizes[si], R.base + 3 * si);          // sizes outer, ratios inner
 }
 
 int build_plan(apse_ctx* c) {

@@ -1,5 +1,5 @@
 // What the training GEMMs (mask_train.hip: wgrad_mfma, conv3x3_mfma; box_train.hip: fc_gemm) share.  Internal device header:
-// included by those two files only.
+// included by those two files, and by rpn_train.hip for block_sum_d.
 //
 // The tile.  A block of 256 threads owns a 128 x 128 tile of C = A B: 4 waves as 2 x 2, each 2 x 2 MFMA tiles of 32 x 32
 // (v_mfma_f32_32x32x2_f32).  The reduction runs in stages of kKT = 32 steps through an LDS double buffer; the global loads of

@@ -438,6 +438,45 @@ class TrackRCNN:
         host = counts.cpu()
         return [boxes[b, :int(host[b])] for b in range(B)]
 
+    def rpn_level_shapes(self):
+        """The (H, W) of p2 .. p6 of the current context: the five anchor grids (3 anchors per position, (level, y, x, a) order)."""
+        if self.c4:
+            raise NotImplementedError("RPN-head training covers FPN models (p2 .. p6): not available for C4 (Res5ROIHeads) models")
+        out = []
+        for name in ("p2", "p3", "p4", "p5", "p6"):
+            shp = (C.c_int * 3)()
+            self._call("apse_feature_shape", name.encode(), C.byref(shp))
+            out.append((int(shp[1]), int(shp[2])))
+        return out
+
+    def rpn_anchor_targets(self, gt_boxes, image=0, iou_thresholds=(0.3, 0.7)):
+        """RPNOutputs._get_ground_truth without the random draw for the anchors of the current context against ``gt_boxes``
+        ([G][4] in resized-image pixels): (labels int32 [A] in {1, 0, -1}, matched_idx int32 [A], matched_iou f32 [A]) on the device
+        (apse_rpn_anchor_labels; FPN models only).  The images of a batch share one size and so one set of anchors: ``image`` only
+        has to name an image of the batch."""
+        from . import rpn_head
+        shapes = self.rpn_level_shapes()
+        if not 0 <= int(image) < int(self._cfg_c.max_batch):
+            raise ValueError("rpn_anchor_targets: image %d is outside the context's batch of %d" % (image, self._cfg_c.max_batch))
+        gt = torch.as_tensor(gt_boxes, dtype=torch.float32).reshape(-1, 4).to(self.device)
+        return rpn_head.anchor_labels(shapes, gt, iou_thresholds[0], iou_thresholds[1])
+
+    def rpn_patches(self, anchor_idx, image=0):
+        """For the anchors ``anchor_idx`` ([S] global indices) of image ``image`` of the last ``apse_backbone`` run: (patches f32
+        [S][2304] in rpn_head.conv's (c, kh, kw) input order, slots int32 [S], anchor boxes f32 [S][4], levels int32 [S]) on the device
+        (apse_rpn_patches; FPN models with f32 maps only -- the RPN-head training input, networks/rpn_head.py)."""
+        if self.c4:
+            raise NotImplementedError("rpn_patches reads p2 .. p6: not available for C4 (Res5ROIHeads) models")
+        idx = torch.as_tensor(anchor_idx).reshape(-1).to(self.device, torch.int32).contiguous()
+        S = idx.shape[0]
+        x = torch.empty((S, 2304), dtype=torch.float32, device=self.device)
+        slots = torch.empty(S, dtype=torch.int32, device=self.device)
+        boxes = torch.empty((S, 4), dtype=torch.float32, device=self.device)
+        levels = torch.empty(S, dtype=torch.int32, device=self.device)
+        self._call("apse_rpn_patches", int(image), _lib.ptr(idx), S, _lib.ptr(x), _lib.ptr(slots), _lib.ptr(boxes), _lib.ptr(levels),
+                   _lib.stream_ptr())
+        return x, slots, boxes, levels
+
     def flops(self, batch, proposals, detections):
         return float(_lib.load().apse_flops(self._ctx, batch, proposals, detections))
 

@@ -261,7 +261,10 @@ class MaskTrainLoader:
     def __iter__(self):
         return self
 
-    def __next__(self):
+    def next_items(self):
+        """The per-image items (``image_item`` / ``augmented_item``) of the next batch, with the draws in their fixed order: the
+        image order, then per image the size and augmentation parameters or the host flip.  The loaders that subclass this one
+        share it and differ in how they join the items."""
         items = []
         for _ in range(self.ims_per_batch):
             if not self._order:
@@ -274,5 +277,9 @@ class MaskTrainLoader:
                 continue
             flipped = bool(self.flip and self.rng.random() < 0.5)
             items.append(self.image_item(d, flipped))
+        return items
+
+    def __next__(self):
+        items = self.next_items()
         feats = torch.cat([i[0] for i in items])[:self.max_rois]
         return feats, torch.cat([i[1] for i in items])[:self.max_rois], torch.cat([i[2] for i in items])[:self.max_rois]

@@ -94,17 +94,6 @@ class BoxTrainLoader(MaskTrainLoader):
         return self._sample(boxes, classes, d)
 
     def __next__(self):
-        items = []
-        for _ in range(self.ims_per_batch):
-            if not self._order:
-                self._order = [int(i) for i in self.rng.permutation(len(self.dicts))]
-            d = self.dicts[self._order.pop(0)]
-            if self.device_path:
-                from . import augment as aug
-                size = aug.draw_size(self.rng, self.min_sizes, self.sampling)
-                items.append(self.augmented_item(d, size, aug.draw_params(self.rng, self.flip, self.augment)))
-                continue
-            flipped = bool(self.flip and self.rng.random() < 0.5)
-            items.append(self.image_item(d, flipped))
+        items = self.next_items()
         self.last_counts = [i[4] for i in items]
         return tuple(torch.cat([i[k] for i in items]) for k in range(4))

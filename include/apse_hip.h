@@ -726,6 +726,57 @@ int apse_box_loss_backward(const float* logits_dev, const float* deltas_dev, con
                            const float* grad_cls_dev, const float* grad_box_dev, float* dlogits_dev, float* ddeltas_dev,
                            void* stream);
 
+/* ---- RPN-head training (csrc/rpn_train.hip): the f32 steps of fine-tuning proposal_generator.rpn_head.conv / objectness_logits /
+ * anchor_deltas of a frozen FPN detector: anchor labelling (RPNOutputs._get_ground_truth of detectron2 0.1.2 without the random
+ * draw), the gather of the 3 x 3 x 256 input patches of the sampled anchors, and RPNOutputs.losses (loss_rpn_cls, loss_rpn_loc) with
+ * its gradient.  The losses read the head only at the sampled anchors, so on the gathered rows X [S][2304] the head is three FC
+ * layers, run on the box trainer's GEMM entries above (conv: O = 256, K = 2304, ReLU; objectness_logits: O = 3; anchor_deltas:
+ * O = 12; S <= APSE_BOX_TRAIN_MAX_N per step) with the checkpoint's tensors as they are.  DESIGN.md "RPN-head training" has the
+ * rules.  Apart from the gather, which reads a context, every entry is stateless, enqueues on `stream` only and allocates nothing;
+ * the caller passes the workspace.  Deterministic: no float atomics, every sum has an order fixed by the shapes, ties go to the
+ * lowest index.  Device arrays need only the alignment of their element type (boxes are read and written element by element).
+ * Errors: APSE_E_INVALID outside the limits, checked before anything is launched, with the text in
+ * apse_last_error(NULL) (the gather: in the context's).
+ * Anchors: sizes 32 .. 512 on strides 4 .. 64, ratios (0.5, 1, 2), offset 0, global index in (level, y, x, a) order; the cell
+ * anchors are the f32 roundings of Python doubles, computed by the function the inference plan uses, and the kernels generate the
+ * boxes from the index as the inference decode does.  A = 3 sum(H W) over the five levels. */
+/* Workspace bytes that cover the labelling of A anchors against G ground truths and the loss of S rows (0 outside the limits). */
+size_t apse_rpn_train_workspace_bytes(int A, int G, int S);
+/* level_h5 / level_w5 (HOST, read before the call returns): the sizes of p2 .. p6.  gt_boxes_dev [G][4] in resized-image pixels.
+ * Per anchor: IoU = inter > 0 ? inter / (area_gt + area_anchor - inter) : 0 in f32 against every ground truth; matched_idx = the
+ * ground truth of highest IoU (lowest index on ties), matched_iou = that IoU; labels (int32) = 1 at IoU >= iou_hi, 0 below
+ * iou_lo, -1 between.  Then Matcher.set_low_quality_matches_, literally: every anchor whose IoU to some ground truth EQUALS that
+ * ground truth's maximum over all anchors gets label 1 (a ground truth whose maximum is 0 included: then every anchor that does
+ * not overlap it); matched_idx stays the anchor's own argmax.  The maximum is taken in two passes: per block of 1024 anchors into
+ * the workspace, then over the blocks in block order.  Anchors outside the image are kept.  G = 0: every label 0, index 0,
+ * IoU 0 (no workspace needed).  Limits: 0 <= G <= 4096, levels of at least 1 x 1, A <= 2^22. */
+int apse_rpn_anchor_labels(const int* level_h5, const int* level_w5, const float* gt_boxes_dev, int G, float iou_lo, float iou_hi,
+                           int* labels_dev, int* matched_idx_dev, float* matched_iou_dev, void* ws, size_t ws_bytes, void* stream);
+/* For S anchors (global indices, anchor_idx_dev [S]) of image `image` of the last apse_backbone run: x_dev [S][2304] = the 3 x 3
+ * neighbourhood of the anchor's position on its own level (p2 .. p6) in (c, kh, kw) order -- the input order of
+ * proposal_generator.rpn_head.conv.weight [256][256][3][3] read as [256][2304] -- with zeros outside the map; per row the anchor
+ * slot a = index % 3 (slots_dev), the anchor box (anchor_boxes_dev [S][4]) and the level 0 .. 4 (levels_dev).  Two rows may name
+ * the same anchor or position.  An index outside 0 .. A - 1 gives a zero row, slot 0, a zero box and level -1.  Joins the tail lane
+ * first.  FPN contexts that store f32 maps only.  0 <= S <= 2^20. */
+int apse_rpn_patches(apse_ctx* ctx, int image, const int* anchor_idx_dev, int S, float* x_dev, int* slots_dev,
+                     float* anchor_boxes_dev, int* levels_dev, void* stream);
+/* RPNOutputs.losses on the sampled rows: logits [S][3], deltas [S][12], per row the slot a (0 .. 2), the label (1 positive,
+ * 0 negative, negative values: the row is ignored), the anchor box and the matched ground-truth box [S][4].  Only column a of the
+ * logits and columns 4 a .. 4 a + 3 of the deltas take part.  loss_rpn_cls = sum of binary cross-entropy with logits x 1 / norm;
+ * loss_rpn_loc = sum over the positive rows of smooth_l1 (beta < 1e-5: L1) against Box2BoxTransform(1, 1, 1, 1).get_deltas(anchor,
+ * gt) x 1 / norm; norm = batch_size_per_image x images.  The sums run in f64 through a fixed tree and are rounded once.
+ * out8 = {loss_rpn_cls, loss_rpn_loc, num_pos, num_neg, share of positive rows with logit > 0, share of negative rows with
+ * logit < 0, 0, 0}.  S = 0 enqueues nothing.  0 <= S <= 2^20, norm >= 1. */
+int apse_rpn_loss_forward(const float* logits_dev, const float* deltas_dev, const int* slots_dev, const int* labels_dev,
+                          const float* anchor_boxes_dev, const float* gt_boxes_dev, int S, int norm, float smooth_l1_beta,
+                          float* out8_dev, void* ws, size_t ws_bytes, void* stream);
+/* dlogits [S][3] = (sigmoid - label) / norm x grad_cls[0] on column a; ddeltas [S][12] = d smooth_l1 / norm x grad_loc[0] on
+ * columns 4 a .. 4 a + 3 of the positive rows; exactly 0 elsewhere.  grad_cls / grad_loc: device scalars (NULL: 1). */
+int apse_rpn_loss_backward(const float* logits_dev, const float* deltas_dev, const int* slots_dev, const int* labels_dev,
+                           const float* anchor_boxes_dev, const float* gt_boxes_dev, int S, int norm, float smooth_l1_beta,
+                           const float* grad_cls_dev, const float* grad_loc_dev, float* dlogits_dev, float* ddeltas_dev,
+                           void* stream);
+
 /* ---- Training augmentation (csrc/augment.hip): the transforms the reference's DatasetMapper applies after ResizeShortestEdge
  * (dcnn/utils/UAV_utils.py:311-449) -- RandomFlip, RandomBrightness, RandomSaturation, RandomContrast, RandomLighting of
  * detectron2 0.1.2 / fvcore, in that order, on resized u8 BGR images.  The rules, with the type of every operation (numpy 1.18
