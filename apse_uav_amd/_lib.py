@@ -19,7 +19,8 @@ LIB_PATH = os.environ.get("APSE_HIP_LIB") or _TREE_LIB
 # entries that only tools/ and the operator tests use: a build from before they existed may still be loaded through
 # APSE_HIP_LIB (load())
 TOOL_ENTRIES = ("apse_winograd_pack_filter", "apse_winograd_conv2d", "apse_lane_stats", "apse_rpn_select", "apse_box_inference",
-                "apse_c4_rpn_select")
+                "apse_c4_rpn_select", "apse_rpn_select_train", "apse_rpn_train_proposals_workspace_bytes", "apse_rpn_train_proposals",
+                "apse_set_rpn_head")
 
 APSE_OK = 0
 
@@ -202,6 +203,10 @@ SIGNATURES = {
     "apse_rpn_loss_forward": ([vp, vp, vp, vp, vp, vp, i, i, f, vp, vp, sz, vp], i),
     "apse_rpn_loss_backward": ([vp, vp, vp, vp, vp, vp, i, i, f, vp, vp, vp, vp, vp], i),
     "apse_augment_u8": ([vp, i, i, i, vp, vp, vp, vp, vp], i),
+    "apse_rpn_select_train": ([C.POINTER(vp), C.POINTER(i), C.POINTER(i), i, i, i, i, i, i, f, i, vp, vp, vp, vp, vp, vp, vp, vp, vp], i),
+    "apse_rpn_train_proposals_workspace_bytes": ([i, i], sz),
+    "apse_rpn_train_proposals": ([vp, i, i, i, vp, vp, vp, vp, sz, vp], i),
+    "apse_set_rpn_head": ([vp, vp, vp, vp, vp, vp, vp, vp], i),
 }
 del vp, i, f, sz
 EXPORTS = list(SIGNATURES)

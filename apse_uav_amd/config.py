@@ -118,7 +118,9 @@ def get_cfg():
                                  "ASPECT_RATIOS": ((0.5, 1.0, 2.0),), "OFFSET": 0.0},
             "RPN": {"IN_FEATURES": ("p2", "p3", "p4", "p5", "p6"), "PRE_NMS_TOPK_TEST": 1000,
                     "POST_NMS_TOPK_TEST": 1000, "NMS_THRESH": 0.7, "BBOX_REG_WEIGHTS": (1.0, 1.0, 1.0, 1.0),
-                    "MIN_SIZE": 0},
+                    "MIN_SIZE": 0,
+                    # the reference's Base-RCNN-FPN.yaml; read by the training path only (TrackRCNN.train_proposals)
+                    "PRE_NMS_TOPK_TRAIN": 2000, "POST_NMS_TOPK_TRAIN": 1000},
             "ROI_HEADS": {"NAME": "StandardROIHeads", "IN_FEATURES": ("p2", "p3", "p4", "p5"), "NUM_CLASSES": 80,
                           "SCORE_THRESH_TEST": 0.05, "NMS_THRESH_TEST": 0.5},
             "ROI_BOX_HEAD": {"NAME": "FastRCNNConvFCHead", "NUM_FC": 2, "FC_DIM": 1024, "POOLER_RESOLUTION": 7,

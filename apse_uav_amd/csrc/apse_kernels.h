@@ -138,6 +138,10 @@ size_t apse_c4_nms_scratch_bytes(int B);
 int apse_k_c4_rpn(const C4Rpn* R, int pre, int post, float img_h, float img_w, float scale_clamp, float thr, float* dec_boxes,
                   float* dec_scores, int* dec_valid, void* scratch, float* props, float* prop_scores, int* prop_entry,
                   int* prop_count, int B, hipStream_t s);
+size_t apse_rpn_train_scratch_bytes(int B);
+int apse_k_rpn_train_select(const RpnLevels* L, int post, float img_h, float img_w, float scale_clamp, float thr, int level_mask,
+                            uint64_t* keys, float* dec_boxes, float* dec_scores, int* dec_valid, void* scratch, float* props,
+                            float* prop_scores, int* prop_entry, int* prop_count, int B, hipStream_t s);
 int apse_k_pack_detections(const float* det_boxes, const float* det_scores, const int* det_entry, const int* det_cnt, int B,
                            int Kd, int ncls, float* pk_boxes, float* pk_scores, int* pk_cls, int* pk_img, int* pk_roi,
                            int* pk_total, int* pk_offset, unsigned long long* zero_sums, hipStream_t s);
@@ -180,4 +184,6 @@ int apse_k_augment(const uint8_t* src, int B, int H, int W, const AugmentBatch* 
 // ---- rpn_train.hip
 int apse_k_rpn_gather(const RpnAnchorGrid* grid, const RpnGatherMaps* maps, const int* anchor_idx, int S, float* x, int* slots,
                       float* anchor_boxes, int* levels, hipStream_t s);
+int apse_k_pack_oihw(const float* w, int Cout, int Cin, int KH, int KW, int cin_p, int KWCp, int row0, float* out, hipStream_t s);
+int apse_k_winograd_filters(const float* oihw, int Cout, int Cin, float* u, hipStream_t s);
 }

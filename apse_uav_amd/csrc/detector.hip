@@ -950,6 +950,85 @@ int apse_rpn_patches(apse_ctx* c, int image, const int* anchor_idx, int S, float
     return rc ? fail(c, rc, "apse_rpn_patches: gather launch failed") : APSE_OK;
 }
 
+// ---- training-time proposals and the RPN-head refresh (include/apse_hip.h "Training-time proposals")
+static int need_fpn_f32(apse_ctx* c, const char* who) {
+    if (!c || !c->finalized) return fail(c, APSE_E_STATE, "weights not finalized");
+    if (c->c4) return fail(c, APSE_E_INVALID, std::string(who) + " works on the five FPN levels: not available under C4 (arch 1)");
+    if (c->cfg.compute_dtype != 0) return fail(c, APSE_E_INVALID, std::string(who) + " needs an f32 context (compute_dtype 0)");
+    return APSE_OK;
+}
+
+static size_t train_ws_dec_offset(int batch) { return (apse_rpn_train_scratch_bytes(batch) + 15) & ~(size_t)15; }
+
+size_t apse_rpn_train_proposals_workspace_bytes(int batch, int pre_topk) {
+    if (batch < 1 || batch > 64 || pre_topk < 1 || pre_topk > APSE_RPN_TRAIN_MAX_PRE_TOPK) return 0;
+    // selection scratch, dec_boxes / dec_scores / dec_valid [batch][5 * pre_topk], entry [batch][APSE_RPN_TRAIN_MAX_POST_TOPK]
+    return train_ws_dec_offset(batch) + (size_t)batch * 5 * pre_topk * 24 + (size_t)batch * APSE_RPN_TRAIN_MAX_POST_TOPK * 4;
+}
+
+int apse_rpn_train_proposals(apse_ctx* c, int batch, int pre_topk, int post_topk, float* boxes, float* scores, int* count, void* ws,
+                             size_t ws_bytes, void* stream) {
+    int rc = need_fpn_f32(c, "apse_rpn_train_proposals");
+    if (rc) return rc;
+    if (batch < 1 || batch > c->cfg.max_batch) return fail(c, APSE_E_INVALID, "apse_rpn_train_proposals: batch out of range");
+    if (pre_topk < 1 || pre_topk > APSE_RPN_TRAIN_MAX_PRE_TOPK)
+        return fail(c, APSE_E_INVALID, "apse_rpn_train_proposals: pre_topk outside 1 .. APSE_RPN_TRAIN_MAX_PRE_TOPK (2048)");
+    if (post_topk < 1 || post_topk > APSE_RPN_TRAIN_MAX_POST_TOPK)
+        return fail(c, APSE_E_INVALID, "apse_rpn_train_proposals: post_topk outside 1 .. APSE_RPN_TRAIN_MAX_POST_TOPK (2048)");
+    if (!boxes || !scores || !count || !ws) return fail(c, APSE_E_INVALID, "apse_rpn_train_proposals: null pointer");
+    if (((uintptr_t)ws & 15) || ws_bytes < apse_rpn_train_proposals_workspace_bytes(batch, pre_topk))
+        return fail(c, APSE_E_INVALID, "apse_rpn_train_proposals: workspace too small or not 16-byte aligned");
+    hipStream_t s = (hipStream_t)stream;
+    const apse_config& g = c->cfg;
+    // the convolutions rewrite the RPN maps that the lane's selection of the last forward may still read
+    if ((rc = lane_join(c, s))) return rc;
+    if ((rc = run_plan(c, c->rpnhead, batch, s))) return rc;
+    RpnLevels L = c->rl_host;
+    L.pre_topk = pre_topk;
+    for (int l = 0; l < 5; ++l) L.lv[l].k = L.lv[l].n < pre_topk ? L.lv[l].n : pre_topk;
+    char* p = reinterpret_cast<char*>(ws) + train_ws_dec_offset(batch);
+    float* dec_boxes = reinterpret_cast<float*>(p); p += (size_t)batch * 5 * pre_topk * 16;
+    float* dec_scores = reinterpret_cast<float*>(p); p += (size_t)batch * 5 * pre_topk * 4;
+    int* dec_valid = reinterpret_cast<int*>(p); p += (size_t)batch * 5 * pre_topk * 4;
+    int* entry = reinterpret_cast<int*>(p);
+    rc = apse_k_rpn_train_select(&L, post_topk, (float)g.image_h, (float)g.image_w, (float)log(1000.0 / 16.0), g.rpn_nms, 31, nullptr,
+                                 dec_boxes, dec_scores, dec_valid, ws, boxes, scores, entry, count, batch, s);
+    if (rc) return fail(c, rc, "apse_rpn_train_proposals: selection launch failed");
+    return lane_follow(c, s);          // the lane's next selection follows the RPN maps written here
+}
+
+int apse_set_rpn_head(apse_ctx* c, const float* conv_w, const float* conv_b, const float* obj_w, const float* obj_b,
+                      const float* delta_w, const float* delta_b, void* stream) {
+    int rc = need_fpn_f32(c, "apse_set_rpn_head");
+    if (rc) return rc;
+    if (!conv_w || !conv_b || !obj_w || !obj_b || !delta_w || !delta_b) return fail(c, APSE_E_INVALID, "apse_set_rpn_head: null pointer");
+    // the plan's RPN steps: five 3 x 3 convolutions 256 -> 256 (one per level, each with its own copy of the filters) and the
+    // fused 1 x 1 head of 3 + 12 rows
+    if (c->rpnhead.size() != 6) return fail(c, APSE_E_STATE, "apse_set_rpn_head: unexpected RPN plan");
+    for (int i = 0; i < 6; ++i) {
+        const ConvParams& q = c->rpnhead[i].c.p;
+        const bool ok = c->rpnhead[i].kind == S_CONV && q.w && !q.w16 && q.bias && q.cin_log2 == 8 &&
+                        (i < 5 ? (q.KH == 3 && q.KW == 3 && q.Cout == 256 && q.KWCp == 768) : (q.KH == 1 && q.KW == 1 && q.Cout == 15 && q.KWCp == 256));
+        if (!ok) return fail(c, APSE_E_STATE, "apse_set_rpn_head: unexpected RPN plan");
+    }
+    hipStream_t s = (hipStream_t)stream;
+    if ((rc = lane_join(c, s))) return rc;
+    for (int i = 0; i < 5 && !rc; ++i) {
+        const ConvParams& q = c->rpnhead[i].c.p;
+        rc = apse_k_pack_oihw(conv_w, 256, 256, 3, 3, 256, q.KWCp, 0, const_cast<float*>(q.w), s);
+        if (!rc && q.wu) rc = apse_k_winograd_filters(conv_w, 256, 256, const_cast<float*>(q.wu), s);
+        if (!rc && hipMemcpyAsync(const_cast<float*>(q.bias), conv_b, 256 * sizeof(float), hipMemcpyDeviceToDevice, s) != hipSuccess) rc = APSE_E_HIP;
+    }
+    const ConvParams& h = c->rpnhead[5].c.p;
+    float* hw = const_cast<float*>(h.w);
+    float* hb = const_cast<float*>(h.bias);
+    if (!rc) rc = apse_k_pack_oihw(obj_w, 3, 256, 1, 1, 256, h.KWCp, 0, hw, s);
+    if (!rc) rc = apse_k_pack_oihw(delta_w, 12, 256, 1, 1, 256, h.KWCp, 3, hw, s);
+    if (!rc && hipMemcpyAsync(hb, obj_b, 3 * sizeof(float), hipMemcpyDeviceToDevice, s) != hipSuccess) rc = APSE_E_HIP;
+    if (!rc && hipMemcpyAsync(hb + 3, delta_b, 12 * sizeof(float), hipMemcpyDeviceToDevice, s) != hipSuccess) rc = APSE_E_HIP;
+    return rc ? fail(c, rc, "apse_set_rpn_head: launch failed") : APSE_OK;
+}
+
 int apse_debug_tensor(apse_ctx* c, const char* name, void* dst, size_t max_bytes, size_t* bytes, void* stream) {
     if (!c || !c->finalized) return fail(c, APSE_E_STATE, "not finalized");
     const apse_config& g = c->cfg;

@@ -153,6 +153,8 @@ struct RpnSelectPlan {
     int final_slot[5];
 };
 void rpn_select_plan(const float* const head[5], const int H[5], const int W[5], int head_ld, int pre_topk, RpnSelectPlan* out);
+// The five levels alone (head rows, cell anchors, n, k = min(pre_topk, n)): all the training-time selection needs
+void rpn_levels_desc(const float* const head[5], const int H[5], const int W[5], int head_ld, int pre_topk, RpnLevels* out);
 // The C4 RPN descriptor: head rows, the 15 cell anchors (sizes outer, ratios inner), n and k
 void c4_rpn_desc(const float* head, int H, int W, int ld, int pre_topk, C4Rpn* R);
 int build_plan(apse_ctx* c);        // FPN (cfg.arch 0)

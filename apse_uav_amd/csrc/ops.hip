@@ -245,6 +245,38 @@ int apse_rpn_select(const float* const* heads_dev, const int* H, const int* W, i
     return rc;
 }
 
+// The training-time selection on injected inputs (select_nms.hip "training-time FPN selection"): apse_rpn_select's arguments and
+// output layouts, lists of up to APSE_RPN_TRAIN_MAX_PRE_TOPK per level.
+int apse_rpn_select_train(const float* const* heads_dev, const int* H, const int* W, int head_ld, int B, int image_h, int image_w,
+                          int pre_topk, int post_topk, float nms_thr, int level_mask, unsigned long long* keys_dev,
+                          float* dec_boxes_dev, float* dec_scores_dev, int* dec_valid_dev, float* props_dev, float* prop_scores_dev,
+                          int* prop_entry_dev, int* prop_count_dev, void* stream) {
+    if (!heads_dev || !H || !W || !dec_boxes_dev || !dec_scores_dev || !dec_valid_dev || !props_dev || !prop_scores_dev ||
+        !prop_entry_dev || !prop_count_dev)
+        return apse_fail_global(APSE_E_INVALID, "apse_rpn_select_train: null pointer");
+    level_mask &= 31;
+    if (!level_mask) return apse_fail_global(APSE_E_INVALID, "apse_rpn_select_train: empty level mask");
+    if (B < 1 || B > 64) return apse_fail_global(APSE_E_INVALID, "apse_rpn_select_train: batch outside 1 .. 64");
+    if (head_ld < 15) return apse_fail_global(APSE_E_INVALID, "apse_rpn_select_train: head_ld below 15");
+    if (pre_topk < 1 || pre_topk > APSE_RPN_TRAIN_MAX_PRE_TOPK)
+        return apse_fail_global(APSE_E_INVALID, "apse_rpn_select_train: pre_topk outside 1 .. APSE_RPN_TRAIN_MAX_PRE_TOPK (2048)");
+    if (post_topk < 1 || post_topk > APSE_RPN_TRAIN_MAX_POST_TOPK)
+        return apse_fail_global(APSE_E_INVALID, "apse_rpn_select_train: post_topk outside 1 .. APSE_RPN_TRAIN_MAX_POST_TOPK (2048)");
+    for (int l = 0; l < 5; ++l)
+        if (!heads_dev[l] || H[l] < 1 || W[l] < 1 || (long long)H[l] * W[l] * 3 > (1ll << 30))
+            return apse_fail_global(APSE_E_INVALID, "apse_rpn_select_train: bad level");
+    hipStream_t s = (hipStream_t)stream;
+    RpnLevels L;
+    rpn_levels_desc(heads_dev, H, W, head_ld, pre_topk, &L);
+    DevBuf scratch;
+    if (!scratch.alloc(apse_rpn_train_scratch_bytes(B))) return apse_fail_global(APSE_E_NOMEM, "apse_rpn_select_train: scratch");
+    int rc = apse_k_rpn_train_select(&L, post_topk, (float)image_h, (float)image_w, (float)log(1000.0 / 16.0), nms_thr, level_mask,
+                                     reinterpret_cast<uint64_t*>(keys_dev), dec_boxes_dev, dec_scores_dev, dec_valid_dev, scratch.p,
+                                     props_dev, prop_scores_dev, prop_entry_dev, prop_count_dev, B, s);
+    if (hipStreamSynchronize(s) != hipSuccess && !rc) rc = APSE_E_HIP;
+    return rc ? apse_fail_global(rc, "apse_rpn_select_train: launch failed") : APSE_OK;
+}
+
 int apse_box_inference(const float* pred_dev, int ld, int K, const float* props_dev, const int* prop_cnt_dev, int P, int B,
                        int image_h, int image_w, float score_thresh, float nms_thr, int dets_per_image, int wide,
                        float* probs_dev, float* cand_boxes_dev, float* cand_scores_dev, int* cand_valid_dev, float* det_boxes_dev,

@@ -479,19 +479,23 @@ void apse_cell_anchors3(int size, float (*base)[4]) {          // DefaultAnchorG
     }
 }
 
-void rpn_select_plan(const float* const head[5], const int H[5], const int W[5], int head_ld, int pre_topk, RpnSelectPlan* out) {
+void rpn_levels_desc(const float* const head[5], const int H[5], const int W[5], int head_ld, int pre_topk, RpnLevels* out) {
     static const int sizes[5] = {32, 64, 128, 256, 512};
     static const int strides[5] = {4, 8, 16, 32, 64};
-    memset(&out->levels, 0, sizeof(out->levels));
-    out->levels.head_ld = head_ld;
-    out->levels.pre_topk = pre_topk;
+    memset(out, 0, sizeof(*out));
+    out->head_ld = head_ld;
+    out->pre_topk = pre_topk;
     for (int l = 0; l < 5; ++l) {
-        RpnLevel& L = out->levels.lv[l];
+        RpnLevel& L = out->lv[l];
         L.head = head[l]; L.H = H[l]; L.W = W[l]; L.stride = strides[l];
         L.n = H[l] * W[l] * 3;
         L.k = L.n < pre_topk ? L.n : pre_topk;
         apse_cell_anchors3(sizes[l], L.base);
     }
+}
+
+void rpn_select_plan(const float* const head[5], const int H[5], const int W[5], int head_ld, int pre_topk, RpnSelectPlan* out) {
+    rpn_levels_desc(head, H, W, head_ld, pre_topk, &out->levels);
     // top-k tournament plan
     out->stages.clear();
     int slot = 0;

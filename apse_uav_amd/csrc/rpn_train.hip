@@ -285,9 +285,56 @@ bool grid_from_shapes(const int* H5, const int* W5, RpnAnchorGrid* g, long long*
     return true;
 }
 
+// ---------------------------------------------------------------------------------------------------------------- weight refresh
+// apse_set_rpn_head: the packing of plan.hip's pack_oihw and winograd_filters on the device, the same operations on the same
+// operands (a copy; float64 products and sums rounded separately, one rounding to f32), so the bits are those of plan time.
+// OIHW [Cout][Cin][KH][KW] -> rows row0 .. row0 + Cout - 1 of the tiled layout [.][KH][KWCp], run = (kw, cin_p).  One thread per
+// element, in the order of the output; the padding the plan zeroed is not written.
+__global__ __launch_bounds__(256) void pack_oihw_dev(const float* __restrict__ w, int Cout, int Cin, int KH, int KW, int cin_p,
+                                                     int KWCp, int row0, float* __restrict__ out) {
+    const size_t total = (size_t)Cout * KH * KW * Cin;
+    const size_t i = (size_t)blockIdx.x * 256 + threadIdx.x;
+    if (i >= total) return;
+    const int ci = (int)(i % Cin);
+    const int s = (int)((i / Cin) % KW);
+    const int r = (int)((i / ((size_t)Cin * KW)) % KH);
+    const int o = (int)(i / ((size_t)Cin * KW * KH));
+    out[((size_t)(row0 + o) * KH + r) * KWCp + s * cin_p + ci] = w[(((size_t)o * Cin + ci) * KH + r) * KW + s];
+}
+
+// U = G g G^T per (cout, cin), stored [cin_p / 8][16][Cout][8] (xi = 4 i + j).  One thread per (cout, cin).
+__global__ __launch_bounds__(256) void winograd_filters_dev(const float* __restrict__ oihw, int Cout, int Cin, float* __restrict__ u) {
+    const double G[4][3] = {{1, 0, 0}, {0.5, 0.5, 0.5}, {0.5, -0.5, 0.5}, {0, 0, 1}};
+    const int idx = blockIdx.x * 256 + threadIdx.x;
+    if (idx >= Cout * Cin) return;
+    const int o = idx % Cout, ci = idx / Cout;               // neighbouring threads write neighbouring 32-byte runs
+    const float* gp = oihw + ((size_t)o * Cin + ci) * 9;
+    double g[9];
+    for (int k = 0; k < 9; ++k) g[k] = (double)gp[k];
+    double t[4][3];                                          // G g
+    for (int i = 0; i < 4; ++i)
+        for (int s = 0; s < 3; ++s) t[i][s] = G[i][0] * g[s] + G[i][1] * g[3 + s] + G[i][2] * g[6 + s];
+    for (int i = 0; i < 4; ++i)
+        for (int j = 0; j < 4; ++j) {
+            const double v = t[i][0] * G[j][0] + t[i][1] * G[j][1] + t[i][2] * G[j][2];      // (G g) G^T
+            u[(((size_t)(ci / 8) * 16 + 4 * i + j) * Cout + o) * 8 + (ci & 7)] = (float)v;
+        }
+}
+
 }  // namespace
 
 extern "C" {
+
+int apse_k_pack_oihw(const float* w, int Cout, int Cin, int KH, int KW, int cin_p, int KWCp, int row0, float* out, hipStream_t s) {
+    const size_t total = (size_t)Cout * KH * KW * Cin;
+    hipLaunchKernelGGL(pack_oihw_dev, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, s, w, Cout, Cin, KH, KW, cin_p, KWCp, row0, out);
+    return hipGetLastError() == hipSuccess ? APSE_OK : APSE_E_HIP;
+}
+
+int apse_k_winograd_filters(const float* oihw, int Cout, int Cin, float* u, hipStream_t s) {
+    hipLaunchKernelGGL(winograd_filters_dev, dim3((Cout * Cin + 255) / 256), dim3(256), 0, s, oihw, Cout, Cin, u);
+    return hipGetLastError() == hipSuccess ? APSE_OK : APSE_E_HIP;
+}
 
 size_t apse_rpn_train_workspace_bytes(int A, int G, int S) {
     if (A < 0 || A > kMaxAnchors || G < 0 || G > kMaxGt || S < 0 || S > kMaxRows) return 0;

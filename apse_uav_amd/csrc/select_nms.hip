@@ -855,6 +855,292 @@ __global__ __launch_bounds__(1024) void c4_nms_scan(C4Nms S, const float* __rest
     if (tid == 0) out_count[b] = cnt;
 }
 
+// ---------------------------------------------------------------- training-time FPN selection
+// find_top_rpn_proposals with the training limits (PRE_NMS_TOPK_TRAIN 2000 per level, POST_NMS_TOPK_TRAIN 1000): the rules of the
+// FPN path above, but lists of up to TR_MAX = 2048 keys per (level, image), which the 1024-slot tournament lists, the 1024-box
+// NMS slot and the 64 KiB rank merge do not hold.  One slot per (level, image), slot = image * 5 + level:
+//   train_rpn_select : one block per slot.  A level of more than TR_MAX anchors: radix select of the k-th smallest composite
+//                      key, as c4_rpn_select does, leaving as soon as the remaining bin is wholly inside the top k (random
+//                      scores: after the four score bytes); then one bitonic sort of <= 2048 keys in LDS, the key list, and
+//                      rpn_decode's arithmetic on the sorted anchors (decode, clip, nonempty flag, running max coordinate).
+//   train_nms_prepare: ordered compaction of the slot's valid boxes (they arrive sorted), shifted by cat * (max_coord + 1).
+//   train_nms_matrix : 64 x 64 tiles of the suppression bit matrix in HBM, [2048][32] u64 per slot (nms_matrix's arithmetic).
+//   train_nms_scan   : greedy scan per slot; stops once post_topk rows are kept (an element behind post_topk others of its own
+//                      sorted list has a merged rank >= post_topk, so the merge below never sees it).
+//   train_rank_merge : rank merge over the five kept lists (80 KiB of keys in LDS), first post_topk.
+// The FPN and C4 kernels above are not touched by this path.
+#define TR_MAX 2048         // keys of a level's list and boxes of an NMS slot (APSE_RPN_TRAIN_MAX_PRE_TOPK, include/apse_hip.h)
+#define TR_WORDS (TR_MAX / 64)
+
+__global__ __launch_bounds__(1024) void train_rpn_select(const RpnLevels L, float img_h, float img_w, float scale_clamp,
+                                                        uint64_t* __restrict__ keys_out, float* __restrict__ boxes,
+                                                        float* __restrict__ scores, int* __restrict__ valid,
+                                                        uint32_t* __restrict__ maxc, int level_mask) {
+    __shared__ uint64_t a[TR_MAX];
+    __shared__ unsigned hist[16 * 256];                                  // [16 waves][256]
+    __shared__ uint64_t prefix_s;
+    __shared__ unsigned rank_s, fill_s;
+    __shared__ int done_s;
+    const int l = blockIdx.x, b = blockIdx.y, tid = threadIdx.x, wave = tid >> 6;
+    const RpnLevel& lv = L.lv[l];
+    const int head_ld = L.head_ld, pre = L.pre_topk;
+    const float* head = lv.head + (size_t)b * lv.H * lv.W * head_ld;
+    const int n = lv.n, k = lv.k;
+    auto key_of = [&](int e) -> uint64_t {
+        const int pix = e / 3, an = e - pix * 3;
+        return comp_key(head[(size_t)pix * head_ld + an], (uint32_t)e);
+    };
+    if (tid == 0) { prefix_s = ~0ull; rank_s = (unsigned)(k - 1); fill_s = 0u; done_s = 0; }
+    __syncthreads();
+    // radix select, 8 bits per pass from the top.  The keys are distinct, so the last pass always ends with one key in the bin
+    for (int pass = 0; pass < 8 && n > TR_MAX; ++pass) {
+        const int shift = 56 - 8 * pass;
+        const uint64_t prefix = pass == 0 ? 0ull : prefix_s;
+        for (int i = tid; i < 16 * 256; i += 1024) hist[i] = 0u;
+        __syncthreads();
+        for (int e = tid; e < n; e += 1024) {
+            const uint64_t key = key_of(e);
+            if (pass == 0 || (key >> (shift + 8)) == (prefix >> (shift + 8))) atomicAdd(&hist[wave * 256 + (int)((key >> shift) & 255u)], 1u);
+        }
+        __syncthreads();
+        if (tid < 256) {
+            unsigned t = 0;
+            for (int w = 0; w < 16; ++w) t += hist[w * 256 + tid];
+            hist[tid] = t;                                                 // wave 0's row now holds the totals
+        }
+        __syncthreads();
+        if (tid == 0) {
+            unsigned r = rank_s;
+            int d = 0;
+            for (; d < 255 && r >= hist[d]; ++d) r -= hist[d];
+            rank_s = r;
+            const uint64_t p = prefix | ((uint64_t)d << shift);
+            // the whole bin is inside the top k: every key up to the bin's last possible one is selected
+            if (r + 1u == hist[d]) { prefix_s = p | ((1ull << shift) - 1ull); done_s = 1; }
+            else prefix_s = p;
+        }
+        __syncthreads();
+        if (done_s) break;                                                 // block-uniform
+    }
+    const uint64_t kth = prefix_s;                                         // all ones for a level that fits the list whole
+    for (int i = tid; i < TR_MAX; i += 1024) a[i] = ~0ull;
+    __syncthreads();
+    for (int e = tid; e < n; e += 1024) {
+        const uint64_t key = key_of(e);
+        if (key <= kth) { const unsigned pos = atomicAdd(&fill_s, 1u); if (pos < TR_MAX) a[pos] = key; }      // exactly k keys
+    }
+    __syncthreads();
+    block_bitonic_sort<TR_MAX / 1024>(a, tid);
+    const bool on = (level_mask >> l) & 1;
+    for (int i = tid; i < pre; i += 1024) {
+        const size_t o = (size_t)b * 5 * pre + (size_t)l * pre + i;
+        if (keys_out) keys_out[o] = i < k ? a[i] : ~0ull;
+        if (i >= k || !on) { valid[o] = 0; scores[o] = 0.f; continue; }
+        const uint64_t key = a[i];
+        const uint32_t e = (uint32_t)key;
+        const float sc = comp_score(key);
+        const int pix = e / 3, an = e - pix * 3;
+        const int y = pix / lv.W, x = pix - y * lv.W;
+        const float sx = (float)(x * lv.stride), sy = (float)(y * lv.stride);
+        const float ax0 = sx + lv.base[an][0], ay0 = sy + lv.base[an][1];
+        const float ax1 = sx + lv.base[an][2], ay1 = sy + lv.base[an][3];
+        const float* d = head + (size_t)pix * head_ld + 3 + an * 4;
+        const float w = ax1 - ax0, h = ay1 - ay0;
+        const float cx = ax0 + 0.5f * w, cy = ay0 + 0.5f * h;
+        float dx = d[0] / 1.0f, dy = d[1] / 1.0f, dw = d[2] / 1.0f, dh = d[3] / 1.0f;
+        dw = dw > scale_clamp ? scale_clamp : dw;
+        dh = dh > scale_clamp ? scale_clamp : dh;
+        const float pcx = dx * w + cx, pcy = dy * h + cy;
+        const float pw = expf(dw) * w, ph = expf(dh) * h;
+        float x0 = pcx - 0.5f * pw, y0 = pcy - 0.5f * ph, x1 = pcx + 0.5f * pw, y1 = pcy + 0.5f * ph;
+        x0 = fminf(fmaxf(x0, 0.f), img_w);
+        y0 = fminf(fmaxf(y0, 0.f), img_h);
+        x1 = fminf(fmaxf(x1, 0.f), img_w);
+        y1 = fminf(fmaxf(y1, 0.f), img_h);
+        const int ok = ((x1 - x0) > 0.f) && ((y1 - y0) > 0.f);
+        boxes[o * 4 + 0] = x0; boxes[o * 4 + 1] = y0; boxes[o * 4 + 2] = x1; boxes[o * 4 + 3] = y1;
+        scores[o] = sc;
+        valid[o] = ok;
+        if (ok) {
+            const float m = fmaxf(fmaxf(x0, x1), fmaxf(y0, y1));   // all >= 0 after the clip
+            atomicMax(maxc + b, __float_as_uint(m));
+        }
+    }
+}
+
+// Per slot: box [4][TR_MAX] (shifted), area, entry, n; mask [TR_MAX][TR_WORDS] u64; keep [TR_MAX] and its count.
+struct TrainNms { float* box; float* area; int* entry; int* n; uint64_t* mask; int* keep; int* keep_cnt; };
+
+// grid (5, B).  Level l's entries l * pre .. l * pre + pre - 1 are in (score desc, anchor asc) order already; the valid ones
+// keep it.  The category of a level is its rank among the levels of the mask (torchvision numbers the categories it is given).
+__global__ __launch_bounds__(1024) void train_nms_prepare(const float* __restrict__ boxes, const int* __restrict__ valid, int pre,
+                                                         const uint32_t* __restrict__ maxc, int level_mask, TrainNms S) {
+    __shared__ int wsum[17];
+    const int l = blockIdx.x, b = blockIdx.y, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const size_t slot = (size_t)b * 5 + l;
+    boxes += (size_t)b * 5 * pre * 4;
+    valid += (size_t)b * 5 * pre;
+    const float off = (float)__popc(level_mask & ((1 << l) - 1)) * (__uint_as_float(maxc[b]) + 1.0f);
+    float* bx = S.box + slot * 4 * TR_MAX;
+    if (tid == 0) wsum[16] = 0;
+    __syncthreads();
+    for (int base = 0; base < pre; base += 1024) {
+        const int i = base + tid, e = l * pre + i;
+        const bool f = i < pre && valid[e];
+        const uint64_t bal = __ballot(f);
+        if (lane == 0) wsum[wave] = __popcll(bal);
+        __syncthreads();
+        int o = wsum[16];
+        for (int w = 0; w < wave; ++w) o += wsum[w];
+        const int pos = o + __popcll(bal & ((1ull << lane) - 1ull));
+        if (f && pos < TR_MAX) {
+            const float x0 = boxes[e * 4 + 0] + off, y0 = boxes[e * 4 + 1] + off;
+            const float x1 = boxes[e * 4 + 2] + off, y1 = boxes[e * 4 + 3] + off;
+            bx[pos] = x0; bx[TR_MAX + pos] = y0; bx[2 * TR_MAX + pos] = x1; bx[3 * TR_MAX + pos] = y1;
+            S.area[slot * TR_MAX + pos] = (x1 - x0) * (y1 - y0);
+            S.entry[slot * TR_MAX + pos] = e;
+        }
+        __syncthreads();
+        if (tid == 0) { int t = wsum[16]; for (int w = 0; w < 16; ++w) t += wsum[w]; wsum[16] = t; }
+        __syncthreads();
+    }
+    if (tid == 0) S.n[slot] = wsum[16] < TR_MAX ? wsum[16] : TR_MAX;
+}
+
+// grid (TR_WORDS column chunks, TR_WORDS row chunks, 5 B), 64 threads: thread t owns row 64 * ic + t.
+__global__ __launch_bounds__(64) void train_nms_matrix(TrainNms S, float thr) {
+    __shared__ float cb[5][64];
+    const int jc = blockIdx.x, ic = blockIdx.y;
+    const size_t slot = blockIdx.z;
+    const int n = S.n[slot];
+    if (jc < ic || 64 * ic >= n || 64 * jc >= n) return;
+    const int t = threadIdx.x;
+    const float* bx = S.box + slot * 4 * TR_MAX;
+    const float* ar = S.area + slot * TR_MAX;
+    const int j = 64 * jc + t;
+    if (j < n) {
+        cb[0][t] = bx[j]; cb[1][t] = bx[TR_MAX + j]; cb[2][t] = bx[2 * TR_MAX + j]; cb[3][t] = bx[3 * TR_MAX + j];
+        cb[4][t] = ar[j];
+    }
+    __syncthreads();
+    const int i = 64 * ic + t;
+    if (i >= n) return;
+    uint64_t bits = 0;
+    const float ix0 = bx[i], iy0 = bx[TR_MAX + i], ix1 = bx[2 * TR_MAX + i], iy1 = bx[3 * TR_MAX + i];
+    const float ia = ar[i];
+    const int jend = (n - 64 * jc) < 64 ? (n - 64 * jc) : 64;
+    for (int jj = 0; jj < jend; ++jj) {
+        if (64 * jc + jj <= i) continue;
+        const float xx0 = fmaxf(ix0, cb[0][jj]), yy0 = fmaxf(iy0, cb[1][jj]);
+        const float xx1 = fminf(ix1, cb[2][jj]), yy1 = fminf(iy1, cb[3][jj]);
+        const float ww = fmaxf(0.f, xx1 - xx0), hh = fmaxf(0.f, yy1 - yy0);
+        const float inter = ww * hh;
+        const float ovr = inter / (ia + cb[4][jj] - inter);
+        if (ovr > thr) bits |= (1ull << jj);
+    }
+    S.mask[(slot * TR_MAX + i) * TR_WORDS + jc] = bits;
+}
+
+// Greedy scan, grid (5, B), the bit matrix read from HBM (only words on and right of the diagonal of rows < n: those the matrix
+// kernel wrote).  Kept entries in processing order -> keep [slot][TR_MAX], at most `post` of them.
+__global__ __launch_bounds__(1024) void train_nms_scan(TrainNms S, int post) {
+    __shared__ uint64_t removed[TR_WORDS];
+    __shared__ uint64_t keepbits_s;
+    __shared__ int kept_s;
+    const size_t slot = (size_t)blockIdx.y * 5 + blockIdx.x;
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int n = S.n[slot];
+    const int nw = (n + 63) >> 6;
+    const uint64_t* gm = S.mask + slot * TR_MAX * TR_WORDS;
+    const int* entry = S.entry + slot * TR_MAX;
+    int* keep = S.keep + slot * TR_MAX;
+    if (tid < TR_WORDS) removed[tid] = 0ull;
+    if (tid == 0) kept_s = 0;
+    __syncthreads();
+    int kept = 0;                                   // wave 0's running count
+    for (int ch = 0; ch < nw; ++ch) {
+        const int rows_here = (n - 64 * ch) < 64 ? (n - 64 * ch) : 64;
+        if (wave == 0) {
+            const int row = 64 * ch + lane;
+            const uint64_t diag = row < n ? gm[(size_t)row * TR_WORDS + ch] : 0ull;
+            uint64_t rem = removed[ch];
+            uint64_t keepbits = 0;
+            uint64_t alive = ~rem & (rows_here == 64 ? ~0ull : ((1ull << rows_here) - 1ull));
+            while (alive) {
+                const int r = __builtin_ctzll(alive);
+                keepbits |= (1ull << r);
+                rem |= readlane64(diag, r) | (1ull << r);
+                alive &= ~rem;
+            }
+            const int pos = kept + __popcll(keepbits & ((1ull << lane) - 1ull));
+            if (((keepbits >> lane) & 1ull) && pos < post) keep[pos] = entry[row];
+            kept += __popcll(keepbits);
+            if (lane == 0) { keepbits_s = keepbits; kept_s = kept; }
+        }
+        __syncthreads();
+        if (kept_s >= post) break;                  // block-uniform
+        const uint64_t kb = keepbits_s;
+        for (int w = ch + 1 + wave; w < nw; w += 16) {
+            uint64_t v = 0;
+            if (lane < rows_here && ((kb >> lane) & 1ull)) v = gm[(size_t)(64 * ch + lane) * TR_WORDS + w];
+            v = wave_or64(v);
+            if (lane == 0) removed[w] |= v;
+        }
+        __syncthreads();
+    }
+    if (tid == 0) S.keep_cnt[slot] = kept_s < post ? kept_s : post;
+}
+
+// rank_merge over five lists of up to TR_MAX keys: grid (image, level), every block loads the five lists of its image and ranks
+// the elements of its own (position + binary-search counts in the other four).  K <= TR_MAX.
+__global__ __launch_bounds__(1024) void train_rank_merge(const float* __restrict__ boxes, const float* __restrict__ scores,
+                                                        int n_total, TrainNms S, int K, float* __restrict__ out_boxes,
+                                                        float* __restrict__ out_scores, int* __restrict__ out_entry,
+                                                        int* __restrict__ out_count) {
+    extern __shared__ __attribute__((aligned(16))) char smem[];
+    uint64_t* keys = reinterpret_cast<uint64_t*>(smem);      // [5][TR_MAX]
+    __shared__ int cnt[5];
+    const int b = blockIdx.x, c = blockIdx.y, tid = threadIdx.x;
+    boxes += (size_t)b * n_total * 4;
+    scores += (size_t)b * n_total;
+    if (tid < 5) cnt[tid] = S.keep_cnt[b * 5 + tid];
+    __syncthreads();
+    int total = 0;
+    for (int o = 0; o < 5; ++o) {
+        const int* src = S.keep + ((size_t)b * 5 + o) * TR_MAX;
+        for (int i = tid; i < cnt[o]; i += 1024) { const int e = src[i]; keys[o * TR_MAX + i] = comp_key(scores[e], (uint32_t)e); }
+        total += cnt[o];
+    }
+    __syncthreads();
+    const int nout = total < K ? total : K;
+    for (int i = tid; i < cnt[c]; i += 1024) {
+        const uint64_t key = keys[c * TR_MAX + i];
+        int rank = i;
+        for (int o = 0; o < 5; ++o) {
+            if (o == c) continue;
+            int lo = 0, hi = cnt[o];
+            const uint64_t* ko = keys + o * TR_MAX;
+            while (lo < hi) { const int mid = (lo + hi) >> 1; if (ko[mid] < key) lo = mid + 1; else hi = mid; }
+            rank += lo;
+        }
+        if (rank < K) {
+            const uint32_t e = (uint32_t)key;
+            float* ob = out_boxes + ((size_t)b * K + rank) * 4;
+            ob[0] = boxes[e * 4 + 0]; ob[1] = boxes[e * 4 + 1]; ob[2] = boxes[e * 4 + 2]; ob[3] = boxes[e * 4 + 3];
+            out_scores[(size_t)b * K + rank] = scores[e];
+            out_entry[(size_t)b * K + rank] = (int)e;
+        }
+    }
+    if (c != 0) return;
+    for (int i = nout + tid; i < K; i += 1024) {
+        float* ob = out_boxes + ((size_t)b * K + i) * 4;
+        ob[0] = ob[1] = ob[2] = ob[3] = 0.f;
+        out_scores[(size_t)b * K + i] = 0.f;
+        out_entry[(size_t)b * K + i] = -1;
+    }
+    if (tid == 0) out_count[b] = nout;
+}
+
 // Pack per-image detections into one dense list (image id kept per entry) so the mask tail's
 // GEMMs see a contiguous M.  det_* are [B][Kd]; packed_* are [B*Kd].
 __global__ void pack_detections(const float* __restrict__ det_boxes, const float* __restrict__ det_scores,
@@ -1020,6 +1306,51 @@ int apse_k_c4_rpn(const C4Rpn* R, int pre, int post, float img_h, float img_w, f
     hipLaunchKernelGGL(c4_nms_matrix, dim3(C4_NMS_WORDS, C4_NMS_WORDS, B), dim3(64), 0, s, S, thr);
     hipLaunchKernelGGL(c4_nms_scan, dim3(B), dim3(1024), 0, s, S, dec_boxes, dec_scores, pre, post, props, prop_scores, prop_entry,
                        prop_count);
+    return hipGetLastError() == hipSuccess ? APSE_OK : APSE_E_HIP;
+}
+size_t apse_rpn_train_scratch_bytes(int B) {
+    const size_t slots = (size_t)B * 5;
+    return slots * ((size_t)TR_MAX * TR_WORDS * 8 + (size_t)TR_MAX * 4 * 4 + (size_t)TR_MAX * 4 * 3 + 8) + (size_t)B * 4 + 16;
+}
+static TrainNms train_carve(void* scratch, int B, uint32_t** maxc) {
+    TrainNms S;
+    const size_t slots = (size_t)B * 5;
+    char* p = reinterpret_cast<char*>(scratch);
+    S.mask = reinterpret_cast<uint64_t*>(p); p += slots * TR_MAX * TR_WORDS * 8;
+    S.box = reinterpret_cast<float*>(p); p += slots * 4 * TR_MAX * 4;
+    S.area = reinterpret_cast<float*>(p); p += slots * TR_MAX * 4;
+    S.entry = reinterpret_cast<int*>(p); p += slots * TR_MAX * 4;
+    S.keep = reinterpret_cast<int*>(p); p += slots * TR_MAX * 4;
+    S.n = reinterpret_cast<int*>(p); p += slots * 4;
+    S.keep_cnt = reinterpret_cast<int*>(p); p += slots * 4;
+    *maxc = reinterpret_cast<uint32_t*>(p);
+    return S;
+}
+// Training-time FPN proposals: L (host; pre_topk and every level's k filled, rpn_select_plan) -> key lists (keys may be null),
+// dec_* [B][5 * pre], props [B][post], counts.  1 <= pre, post <= TR_MAX; scratch of apse_rpn_train_scratch_bytes(B).
+int apse_k_rpn_train_select(const RpnLevels* L, int post, float img_h, float img_w, float scale_clamp, float thr, int level_mask,
+                            uint64_t* keys, float* dec_boxes, float* dec_scores, int* dec_valid, void* scratch, float* props,
+                            float* prop_scores, int* prop_entry, int* prop_count, int B, hipStream_t s) {
+    const int pre = L->pre_topk;
+    if (pre < 1 || pre > TR_MAX || post < 1 || post > TR_MAX || B < 1) return APSE_E_INVALID;
+    for (int l = 0; l < 5; ++l)
+        if (L->lv[l].k > pre || L->lv[l].k > L->lv[l].n) return APSE_E_INVALID;
+    static bool done = false;
+    if (!done) {
+        hipFuncSetAttribute(reinterpret_cast<const void*>(&train_rank_merge), hipFuncAttributeMaxDynamicSharedMemorySize,
+                            5 * TR_MAX * 8);
+        done = true;
+    }
+    uint32_t* maxc;
+    TrainNms S = train_carve(scratch, B, &maxc);
+    if (hipMemsetAsync(maxc, 0, (size_t)B * 4, s) != hipSuccess) return APSE_E_HIP;
+    hipLaunchKernelGGL(train_rpn_select, dim3(5, B), dim3(1024), 0, s, *L, img_h, img_w, scale_clamp, keys, dec_boxes, dec_scores,
+                       dec_valid, maxc, level_mask);
+    hipLaunchKernelGGL(train_nms_prepare, dim3(5, B), dim3(1024), 0, s, dec_boxes, dec_valid, pre, maxc, level_mask, S);
+    hipLaunchKernelGGL(train_nms_matrix, dim3(TR_WORDS, TR_WORDS, 5 * B), dim3(64), 0, s, S, thr);
+    hipLaunchKernelGGL(train_nms_scan, dim3(5, B), dim3(1024), 0, s, S, post);
+    hipLaunchKernelGGL(train_rank_merge, dim3(B, 5), dim3(1024), (size_t)5 * TR_MAX * 8, s, dec_boxes, dec_scores, 5 * pre, S, post,
+                       props, prop_scores, prop_entry, prop_count);
     return hipGetLastError() == hipSuccess ? APSE_OK : APSE_E_HIP;
 }
 int apse_k_pack_detections(const float* det_boxes, const float* det_scores, const int* det_entry, const int* det_cnt, int B,

@@ -133,6 +133,11 @@ class TrackRCNN:
         self._input_tag = None                # frames (objects) the network input was pre-staged with, or None
         self._running_tag = None              # (frames, rpn_levels) whose forward is already enqueued and not yet read, or None
         self.last_results = None
+        # set_rpn_head: the six device tensors a live context's RPN head was last replaced with, their version, and the version
+        # every live context holds (key -> version; a context is built from _state, which set_rpn_head keeps current)
+        self._rpn_head = None
+        self._rpn_head_version = 0
+        self._ctx_head_version = {}
 
     # ---- nn.Module-like surface the reference touches
     def to(self, device):
@@ -175,6 +180,7 @@ class TrackRCNN:
         self._running_tag = None
         self._ctx = None
         self._ctx_key = None
+        self._ctx_head_version = {}
         while self._cache:
             _, entry = self._cache.popitem(last=False)
             _lib.load().apse_destroy(entry[0])
@@ -204,7 +210,8 @@ class TrackRCNN:
             self._ctx = None
             self._ctx_key = None
             while len(self._cache) >= keep:
-                _, entry = self._cache.popitem(last=False)          # the least recently used one
+                old, entry = self._cache.popitem(last=False)        # the least recently used one
+                self._ctx_head_version.pop(old, None)
                 _lib.load().apse_destroy(entry[0])
         if self.device.type != "cuda" or not torch.cuda.is_available():
             raise _lib.ApseError("the apse_uav hot path needs a ROCm GPU (cfg.MODEL.DEVICE=%s): no CPU fallback" % self.device)
@@ -288,6 +295,7 @@ class TrackRCNN:
         self._host = torch.empty(lay.bytes, dtype=torch.uint8).pin_memory()
         self._cfg_c = c
         self._cache[key] = (ctx, lay, self._host, c)
+        self._ctx_head_version[key] = self._rpn_head_version      # built from _state, which holds the current head
         if self._camera is not None:
             self._push_camera(ctx)
 
@@ -320,6 +328,7 @@ class TrackRCNN:
 
     def run(self, batch, given=None, rpn_levels=31):
         self._running_tag = None              # any forward invalidates a speculatively enqueued one (TrackPredictor run-ahead)
+        self._refresh_rpn_head()
         s = _lib.stream_ptr()
         self._call("apse_backbone", batch, s)
         if given is None:
@@ -428,6 +437,7 @@ class TrackRCNN:
                                       "(Res5ROIHeads) models")
         B = int(batch)
         self._running_tag = None
+        self._refresh_rpn_head()
         s = _lib.stream_ptr()
         self._call("apse_rpn", B, s)
         post = int(self._cfg_c.rpn_post_topk)
@@ -437,6 +447,64 @@ class TrackRCNN:
             self._call("apse_proposals", b, _lib.ptr(boxes[b]), C.c_void_p(counts[b:].data_ptr()), s)
         host = counts.cpu()
         return [boxes[b, :int(host[b])] for b in range(B)]
+
+    def set_rpn_head(self, head):
+        """Replaces the RPN head of the live contexts with ``head``'s weights (networks.rpn_head.RPNHead, or a mapping of its six
+        tensors under the bare or the ``proposal_generator.rpn_head.`` names) without rebuilding them: the joint trainer calls
+        this after every optimiser step (apse_set_rpn_head; FPN f32 models only).  The tensors are copied and given a version
+        number; the current context is refreshed before its next RPN run, a cached one (cfg.APSE.CONTEXT_CACHE > 1) when it is
+        used again, and ``_state`` is updated so that a context built later starts from the same head."""
+        from . import rpn_head as rh
+        if self.c4:
+            raise NotImplementedError("set_rpn_head covers FPN models (p2 .. p6): not available for C4 (Res5ROIHeads) models")
+        if self._state is None:
+            raise _lib.ApseError("set_rpn_head: the detector has no weights loaded")
+        sd = head.state_dict() if hasattr(head, "state_dict") else dict(head)
+        ts = []
+        for name in rh._names():
+            t = sd.get(name, sd.get(rh.PREFIX + name))
+            if t is None:
+                raise KeyError("set_rpn_head: missing %s" % name)
+            t = torch.as_tensor(t).detach()
+            if tuple(t.shape) != tuple(rh.SHAPES[name]):
+                raise ValueError("set_rpn_head: %s has shape %s, expected %s" % (name, tuple(t.shape), tuple(rh.SHAPES[name])))
+            ts.append(t.to(self.device, torch.float32, copy=True).contiguous())
+        self._rpn_head = ts
+        self._rpn_head_version += 1
+        for name, t in zip(rh._names(), ts):
+            self._state[rh.PREFIX + name] = t.cpu()
+
+    def _refresh_rpn_head(self):
+        """Brings the current context's RPN head up to the version of the last ``set_rpn_head``."""
+        if self._rpn_head is None or self._ctx is None or self._ctx_head_version.get(self._ctx_key) == self._rpn_head_version:
+            return
+        self._call("apse_set_rpn_head", *[_lib.ptr(t) for t in self._rpn_head], _lib.stream_ptr())
+        self._ctx_head_version[self._ctx_key] = self._rpn_head_version
+
+    def train_proposals(self, batch, pre_topk=None, post_topk=None):
+        """The proposals a training step sees, for the ``batch`` images of the last ``backbone_frames`` / ``backbone_images``
+        run: the context's RPN convolutions (current head) and find_top_rpn_proposals at the training limits, by default
+        cfg.MODEL.RPN.PRE_NMS_TOPK_TRAIN per level and POST_NMS_TOPK_TRAIN (2000, 1000; each up to 2048).  Returns per image
+        (boxes f32 [count][4] in resized-image pixels, scores f32 [count]) on the device, best first.  The training counterpart
+        of ``proposals_after_backbone``; the context's own proposals and results are left alone (apse_rpn_train_proposals; FPN
+        f32 models only)."""
+        if self.c4:
+            raise NotImplementedError("train_proposals feeds box-head training, which pools p2..p5: not available for C4 "
+                                      "(Res5ROIHeads) models")
+        B = int(batch)
+        pre = int(self.cfg.MODEL.RPN.PRE_NMS_TOPK_TRAIN if pre_topk is None else pre_topk)
+        post = int(self.cfg.MODEL.RPN.POST_NMS_TOPK_TRAIN if post_topk is None else post_topk)
+        self._running_tag = None
+        self._refresh_rpn_head()
+        nbytes = int(_lib.load().apse_rpn_train_proposals_workspace_bytes(B, pre))
+        ws = torch.empty(max(nbytes, 16), dtype=torch.uint8, device=self.device)
+        boxes = torch.empty((B, max(post, 1), 4), dtype=torch.float32, device=self.device)
+        scores = torch.empty((B, max(post, 1)), dtype=torch.float32, device=self.device)
+        counts = torch.empty(B, dtype=torch.int32, device=self.device)
+        self._call("apse_rpn_train_proposals", B, pre, post, _lib.ptr(boxes), _lib.ptr(scores), _lib.ptr(counts), _lib.ptr(ws),
+                   nbytes, _lib.stream_ptr())
+        host = counts.cpu()
+        return [(boxes[b, :int(host[b])], scores[b, :int(host[b])]) for b in range(B)]
 
     def rpn_level_shapes(self):
         """The (H, W) of p2 .. p6 of the current context: the five anchor grids (3 anchors per position, (level, y, x, a) order)."""

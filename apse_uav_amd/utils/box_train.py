@@ -48,10 +48,12 @@ class BoxTrainLoader(MaskTrainLoader):
     weights.  Per image: the image and annotation path of MaskTrainLoader (test size on the host, or the device path with
     ``augment`` / ``min_sizes``), the context's own RPN (its test-time selection), ``label_and_sample_proposals`` with a device
     generator seeded from ``seed``, then ROIAlign 7 of the sampled boxes.  Crowd annotations are dropped.  ``state_dict`` also
-    carries the sampling generator's state."""
+    carries the sampling generator's state.  ``train_topk`` = (pre, post): the proposals are ``model.train_proposals(1, pre, post)``,
+    detectron2's training-time selection (2000 per level, 1000), instead of the test-time one."""
 
     def __init__(self, dicts, model, ims_per_batch=2, seed=0, flip=False, augment=False, min_sizes=None, max_size=None,
-                 sampling="choice", num_classes=None, batch_size_per_image=512, positive_fraction=0.25, iou_thresh=0.5):
+                 sampling="choice", num_classes=None, batch_size_per_image=512, positive_fraction=0.25, iou_thresh=0.5,
+                 train_topk=None):
         if getattr(model, "c4", False):
             raise NotImplementedError("box-head training covers FPN models; under C4 (Res5ROIHeads) the box branch is the res5 stage")
         super().__init__(dicts, model, ims_per_batch, seed, flip, False, bh.MAX_ROIS, augment, min_sizes, max_size, sampling)
@@ -59,6 +61,7 @@ class BoxTrainLoader(MaskTrainLoader):
         self.batch_size_per_image = int(batch_size_per_image)
         self.positive_fraction = float(positive_fraction)
         self.iou_thresh = float(iou_thresh)
+        self.train_topk = None if train_topk is None else (int(train_topk[0]), int(train_topk[1]))
         if self.ims_per_batch * self.batch_size_per_image > bh.MAX_ROIS:
             raise ValueError("%d images x %d RoIs exceed the %d RoIs of one step (APSE_BOX_TRAIN_MAX_N)"
                              % (self.ims_per_batch, self.batch_size_per_image, bh.MAX_ROIS))
@@ -80,7 +83,7 @@ class BoxTrainLoader(MaskTrainLoader):
         keep = [i for i, a in enumerate(d["annotations"]) if not a.get("iscrowd", 0)]
         gt = torch.from_numpy(np.asarray(boxes, np.float64)[keep].astype(np.float32)).reshape(-1, 4).to(model.device)
         cls = torch.as_tensor(classes)[keep].to(model.device, torch.int32)
-        props = model.proposals_after_backbone(1)[0]
+        props = model.train_proposals(1, *self.train_topk)[0][0] if self.train_topk else model.proposals_after_backbone(1)[0]
         sb, labels, matched, counts = label_and_sample_proposals(props, gt, cls, self.num_classes, self.batch_size_per_image,
                                                                  self.positive_fraction, self.generator, self.iou_thresh)
         return model.box_roi_features(sb), labels, sb, matched, counts

@@ -777,6 +777,45 @@ int apse_rpn_loss_backward(const float* logits_dev, const float* deltas_dev, con
                            const float* grad_cls_dev, const float* grad_loc_dev, float* dlogits_dev, float* ddeltas_dev,
                            void* stream);
 
+/* ---- Training-time proposals (csrc/select_nms.hip "training-time FPN selection", csrc/rpn_train.hip): what joint training of
+ * the RPN head and the box head needs from a live context.  detectron2 0.1.2 runs the same find_top_rpn_proposals in training
+ * and in test; only PRE_NMS_TOPK / POST_NMS_TOPK differ (2000 per level / 1000 in Base-RCNN-FPN.yaml), so the rules are those of
+ * apse_rpn_select: per-level top-k (score descending, anchor ascending, the two zeros one score), decode with weights
+ * (1, 1, 1, 1), clip, nonempty flag, batched_nms per level on boxes shifted by category x (max_coord + 1) with the categories
+ * numbered over the levels present and `iou > thr` suppressing, merge by (score descending, entry ascending), first post_topk.
+ * The reach is longer: 1 <= pre_topk <= APSE_RPN_TRAIN_MAX_PRE_TOPK per level, 1 <= post_topk <= APSE_RPN_TRAIN_MAX_POST_TOPK.
+ * Inference keeps its own kernels and limits.  Every entry checks its limits before anything is launched: APSE_E_INVALID with
+ * the text in apse_last_error (of the context where there is one, of NULL otherwise), nothing launched, outputs untouched. */
+#define APSE_RPN_TRAIN_MAX_PRE_TOPK 2048
+#define APSE_RPN_TRAIN_MAX_POST_TOPK 2048
+/* The selection on injected inputs: the arguments and output layouts of apse_rpn_select (keys_dev [B][5][pre_topk], may be
+ * NULL; dec_* [B][5*pre_topk]; props and friends [B][post_topk]; entry = level * pre_topk + rank; zeros and -1 past the count).
+ * 1 <= B <= 64.  Allocates its own scratch and synchronises `stream` before it returns. */
+int apse_rpn_select_train(const float* const* heads_dev, const int* H, const int* W, int head_ld, int B, int image_h, int image_w,
+                          int pre_topk, int post_topk, float nms_thr, int level_mask, unsigned long long* keys_dev,
+                          float* dec_boxes_dev, float* dec_scores_dev, int* dec_valid_dev, float* props_dev, float* prop_scores_dev,
+                          int* prop_entry_dev, int* prop_count_dev, void* stream);
+/* Bytes of workspace apse_rpn_train_proposals needs (0 outside the limits). */
+size_t apse_rpn_train_proposals_workspace_bytes(int batch, int pre_topk);
+/* The proposals a training step sees: runs the context's RPN convolutions on the maps of the last apse_backbone, then the
+ * training selection (all five levels, the context's rpn_nms) on its rpn_head2 .. rpn_head6 tensors.  boxes_dev
+ * [batch][post_topk][4] and scores_dev [batch][post_topk], best first, zeros past count_dev [batch].  Outputs and scratch are the
+ * caller's: the context's own proposals, proposal counts and results block are not touched, so a later inference forward is
+ * unchanged.  Everything is enqueued on `stream` after joining the tail lane; nothing is allocated, nothing synchronised.
+ * workspace_dev: 16-byte aligned.  FPN contexts with compute_dtype 0 only. */
+int apse_rpn_train_proposals(apse_ctx* ctx, int batch, int pre_topk, int post_topk, float* boxes_dev, float* scores_dev,
+                             int* count_dev, void* workspace_dev, size_t workspace_bytes, void* stream);
+/* Replaces the RPN head of a live context: the six tensors of proposal_generator.rpn_head in checkpoint layout, DEVICE pointers
+ * (conv_w [256][256][3][3], conv_b [256], obj_w [3][256][1][1], obj_b [3], delta_w [12][256][1][1], delta_b [12]).  Kernels on
+ * `stream` re-pack them as the plan packed them (the tiled layout of every level's 3 x 3 step and of the fused 1 x 1 head; the
+ * Winograd filters U = G g G^T in float64, rounded once, where a level's step holds them) straight into the buffers the steps
+ * own: no allocation, no host copy, no synchronisation, the plan is left alone.  Joins the tail lane first; RPN launches
+ * enqueued on `stream` before the call read the old weights, those after it the new ones.  Afterwards the context's
+ * rpn_head{l} maps and proposals equal, bit for bit, those of a context created from a state with these six tensors.
+ * FPN contexts with compute_dtype 0 only. */
+int apse_set_rpn_head(apse_ctx* ctx, const float* conv_w_dev, const float* conv_b_dev, const float* obj_w_dev,
+                      const float* obj_b_dev, const float* delta_w_dev, const float* delta_b_dev, void* stream);
+
 /* ---- Training augmentation (csrc/augment.hip): the transforms the reference's DatasetMapper applies after ResizeShortestEdge
  * (dcnn/utils/UAV_utils.py:311-449) -- RandomFlip, RandomBrightness, RandomSaturation, RandomContrast, RandomLighting of
  * detectron2 0.1.2 / fvcore, in that order, on resized u8 BGR images.  The rules, with the type of every operation (numpy 1.18

@@ -1,88 +1,76 @@
 #!/usr/bin/env python
-"""Fine-tune the box branch of a detector on the GPU -- the ``roi_heads`` half of dcnn/scripts/train/finetune_uav.py and
-finetune_faster_rcnn_aerial.py.
+"""Fine-tune the RPN head and the box branch of a detector jointly on the GPU -- dcnn/scripts/train/finetune_uav.py and
+finetune_faster_rcnn_aerial.py with ``to_train=['proposal_generator', 'roi_heads']``: one loop, one optimiser.
 
-Everything is frozen except ``roi_heads.box_head.fc{1,2}`` and ``roi_heads.box_predictor.{cls_score,bbox_pred}``; the proposals
-are the detector's own RPN output (its test-time selection) with the ground-truth boxes appended, labelled and sampled as
-detectron2's ``ROIHeads.label_and_sample_proposals`` does (512 per image, a quarter foreground); ``loss_cls + loss_box_reg`` is
-optimised with momentum SGD under detectron2's WarmupMultiStepLR; every CHECKPOINT_PERIOD iterations the held-out images are
-scored (bbox AP / AR) and a checkpoint with the merged full detector is written.
+Everything is frozen except ``proposal_generator.rpn_head.{conv,objectness_logits,anchor_deltas}``, ``roi_heads.box_head.fc{1,2}``
+and ``roi_heads.box_predictor.{cls_score,bbox_pred}`` (14 tensors).  Per step and image the frozen backbone runs once; the anchors
+are labelled and sampled as ``RPNOutputs._get_ground_truth`` does (256 per image); the box head's proposals come from the RPN
+head AS IT IS AT THAT STEP, selected with detectron2's training limits (2000 per level before NMS, 1000 after), the ground truths
+are appended, and 512 per image are sampled as ``ROIHeads.label_and_sample_proposals`` does.  ``loss_rpn_cls + loss_rpn_loc +
+loss_cls + loss_box_reg`` is optimised with one momentum SGD under detectron2's WarmupMultiStepLR, and after every optimiser step
+the new RPN head is written into the live detector contexts (``TrackRCNN.set_rpn_head``: no rebuild).  At most 4 images per batch
+(4 x 256 RPN rows is one step's limit); their up to 2048 box rows go through the box head in chunks of whole images
+(utils/joint_train.py box_losses_chunked).  Every CHECKPOINT_PERIOD iterations the held-out images are scored (bbox AP / AR, and
+the recall of the proposals at 100 and 1000) and a checkpoint with the merged full detector is written.
 
-``--classes`` with a class count other than the checkpoint's keeps fc1 / fc2 and re-initialises the two predictor layers (and
-the mask predictor, whose channels are per class): a COCO model to three or four vehicle classes.
-
-  python tools/finetune_box_head.py --images DIR --annotations FILE.json --weights detector.pth --classes car truck bus --out DIR
-  python tools/finetune_box_head.py --synthetic 6 --iters 12 --checkpoint-period 4 --out DIR     # dry run on generated data
-  python tools/finetune_box_head.py ... --resume                                                 # continue from DIR/<name>_last.pth
+  python tools/finetune_uav.py --images DIR --annotations FILE.json --weights detector.pth --classes car truck bus --out DIR
+  python tools/finetune_uav.py --synthetic 6 --iters 12 --checkpoint-period 4 --out DIR     # dry run on generated data
+  python tools/finetune_uav.py ... --resume                                                 # continue from DIR/<name>_last.pth
 
 Checkpoint keys: model, optimizer, scheduler, iteration, kfold_split, k_folds, best_precision, best_recall, training_results,
-loader (the image order, the augmentation draws and the sampling generator), so that a resumed run repeats the uninterrupted one
-bit for bit.
+loader (the image order, the augmentation draws and both sampling generators), so that a resumed run repeats the uninterrupted
+one bit for bit.
 """
 import argparse
 import os
 import sys
 
-import numpy as np
-
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 
 RESULTS_FILE = "results.txt"
-HEADER = "\t\tAP\tAP_05\tAP0.75\tAP_s\tAP_m\tAP_l\tAR_1\tAR_10\tAR_100\tAR_s\tAR_m\tAR_l\n"
-MASK_PREDICTOR = "roi_heads.mask_head.predictor."
+HEADER = "\t\tAP\tAP_05\tAP0.75\tAP_s\tAP_m\tAP_l\tAR_1\tAR_10\tAR_100\tAR_s\tAR_m\tAR_l\tprop_AR@100\tprop_AR@1000\n"
+MAX_IMS = 4
+
+
+def merged_state(detector, rpn_head, box_head):
+    from apse_uav_amd.networks.box_head import merge_box_head
+    from apse_uav_amd.networks.rpn_head import merge_rpn_head
+    return merge_box_head(merge_rpn_head(detector, rpn_head.state_dict()), box_head.state_dict())
 
 
 def do_test(pred, dicts, coco_gt):
-    """bbox COCOeval stats (12 numbers) of the predictor's detections on ``dicts``; None when there is nothing to score."""
-    from PIL import Image
-    from apse_uav_amd.utils.coco_eval import CocoEvaluator
-    ev = CocoEvaluator(coco_gt)
-    total = 0
-    for d in dicts:
-        frame = np.asarray(Image.open(d["file_name"]).convert("RGB"))[:, :, ::-1].copy()
-        inst = pred(frame)[0]["instances"]
-        ev.add(d["image_id"], inst)
-        total += len(inst)
-    if total == 0:
+    """The 12 bbox COCOeval numbers (zeros when nothing was detected) followed by the proposal recall at 100 and 1000 (IoU 0.5)
+    of the predictor on ``dicts``; None when there is no ground truth."""
+    import finetune_box_head
+    import finetune_rpn
+    recall = finetune_rpn.do_test(pred, dicts)
+    if recall is None:
         return None
-    return [float(v) for v in ev.evaluate("bbox").stats]
-
-
-def adapt_detector(detector, K):
-    """The frozen detector for K classes: when the checkpoint's class count differs, the per-class tensors outside the trained
-    layers (the mask predictor) are re-initialised as detectron2 leaves shape-mismatched keys (normal(std = 0.001), bias 0).
-    -> (state, True when the class count changed)."""
-    import torch
-    have = int(detector["roi_heads.box_predictor.cls_score.weight"].shape[0]) - 1
-    if have == K:
-        return detector, False
-    out = dict(detector)
-    if MASK_PREDICTOR + "weight" in out:
-        cin = int(out[MASK_PREDICTOR + "weight"].shape[1])
-        out[MASK_PREDICTOR + "weight"] = torch.nn.init.normal_(torch.zeros(K, cin, 1, 1), std=0.001)
-        out[MASK_PREDICTOR + "bias"] = torch.zeros(K)
-    return out, True
+    ap = finetune_box_head.do_test(pred, dicts, coco_gt)
+    return (ap if ap is not None else [0.0] * 12) + recall
 
 
 def main(argv=None):
+    from finetune_box_head import adapt_detector
     from finetune_segmentation import holdout_split
     ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
     ap.add_argument("--images", default="")
     ap.add_argument("--annotations", default="")
-    ap.add_argument("--weights", default="", help="detector (.pth / converted model-zoo file); its box branch is the start")
+    ap.add_argument("--weights", default="", help="detector (.pth / converted model-zoo file); its two heads are the start")
     ap.add_argument("--classes", nargs="*", default=None, help="category names to train on (default: all)")
     ap.add_argument("--out", required=True)
-    ap.add_argument("--name", default="R_50_FPN_UAV_BOX")
+    ap.add_argument("--name", default="R_50_FPN_UAV")
     ap.add_argument("--iters", type=int, default=20000, help="MAX_ITER")
     ap.add_argument("--checkpoint-period", type=int, default=10)
-    ap.add_argument("--ims-per-batch", type=int, default=2)
+    ap.add_argument("--ims-per-batch", type=int, default=2, help="at most %d, the reference yaml's value" % MAX_IMS)
     ap.add_argument("--lr", type=float, default=0.02)
     ap.add_argument("--momentum", type=float, default=0.9)
     ap.add_argument("--steps", type=int, nargs="*", default=[30000])
     ap.add_argument("--gamma", type=float, default=0.1)
     ap.add_argument("--warmup-iters", type=int, default=1000)
     ap.add_argument("--warmup-factor", type=float, default=0.001)
+    ap.add_argument("--optimizer", choices=("apse", "torch"), default="apse", help="apse_uav_amd.optim.SGD (HIP) or torch.optim.SGD")
     ap.add_argument("--k-folds", type=int, default=1000)
     ap.add_argument("--seed", type=int, default=0)
     ap.add_argument("--flip", action="store_true", help="random horizontal flip")
@@ -93,23 +81,23 @@ def main(argv=None):
                     help="multi-scale training: the short edge of every training image is drawn from these sizes "
                          "(default: the test size)")
     ap.add_argument("--max-size", type=int, default=0, help="cap of the long edge with --min-sizes / --augment (default: the test one)")
-    ap.add_argument("--train-topk", default="", metavar="PRE,POST",
-                    help="train on the RPN's training-time selection, e.g. 2000,1000 as the reference's yaml (default: the "
-                         "test-time selection)")
     ap.add_argument("--stop-at", type=int, default=0, help="stop after this iteration's checkpoint (an interrupted run, for --resume)")
     ap.add_argument("--resume", action="store_true")
     ap.add_argument("--test-on-train", action="store_true", help="score the training images instead of the held-out ones")
     ap.add_argument("--synthetic", type=int, default=0, metavar="N")
     args = ap.parse_args(argv)
+    if not 1 <= args.ims_per_batch <= MAX_IMS:
+        ap.error("--ims-per-batch must be 1 .. %d (%d x 256 RPN rows is the limit of one step)" % (MAX_IMS, MAX_IMS))
 
     import torch
     from apse_uav_amd import optim
     from apse_uav_amd.config import is_c4, setup_cfg
     from apse_uav_amd.engines.track_predictor import TrackPredictor
-    from apse_uav_amd.networks.box_head import BoxHead, merge_box_head
+    from apse_uav_amd.networks.box_head import BoxHead
+    from apse_uav_amd.networks.rpn_head import RPNHead
     from apse_uav_amd.utils import COCO_utils
-    from apse_uav_amd.utils.box_train import BoxTrainLoader
     from apse_uav_amd.utils.coco import COCO
+    from apse_uav_amd.utils.joint_train import JointTrainLoader, box_losses_chunked
     from apse_uav_amd.weights import load_detector_file, synthetic_detector_state
 
     os.makedirs(args.out, exist_ok=True)
@@ -134,23 +122,29 @@ def main(argv=None):
     # the loop alternates between images of several sizes and every size has a context of its own: keep a few alive
     cfg.APSE.CONTEXT_CACHE = max(int(cfg.APSE.get("CONTEXT_CACHE", 1)), 4)
     if is_c4(cfg):
-        raise NotImplementedError("box-head training covers FPN models")
+        raise NotImplementedError("joint detection-head training covers FPN models")
     last_path = os.path.join(args.out, args.name + "_last.pth")
     results_path = os.path.join(args.out, RESULTS_FILE)
 
     torch.manual_seed(args.seed)
     detector, changed = adapt_detector(detector, K)
-    head = BoxHead(K, "cuda")
-    head.load_state_dict(detector, keep_predictor=changed)          # another class count: fc1 / fc2 only, fresh predictors
-    params = list(head.parameters())
-    opt = optim.SGD(params, lr=args.lr, momentum=args.momentum)
+    rpn_head = RPNHead.from_cfg(cfg, "cuda")
+    rpn_head.load_state_dict(detector)
+    box_head = BoxHead(K, "cuda")
+    box_head.load_state_dict(detector, keep_predictor=changed)      # another class count: fc1 / fc2 only, fresh predictors
+    params = list(rpn_head.parameters()) + list(box_head.parameters())
+    if args.optimizer == "torch":
+        opt = torch.optim.SGD(params, lr=args.lr, momentum=args.momentum)
+    else:
+        opt = optim.SGD(params, lr=args.lr, momentum=args.momentum)
     sched = optim.WarmupMultiStepLR(opt, args.steps, args.gamma, args.warmup_factor, args.warmup_iters)
     start_iter, best_p, best_r = 0, 0.0, 0.0
     chk = None
     if args.resume:
         chk = torch.load(last_path, map_location="cpu", weights_only=False)
         detector = {k: v for k, v in chk["model"].items()}           # the frozen part as the interrupted run had it
-        head.load_state_dict(chk["model"])
+        rpn_head.load_state_dict(chk["model"])
+        box_head.load_state_dict(chk["model"])
         opt.load_state_dict(chk["optimizer"])
         sched.load_state_dict(chk["scheduler"])
         start_iter = int(chk["iteration"]) + 1
@@ -168,30 +162,37 @@ def main(argv=None):
     test_dicts = train_dicts if args.test_on_train else [dicts[i] for i in test_ids]
     gt = COCO.from_dataset(COCO_utils.detectron2_dataset_to_coco(test_dicts), verbose=False)
 
-    pred = TrackPredictor(cfg, state_dict=merge_box_head(detector, head.state_dict()))
+    pred = TrackPredictor(cfg, state_dict=merged_state(detector, rpn_head, box_head))
     min_sizes = tuple(int(v) for v in args.min_sizes.split(",")) if args.min_sizes else None
-    loader = BoxTrainLoader(train_dicts, pred.model, args.ims_per_batch, args.seed, args.flip, augment=args.augment,
-                            min_sizes=min_sizes, max_size=args.max_size or None, num_classes=K,
-                            train_topk=tuple(int(v) for v in args.train_topk.split(",")) if args.train_topk else None)
+    loader = JointTrainLoader(train_dicts, pred.model, args.ims_per_batch, args.seed, args.flip, augment=args.augment,
+                              min_sizes=min_sizes, max_size=args.max_size or None, num_classes=K)
     if chk is not None:
         loader.load_state_dict(chk["loader"])
 
+    def push_heads():
+        """Both heads into the predictor: the box branch rebuilds the contexts (from a state that holds the current RPN head)."""
+        pred.model.set_rpn_head(rpn_head)
+        box_head.push_into(pred)
+
+    names = ("loss_rpn_cls", "loss_rpn_loc", "loss_cls", "loss_box_reg")
     summary = {"losses": [], "tests": [], "num_classes": K}
-    summary["ap_before"] = do_test(pred, test_dicts, gt) if not args.resume else None
+    summary["before"] = do_test(pred, test_dicts, gt) if not args.resume else None
     print("Training for {} iterations started".format(args.iters))
     for iteration in range(start_iter, args.iters):
-        feats, labels, prop_boxes, gt_boxes = next(loader)
-        losses = head(feats, labels, prop_boxes, gt_boxes)
-        loss = losses["loss_cls"] + losses["loss_box_reg"]
+        rpn, box = next(loader)
+        losses = dict(rpn_head(*rpn, args.ims_per_batch))
+        losses.update(box_losses_chunked(box_head, *box, loader.last_box_rows))
+        loss = losses["loss_rpn_cls"] + losses["loss_rpn_loc"] + losses["loss_cls"] + losses["loss_box_reg"]
         opt.zero_grad()
         loss.backward()
         opt.step()
         sched.step()
-        summary["losses"].append((float(losses["loss_cls"].detach()), float(losses["loss_box_reg"].detach())))
-        print("Iter. {}/{}:\tloss_cls: {}\tloss_box_reg: {}\tfg/bg: {}".format(iteration, args.iters, summary["losses"][-1][0],
-                                                                              summary["losses"][-1][1], loader.last_counts))
+        pred.model.set_rpn_head(rpn_head)                            # the next step's proposals come from this head
+        summary["losses"].append(tuple(float(losses[k].detach()) for k in names))
+        print("Iter. {}/{}:\t".format(iteration, args.iters) + "\t".join("{}: {}".format(k, v) for k, v in zip(names, summary["losses"][-1]))
+              + "\tpos/neg: {}\tfg/bg: {}".format(loader.last_rpn_counts, loader.last_box_counts))
         if iteration != 0 and iteration % args.checkpoint_period == 0:
-            head.push_into(pred)
+            push_heads()
             res = do_test(pred, test_dicts, gt)
             print("test results:", res)
             if res is not None:
@@ -199,28 +200,30 @@ def main(argv=None):
                 if res[0] > best_p:
                     best_p = res[0]
                     line += " Best precision!"
-                if res[8] > best_r:
-                    best_r = res[8]
+                if res[12] > best_r:
+                    best_r = res[12]
                     line += " Best recall!"
                 with open(results_path, "a") as fh:
                     fh.write(line + "\n")
                 summary["tests"].append((iteration, res))
             with open(results_path) as fh:
-                chkpt = {"model": merge_box_head(detector, head.state_dict()), "optimizer": opt.state_dict(),
+                chkpt = {"model": merged_state(detector, rpn_head, box_head), "optimizer": opt.state_dict(),
                          "scheduler": sched.state_dict(), "iteration": iteration, "kfold_split": split, "k_folds": k_folds,
                          "best_precision": best_p, "best_recall": best_r, "training_results": fh.read(),
                          "loader": loader.state_dict()}
             torch.save(chkpt, last_path)
             if res is None or res[0] == best_p or not os.path.exists(os.path.join(args.out, args.name + "_bestAP.pth")):
                 torch.save(chkpt, os.path.join(args.out, args.name + "_bestAP.pth"))
-            if res is None or res[8] == best_r or not os.path.exists(os.path.join(args.out, args.name + "_bestAR.pth")):
+            if res is None or res[12] == best_r or not os.path.exists(os.path.join(args.out, args.name + "_bestAR.pth")):
                 torch.save(chkpt, os.path.join(args.out, args.name + "_bestAR.pth"))
             if args.stop_at and iteration >= args.stop_at:
                 break
-    head.push_into(pred)
-    summary["ap_after"] = do_test(pred, test_dicts, gt)
+    push_heads()
+    summary["after"] = do_test(pred, test_dicts, gt)
     summary["checkpoint"] = last_path
-    summary["state"] = {k: v.cpu() for k, v in head.state_dict().items()}
+    summary["state"] = {k: v.cpu() for k, v in list(rpn_head.state_dict("proposal_generator.rpn_head.").items())
+                        + list(box_head.state_dict("roi_heads.").items())}
+    summary["predictor"] = pred
     return summary
 
 
