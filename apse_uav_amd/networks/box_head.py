@@ -19,6 +19,7 @@ import ctypes as C
 import torch
 
 from .. import _lib
+from .head_base import TrainableHead, _check, relu_grad, roi_nhwc, workspace_tensor
 
 PREFIX = "roi_heads."
 FC_DIM = 1024
@@ -35,17 +36,12 @@ def _names():
     return [n + s for n in NAMES for s in (".weight", ".bias")]
 
 
-def _check(rc, what):
-    if rc != _lib.APSE_OK:
-        raise _lib.ApseError("%s failed (code %d) %s" % (what, rc, _lib.load().apse_last_error(None).decode()))
-
-
 def _workspace(n, K, device):
     nbytes = int(_lib.load().apse_box_train_workspace_bytes(int(n), int(K)))
     if nbytes == 0:
         raise _lib.ApseError("box-head training needs 1 <= n <= %d RoIs and 1 <= K <= %d classes (got n = %d, K = %d)"
                              % (MAX_ROIS, MAX_CLASSES, n, K))
-    return torch.empty((nbytes + 3) // 4, dtype=torch.float32, device=device)
+    return workspace_tensor(nbytes, device)
 
 
 def _w4(weights):
@@ -108,13 +104,6 @@ def bias_grad(dy, ws):
     _check(_lib.load().apse_box_bias_grad(_lib.ptr(dy), n, O, _lib.ptr(db), _lib.ptr(ws), ws.numel() * 4, _lib.stream_ptr()),
            "apse_box_bias_grad")
     return db
-
-
-def relu_grad(y, dy):
-    g = torch.empty_like(dy)
-    _check(_lib.load().apse_mask_relu_grad(_lib.ptr(y), _lib.ptr(dy), dy.numel(), _lib.ptr(g), _lib.stream_ptr()),
-           "apse_mask_relu_grad")
-    return g
 
 
 def loss_forward(logits, deltas, labels, prop_boxes, gt_boxes, ws, weights=BBOX_REG_WEIGHTS, beta=0.0):
@@ -187,22 +176,22 @@ class _BoxLoss(torch.autograd.Function):
         return (None,) * 6 + tuple(grads)
 
 
-class BoxHead:
+class BoxHead(TrainableHead):
+    prefix = PREFIX
+    names = _names()
+    noun = "box-head"
+
     def __init__(self, num_classes, device="cuda", smooth_l1_beta=0.0):
         if not 1 <= int(num_classes) <= MAX_CLASSES:
             raise ValueError("BoxHead: num_classes must be in 1..%d (APSE_MAX_CLASSES), got %d" % (MAX_CLASSES, num_classes))
         self.num_classes = K = int(num_classes)
         self.smooth_l1_beta = float(smooth_l1_beta)
-        self._device = torch.device(device)
-        self.training = True
-        self.last_stats = None                # f32 [8] on the device after a forward: apse_box_loss_forward's out8
-        self._shapes = {
+        super().__init__({                    # last_stats: f32 [8], apse_box_loss_forward's out8
             "box_head.fc1.weight": (FC_DIM, FEAT), "box_head.fc1.bias": (FC_DIM,),
             "box_head.fc2.weight": (FC_DIM, FC_DIM), "box_head.fc2.bias": (FC_DIM,),
             "box_predictor.cls_score.weight": (K + 1, FC_DIM), "box_predictor.cls_score.bias": (K + 1,),
             "box_predictor.bbox_pred.weight": (4 * K, FC_DIM), "box_predictor.bbox_pred.bias": (4 * K,),
-        }
-        self._params = None
+        }, device)
 
     @classmethod
     def from_cfg(cls, cfg, device="cuda"):
@@ -213,96 +202,20 @@ class BoxHead:
                                       "under C4 (Res5ROIHeads) the box branch is the res5 stage")
         return cls(int(cfg.MODEL.ROI_HEADS.NUM_CLASSES), device)
 
-    # ---- parameters
-    def _init(self, only=None):
+    def _init_tensor(self, name, t):
         """detectron2's initialisation: c2_xavier_fill (kaiming_uniform_(a = 1), bias 0) on fc1 / fc2, normal(std = 0.01) on
-        cls_score, normal(std = 0.001) on bbox_pred, biases 0; drawn on the CPU from torch's global generator."""
-        ps = dict(self._params or {})
-        for name in _names():
-            if only is not None and not name.startswith(only):
-                continue
-            t = torch.zeros(self._shapes[name])
-            if name.endswith(".weight"):
-                if name.startswith("box_head"):
-                    torch.nn.init.kaiming_uniform_(t, a=1)
-                else:
-                    torch.nn.init.normal_(t, std=0.01 if "cls_score" in name else 0.001)
-            ps[name] = t.to(self._device).requires_grad_(True)
-        self._params = ps
-
-    def named_parameters(self):
-        if self._params is None:
-            self._init()
-        return iter([(k, self._params[k]) for k in _names()])
-
-    def parameters(self, recurse=True):
-        return iter([p for _, p in self.named_parameters()])
-
-    def to(self, device):
-        self._device = torch.device(device)
-        if self._params is not None:
-            for p in self._params.values():
-                p.data = p.data.to(self._device)
-                if p.grad is not None:
-                    p.grad = p.grad.to(self._device)
-        return self
-
-    def state_dict(self, prefix=""):
-        return {prefix + k: p.detach().clone() for k, p in self.named_parameters()}
+        cls_score, normal(std = 0.001) on bbox_pred."""
+        if name.startswith("box_head"):
+            torch.nn.init.kaiming_uniform_(t, a=1)
+        else:
+            torch.nn.init.normal_(t, std=0.01 if "cls_score" in name else 0.001)
 
     def load_state_dict(self, sd, strict=True, keep_predictor=False):
-        """Accepts the bare names or the detector's (``roi_heads.`` prefix; other keys of a full detector are ignored).
-        ``keep_predictor``: load fc1 / fc2 only and leave ``box_predictor.*`` as initialised (a checkpoint of another class
-        count)."""
-        if self._params is None:
-            if keep_predictor:
-                self._init()
-            else:
-                self._params = {k: torch.zeros(self._shapes[k], device=self._device).requires_grad_(True) for k in _names()}
-        missing = []
-        with torch.no_grad():
-            for k in _names():
-                if keep_predictor and k.startswith("box_predictor"):
-                    continue
-                src = sd.get(k, sd.get(PREFIX + k))
-                if src is None:
-                    missing.append(k)
-                    continue
-                src = torch.as_tensor(src)
-                if tuple(src.shape) != tuple(self._shapes[k]):
-                    raise RuntimeError("size mismatch for %s: %s vs %s" % (k, tuple(src.shape), tuple(self._shapes[k])))
-                self._params[k].copy_(src.to(torch.float32))
-        if missing and strict:
-            raise RuntimeError("missing box-head keys: %s" % ", ".join(missing))
-        return missing
-
-    def zero_grad(self, set_to_none=True):
-        for p in self.parameters():
-            if p.grad is not None:
-                if set_to_none:
-                    p.grad = None
-                else:
-                    p.grad.detach_()
-                    p.grad.zero_()
-
-    def train(self, mode=True):
-        self.training = bool(mode)
-        return self
-
-    def eval(self):
-        return self.train(False)
+        """TrainableHead.load_state_dict.  ``keep_predictor``: load fc1 / fc2 only and leave ``box_predictor.*`` as initialised
+        (a checkpoint of another class count)."""
+        return super().load_state_dict(sd, strict, ("box_predictor",) if keep_predictor else ())
 
     # ---- compute
-    @staticmethod
-    def _nhwc(x):
-        if x.dim() != 4:
-            raise ValueError("RoI features must be [n][7][7][256] (NHWC) or [n][256][7][7]")
-        if tuple(x.shape[1:]) == (POOL, POOL, CONV_DIM):
-            return x.to(torch.float32).contiguous()
-        if tuple(x.shape[1:]) == (CONV_DIM, POOL, POOL):
-            return x.to(torch.float32).permute(0, 2, 3, 1).contiguous()
-        raise ValueError("RoI features must be [n][7][7][256] (NHWC) or [n][256][7][7], got %s" % (tuple(x.shape),))
-
     def _check_input(self, x):
         if not x.is_cuda:
             raise _lib.ApseError("BoxHead needs GPU tensors (no CPU fallback)")
@@ -312,7 +225,7 @@ class BoxHead:
     def predict(self, roi_features):
         """(logits [n][K + 1], deltas [n][4 K]) of the current weights (no graph)."""
         self._check_input(roi_features)
-        x = self._nhwc(roi_features)
+        x = roi_nhwc(roi_features, POOL)
         K = self.num_classes
         if x.shape[0] == 0:
             return torch.zeros((0, K + 1), device=x.device), torch.zeros((0, 4 * K), device=x.device)
@@ -324,7 +237,7 @@ class BoxHead:
         sampled boxes and their matched ground truths, read on foreground rows) -> {"loss_cls", "loss_box_reg"}.
         ``last_stats`` holds apse_box_loss_forward's out8."""
         self._check_input(roi_features)
-        x = self._nhwc(roi_features)
+        x = roi_nhwc(roi_features, POOL)
         n = x.shape[0]
         params = list(self.parameters())
         if n == 0:
@@ -344,33 +257,8 @@ class BoxHead:
 
     __call__ = forward
 
-    def push_into(self, model):
-        """Loads the current head weights into a TrackRCNN (or a TrackPredictor's ``model``): its state gets the
-        ``roi_heads.box_head.*`` / ``roi_heads.box_predictor.*`` entries replaced and its context is rebuilt on the next frame."""
-        target = getattr(model, "model", model)
-        if target._state is None:
-            raise _lib.ApseError("push_into: the detector has no weights loaded")
-        sd = dict(target._state)
-        sd.update({k: v.cpu() for k, v in self.state_dict(PREFIX).items()})
-        target.load_state_dict(sd)
-        return model
-
 
 def merge_box_head(detector_state, box_head_state):
     """A full detector checkpoint with the eight box-branch tensors taken from ``box_head_state`` (bare names or ``roi_heads.``
     prefixed; an optional leading ``model.`` is dropped): the counterpart of merge_full_mask_rcnn."""
-    out = {}
-    for k, v in detector_state.items():
-        out[k[6:] if k.startswith("model.") else k] = v
-    found = 0
-    for k, v in box_head_state.items():
-        k = k[6:] if k.startswith("model.") else k
-        bare = k[len(PREFIX):] if k.startswith(PREFIX) else k
-        if bare in _names():
-            out[PREFIX + bare] = torch.as_tensor(v).detach().cpu()
-            found += 1
-        elif not k.startswith(("backbone.", "proposal_generator.", "roi_heads.", "pixel_")):
-            raise KeyError("merge_box_head: %r is not a box-head parameter" % k)
-    if found != len(_names()):
-        raise KeyError("merge_box_head: the box-head state has %d of %d parameters" % (found, len(_names())))
-    return out
+    return BoxHead.merge_into(detector_state, box_head_state, "merge_box_head")

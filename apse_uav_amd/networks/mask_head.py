@@ -17,6 +17,7 @@ RoI features are NHWC ``[n][14][14][256]`` (``apse_mask_roi_features`` / ``Track
 import torch
 
 from .. import _lib
+from .head_base import TrainableHead, _check, relu_grad, roi_nhwc, workspace_tensor
 
 PREFIX = "roi_heads.mask_head."
 CONV_DIM = 256
@@ -26,17 +27,12 @@ MAX_ROIS = 1024            # APSE_MASK_TRAIN_MAX_N
 MAX_CLASSES = 80           # APSE_MAX_CLASSES
 
 
-def _check(rc, what):
-    if rc != _lib.APSE_OK:
-        raise _lib.ApseError("%s failed (code %d) %s" % (what, rc, _lib.load().apse_last_error(None).decode()))
-
-
 def _workspace(n, K, device):
     nbytes = int(_lib.load().apse_mask_train_workspace_bytes(int(n), int(K)))
     if nbytes == 0:
         raise _lib.ApseError("mask-head training needs 1 <= n <= %d RoIs and 1 <= K <= %d classes (got n = %d, K = %d)"
                              % (MAX_ROIS, MAX_CLASSES, n, K))
-    return torch.empty((nbytes + 3) // 4, dtype=torch.float32, device=device)
+    return workspace_tensor(nbytes, device)
 
 
 # ---- thin operator wrappers (also the surface the layer tests drive)
@@ -68,13 +64,6 @@ def conv3x3(x, packed, bias_p, relu):
     _check(_lib.load().apse_mask_conv3x3(_lib.ptr(x), _lib.ptr(packed), _lib.ptr(bias_p), x.shape[0], int(relu), _lib.ptr(y),
                                          _lib.stream_ptr()), "apse_mask_conv3x3")
     return y
-
-
-def relu_grad(y, dy):
-    g = torch.empty_like(dy)
-    _check(_lib.load().apse_mask_relu_grad(_lib.ptr(y), _lib.ptr(dy), dy.numel(), _lib.ptr(g), _lib.stream_ptr()),
-           "apse_mask_relu_grad")
-    return g
 
 
 def bias_grad(g, ws):
@@ -186,14 +175,16 @@ def _names():
     return names + ["deconv.weight", "deconv.bias", "predictor.weight", "predictor.bias"]
 
 
-class MaskHead:
+class MaskHead(TrainableHead):
+    prefix = PREFIX
+    names = _names()
+    noun = "mask-head"
+    stray_under_prefix = True
+
     def __init__(self, num_classes, device="cuda"):
         if not 1 <= int(num_classes) <= MAX_CLASSES:
             raise ValueError("MaskHead: num_classes must be in 1..%d (APSE_MAX_CLASSES), got %d" % (MAX_CLASSES, num_classes))
         self.num_classes = int(num_classes)
-        self._device = torch.device(device)
-        self.training = True
-        self.last_stats = None                # f32 [4] on the device after a forward: loss, accuracy, false positive, false negative
         shapes = {}
         for i in range(1, NUM_CONV + 1):
             shapes["mask_fcn%d.weight" % i] = (CONV_DIM, CONV_DIM, 3, 3)
@@ -202,8 +193,7 @@ class MaskHead:
         shapes["deconv.bias"] = (CONV_DIM,)
         shapes["predictor.weight"] = (self.num_classes, CONV_DIM, 1, 1)
         shapes["predictor.bias"] = (self.num_classes,)
-        self._shapes = shapes
-        self._params = None
+        super().__init__(shapes, device)      # last_stats: f32 [4], loss, accuracy, false positive, false negative
 
     @classmethod
     def from_cfg(cls, cfg, device="cuda"):
@@ -214,87 +204,15 @@ class MaskHead:
                                       "under C4 (Res5ROIHeads) the mask branch shares res5 with the box branch")
         return cls(int(cfg.MODEL.ROI_HEADS.NUM_CLASSES), device)
 
-    # ---- parameters
-    def _init(self):
+    def _init_tensor(self, name, t):
         """detectron2's initialisation: c2_msra_fill (kaiming_normal_, fan_out, relu; bias 0) on the convolutions and the
-        deconvolution, normal(std = 0.001) on the predictor; drawn on the CPU from torch's global generator."""
-        ps = {}
-        for name in _names():
-            t = torch.zeros(self._shapes[name])
-            if name.endswith(".weight"):
-                if name.startswith("predictor"):
-                    torch.nn.init.normal_(t, std=0.001)
-                else:
-                    torch.nn.init.kaiming_normal_(t, mode="fan_out", nonlinearity="relu")
-            ps[name] = t.to(self._device).requires_grad_(True)
-        self._params = ps
-
-    def named_parameters(self):
-        if self._params is None:
-            self._init()
-        return iter([(k, self._params[k]) for k in _names()])
-
-    def parameters(self, recurse=True):
-        return iter([p for _, p in self.named_parameters()])
-
-    def to(self, device):
-        self._device = torch.device(device)
-        if self._params is not None:
-            for p in self._params.values():
-                p.data = p.data.to(self._device)
-                if p.grad is not None:
-                    p.grad = p.grad.to(self._device)
-        return self
-
-    def state_dict(self, prefix=""):
-        return {prefix + k: p.detach().clone() for k, p in self.named_parameters()}
-
-    def load_state_dict(self, sd, strict=True):
-        """Accepts the bare names or the detector's (``roi_heads.mask_head.`` prefix; other keys of a full detector are ignored)."""
-        if self._params is None:
-            self._params = {k: torch.zeros(self._shapes[k], device=self._device).requires_grad_(True) for k in _names()}
-        missing = []
-        with torch.no_grad():
-            for k in _names():
-                src = sd.get(k, sd.get(PREFIX + k))
-                if src is None:
-                    missing.append(k)
-                    continue
-                src = torch.as_tensor(src)
-                if tuple(src.shape) != tuple(self._shapes[k]):
-                    raise RuntimeError("size mismatch for %s: %s vs %s" % (k, tuple(src.shape), tuple(self._shapes[k])))
-                self._params[k].copy_(src.to(torch.float32))
-        if missing and strict:
-            raise RuntimeError("missing mask-head keys: %s" % ", ".join(missing))
-        return missing
-
-    def zero_grad(self, set_to_none=True):
-        for p in self.parameters():
-            if p.grad is not None:
-                if set_to_none:
-                    p.grad = None
-                else:
-                    p.grad.detach_()
-                    p.grad.zero_()
-
-    def train(self, mode=True):
-        self.training = bool(mode)
-        return self
-
-    def eval(self):
-        return self.train(False)
+        deconvolution, normal(std = 0.001) on the predictor."""
+        if name.startswith("predictor"):
+            torch.nn.init.normal_(t, std=0.001)
+        else:
+            torch.nn.init.kaiming_normal_(t, mode="fan_out", nonlinearity="relu")
 
     # ---- compute
-    @staticmethod
-    def _nhwc(x):
-        if x.dim() != 4:
-            raise ValueError("RoI features must be [n][14][14][256] (NHWC) or [n][256][14][14]")
-        if tuple(x.shape[1:]) == (POOL, POOL, CONV_DIM):
-            return x.to(torch.float32).contiguous()
-        if tuple(x.shape[1:]) == (CONV_DIM, POOL, POOL):
-            return x.to(torch.float32).permute(0, 2, 3, 1).contiguous()
-        raise ValueError("RoI features must be [n][14][14][256] (NHWC) or [n][256][14][14], got %s" % (tuple(x.shape),))
-
     def _check_input(self, x):
         if not x.is_cuda:
             raise _lib.ApseError("MaskHead needs GPU tensors (no CPU fallback)")
@@ -304,7 +222,7 @@ class MaskHead:
     def logits(self, roi_features):
         """Mask logits [n][28][28][K] of the current weights (no graph)."""
         self._check_input(roi_features)
-        x = self._nhwc(roi_features)
+        x = roi_nhwc(roi_features, POOL)
         n = x.shape[0]
         if n == 0:
             return torch.zeros((0, 28, 28, self.num_classes), device=x.device)
@@ -315,7 +233,7 @@ class MaskHead:
         """roi_features [n][14][14][256]; gt_classes [n] integer class indices; targets [n][28][28] (non-zero = inside) ->
         {"loss_mask": scalar tensor}.  ``last_stats`` holds the loss and detectron2's three logged ratios."""
         self._check_input(roi_features)
-        x = self._nhwc(roi_features)
+        x = roi_nhwc(roi_features, POOL)
         n = x.shape[0]
         params = list(self.parameters())
         if n == 0:
@@ -336,34 +254,8 @@ class MaskHead:
 
     __call__ = forward
 
-    def push_into(self, model):
-        """Loads the current head weights into a TrackRCNN (or a TrackPredictor's ``model``): its state gets the
-        ``roi_heads.mask_head.*`` entries replaced and its context is rebuilt on the next frame."""
-        target = getattr(model, "model", model)
-        if target._state is None:
-            raise _lib.ApseError("push_into: the detector has no weights loaded")
-        sd = dict(target._state)
-        sd.update({k: v.cpu() for k, v in self.state_dict(PREFIX).items()})
-        target.load_state_dict(sd)
-        return model
-
 
 def merge_full_mask_rcnn(detector_state, mask_head_state):
     """The merged checkpoint of add_mask_head_to_frcnn.py / finetune_segmentation.py: every key of the detector, with
     ``roi_heads.mask_head.*`` taken from ``mask_head_state`` (bare names or prefixed; an optional leading ``model.`` is dropped)."""
-    out = {}
-    for k, v in detector_state.items():
-        out[k[6:] if k.startswith("model.") else k] = v
-    found = 0
-    for k, v in mask_head_state.items():
-        k = k[6:] if k.startswith("model.") else k
-        if k.startswith(PREFIX):
-            k = k[len(PREFIX):]
-        if k in _names():
-            out[PREFIX + k] = torch.as_tensor(v).detach().cpu()
-            found += 1
-        elif not k.startswith(("backbone.", "proposal_generator.", "roi_heads.", "pixel_")):
-            raise KeyError("merge_full_mask_rcnn: %r is not a mask-head parameter" % k)
-    if found != len(_names()):
-        raise KeyError("merge_full_mask_rcnn: the mask-head state has %d of %d parameters" % (found, len(_names())))
-    return out
+    return MaskHead.merge_into(detector_state, mask_head_state, "merge_full_mask_rcnn")

@@ -20,6 +20,7 @@ import torch
 
 from .. import _lib
 from . import box_head as bh
+from .head_base import TrainableHead, _check, workspace_tensor
 
 PREFIX = "proposal_generator.rpn_head."
 CONV_DIM = 256
@@ -38,16 +39,13 @@ def _names():
     return [n + s for n in NAMES for s in (".weight", ".bias")]
 
 
-_check = bh._check
-
-
 def train_workspace(A, G, S, device):
     """The workspace of the labelling of A anchors against G ground truths / the loss of S rows (f32 elements)."""
     nbytes = int(_lib.load().apse_rpn_train_workspace_bytes(int(A), int(G), int(S)))
     if nbytes == 0:
         raise _lib.ApseError("RPN-head training needs A <= 2^22 anchors, G <= 4096 ground truths and S <= 2^20 rows "
                              "(got A = %d, G = %d, S = %d)" % (A, G, S))
-    return torch.empty((nbytes + 3) // 4, dtype=torch.float32, device=device)
+    return workspace_tensor(nbytes, device)
 
 
 # ---- thin operator wrappers (also the surface the layer tests drive)
@@ -146,15 +144,16 @@ class _RpnLoss(torch.autograd.Function):
         return (None,) * 8 + tuple(grads)
 
 
-class RPNHead:
+class RPNHead(TrainableHead):
+    prefix = PREFIX
+    names = _names()
+    noun = "RPN-head"
+    a_noun = "an RPN-head"
+
     def __init__(self, device="cuda", smooth_l1_beta=0.0, batch_size_per_image=256):
         self.smooth_l1_beta = float(smooth_l1_beta)
         self.batch_size_per_image = int(batch_size_per_image)
-        self._device = torch.device(device)
-        self.training = True
-        self.last_stats = None                # f32 [8] on the device after a forward: apse_rpn_loss_forward's out8
-        self._shapes = dict(SHAPES)
-        self._params = None
+        super().__init__(dict(SHAPES), device)          # last_stats: f32 [8], apse_rpn_loss_forward's out8
 
     @classmethod
     def from_cfg(cls, cfg, device="cuda"):
@@ -165,73 +164,9 @@ class RPNHead:
                                       "the C4 head (res4, 15 anchors, 1024 channels) is not covered")
         return cls(device)
 
-    # ---- parameters
-    def _init(self):
-        """detectron2's initialisation: normal(std = 0.01) on the three weights, biases 0; drawn on the CPU from torch's global
-        generator."""
-        ps = {}
-        for name in _names():
-            t = torch.zeros(self._shapes[name])
-            if name.endswith(".weight"):
-                torch.nn.init.normal_(t, std=0.01)
-            ps[name] = t.to(self._device).requires_grad_(True)
-        self._params = ps
-
-    def named_parameters(self):
-        if self._params is None:
-            self._init()
-        return iter([(k, self._params[k]) for k in _names()])
-
-    def parameters(self, recurse=True):
-        return iter([p for _, p in self.named_parameters()])
-
-    def to(self, device):
-        self._device = torch.device(device)
-        if self._params is not None:
-            for p in self._params.values():
-                p.data = p.data.to(self._device)
-                if p.grad is not None:
-                    p.grad = p.grad.to(self._device)
-        return self
-
-    def state_dict(self, prefix=""):
-        return {prefix + k: p.detach().clone() for k, p in self.named_parameters()}
-
-    def load_state_dict(self, sd, strict=True):
-        """Accepts the bare names or the detector's (``proposal_generator.rpn_head.`` prefix; other keys of a full detector are
-        ignored)."""
-        if self._params is None:
-            self._params = {k: torch.zeros(self._shapes[k], device=self._device).requires_grad_(True) for k in _names()}
-        missing = []
-        with torch.no_grad():
-            for k in _names():
-                src = sd.get(k, sd.get(PREFIX + k))
-                if src is None:
-                    missing.append(k)
-                    continue
-                src = torch.as_tensor(src)
-                if tuple(src.shape) != tuple(self._shapes[k]):
-                    raise RuntimeError("size mismatch for %s: %s vs %s" % (k, tuple(src.shape), tuple(self._shapes[k])))
-                self._params[k].copy_(src.to(torch.float32))
-        if missing and strict:
-            raise RuntimeError("missing RPN-head keys: %s" % ", ".join(missing))
-        return missing
-
-    def zero_grad(self, set_to_none=True):
-        for p in self.parameters():
-            if p.grad is not None:
-                if set_to_none:
-                    p.grad = None
-                else:
-                    p.grad.detach_()
-                    p.grad.zero_()
-
-    def train(self, mode=True):
-        self.training = bool(mode)
-        return self
-
-    def eval(self):
-        return self.train(False)
+    def _init_tensor(self, name, t):
+        """detectron2's initialisation: normal(std = 0.01) on the three weights."""
+        torch.nn.init.normal_(t, std=0.01)
 
     # ---- compute
     def _rows(self, patches):
@@ -280,33 +215,8 @@ class RPNHead:
 
     __call__ = forward
 
-    def push_into(self, model):
-        """Loads the current head weights into a TrackRCNN (or a TrackPredictor's ``model``): its state gets the
-        ``proposal_generator.rpn_head.*`` entries replaced and its context is rebuilt on the next frame."""
-        target = getattr(model, "model", model)
-        if target._state is None:
-            raise _lib.ApseError("push_into: the detector has no weights loaded")
-        sd = dict(target._state)
-        sd.update({k: v.cpu() for k, v in self.state_dict(PREFIX).items()})
-        target.load_state_dict(sd)
-        return model
-
 
 def merge_rpn_head(detector_state, rpn_state):
     """A full detector checkpoint with the six RPN-head tensors taken from ``rpn_state`` (bare names or
     ``proposal_generator.rpn_head.`` prefixed; an optional leading ``model.`` is dropped): the counterpart of merge_box_head."""
-    out = {}
-    for k, v in detector_state.items():
-        out[k[6:] if k.startswith("model.") else k] = v
-    found = 0
-    for k, v in rpn_state.items():
-        k = k[6:] if k.startswith("model.") else k
-        bare = k[len(PREFIX):] if k.startswith(PREFIX) else k
-        if bare in _names():
-            out[PREFIX + bare] = torch.as_tensor(v).detach().cpu()
-            found += 1
-        elif not k.startswith(("backbone.", "proposal_generator.", "roi_heads.", "pixel_")):
-            raise KeyError("merge_rpn_head: %r is not an RPN-head parameter" % k)
-    if found != len(_names()):
-        raise KeyError("merge_rpn_head: the RPN-head state has %d of %d parameters" % (found, len(_names())))
-    return out
+    return RPNHead.merge_into(detector_state, rpn_state, "merge_rpn_head")

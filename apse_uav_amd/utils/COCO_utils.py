@@ -195,10 +195,11 @@ class MaskTrainLoader:
         self.rng.bit_generator.state = sd["rng"]
         self._order = list(sd["order"])
 
-    def prepare_image(self, d, flipped=False):
-        """One image through the frozen backbone at the test size: (boxes f64 [G][4] in resized-image pixels, polygons, classes)."""
+    @staticmethod
+    def read_annotated(d):
+        """The image of a dataset dictionary and its annotations as they are stored: (frame BGR uint8 [H][W][3], boxes f64 [G][4]
+        XYXY, polygons, classes int64 [G]).  An image whose size is not the annotated one is refused."""
         from PIL import Image
-        model = self.model
         frame = np.asarray(Image.open(d["file_name"]).convert("RGB"))[:, :, ::-1].copy()
         H, W = frame.shape[:2]
         if (H, W) != (d["height"], d["width"]):
@@ -207,6 +208,13 @@ class MaskTrainLoader:
                           for a in d["annotations"]], np.float64).reshape(-1, 4)
         polys = [a["segmentation"] for a in d["annotations"]]
         classes = torch.tensor([a["category_id"] for a in d["annotations"]], dtype=torch.int64)
+        return frame, boxes, polys, classes
+
+    def prepare_image(self, d, flipped=False):
+        """One image through the frozen backbone at the test size: (boxes f64 [G][4] in resized-image pixels, polygons, classes)."""
+        model = self.model
+        frame, boxes, polys, classes = self.read_annotated(d)
+        H, W = frame.shape[:2]
         if flipped:
             frame = frame[:, ::-1].copy()
             boxes, polys = flip_annotations(boxes, polys, W)
@@ -217,34 +225,13 @@ class MaskTrainLoader:
         model.backbone_frames(torch.from_numpy(frame[None]).to(model.device))
         return boxes, polys, classes
 
-    def image_item(self, d, flipped=False):
-        """One image through the frozen backbone: (features, classes, targets) of its ground-truth boxes."""
-        key = d["image_id"]
-        if self.cache is not None and key in self.cache:
-            return self.cache[key]
-        model = self.model
-        boxes, polys, classes = self.prepare_image(d, flipped)
-        feats = model.mask_roi_features(boxes.astype(np.float32))
-        targets = mask_targets(polys, boxes, model.device)
-        item = (feats, classes, targets)
-        if self.cache is not None:
-            self.cache[key] = item
-        return item
-
     def prepare_augmented(self, d, size, params):
         """One image down the device path: resized to short edge ``size``, augmented with ``params`` (utils.augment.AugmentParams),
         through the frozen backbone: (transformed boxes f64 [G][4], polygons, classes)."""
-        from PIL import Image
         from . import augment as aug
         model = self.model
-        frame = np.asarray(Image.open(d["file_name"]).convert("RGB"))[:, :, ::-1].copy()
+        frame, boxes, polys, classes = self.read_annotated(d)
         H, W = frame.shape[:2]
-        if (H, W) != (d["height"], d["width"]):
-            raise ValueError("%s is %dx%d, the annotations say %dx%d" % (d["file_name"], H, W, d["height"], d["width"]))
-        boxes = np.array([[a["bbox"][0], a["bbox"][1], a["bbox"][0] + a["bbox"][2], a["bbox"][1] + a["bbox"][3]]
-                          for a in d["annotations"]], np.float64).reshape(-1, 4)
-        polys = [a["segmentation"] for a in d["annotations"]]
-        classes = torch.tensor([a["category_id"] for a in d["annotations"]], dtype=torch.int64)
         ih, iw = resample.resize_shortest_edge(H, W, size, self.max_size)
         boxes, polys = aug.transform_annotations(boxes, polys, (H, W), (ih, iw), params.flip)
         resized = aug.resize_frames(torch.from_numpy(frame[None]).to(model.device), ih, iw)
@@ -252,11 +239,25 @@ class MaskTrainLoader:
         model.backbone_images(chw, (H, W))
         return boxes, polys, classes
 
-    def augmented_item(self, d, size, params):
-        """``prepare_augmented``, then (features, classes, targets) of the transformed ground-truth boxes."""
-        boxes, polys, classes = self.prepare_augmented(d, size, params)
+    def _sample(self, boxes, polys, classes, d):
+        """The item of one image whose backbone has just run, from its transformed annotations: here (features, classes, targets)
+        of the ground-truth boxes.  The loaders that subclass this one override it."""
         feats = self.model.mask_roi_features(boxes.astype(np.float32))
         return feats, classes, mask_targets(polys, boxes, self.model.device)
+
+    def image_item(self, d, flipped=False):
+        """One image through the frozen backbone at the test size, then ``_sample``."""
+        key = d["image_id"]
+        if self.cache is not None and key in self.cache:
+            return self.cache[key]
+        item = self._sample(*self.prepare_image(d, flipped), d)
+        if self.cache is not None:
+            self.cache[key] = item
+        return item
+
+    def augmented_item(self, d, size, params):
+        """``prepare_augmented``, then ``_sample``."""
+        return self._sample(*self.prepare_augmented(d, size, params), d)
 
     def __iter__(self):
         return self

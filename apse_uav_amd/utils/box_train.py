@@ -42,7 +42,41 @@ def label_and_sample_proposals(proposals, gt_boxes, gt_classes, num_classes, bat
     return cand[sel], labels[sel], matched, (int(pos.numel()), int(neg.numel()))
 
 
-class BoxTrainLoader(MaskTrainLoader):
+class SamplingLoader(MaskTrainLoader):
+    """What the loaders that sample rows on the device share on top of MaskTrainLoader: the ground truth of an image on the
+    device and named device generators whose states travel in ``state_dict``.  A subclass calls ``seed_generators`` once and
+    overrides ``_sample``."""
+
+    def seed_generators(self, **seeds):
+        """One ``torch.Generator`` on the model's device per name, seeded, as an attribute of that name; ``state_dict`` carries
+        their states under the same names, in this order."""
+        self._generators = {}
+        for name, seed in seeds.items():
+            g = torch.Generator(device=self.model.device)
+            g.manual_seed(int(seed))
+            self._generators[name] = g
+            setattr(self, name, g)
+
+    def state_dict(self):
+        sd = super().state_dict()
+        for name, g in self._generators.items():
+            sd[name] = g.get_state().clone()
+        return sd
+
+    def load_state_dict(self, sd):
+        super().load_state_dict(sd)
+        for name, g in self._generators.items():
+            g.set_state(sd[name].cpu())
+
+    def ground_truth(self, boxes, classes, d):
+        """The image's non-crowd annotations on the device: (boxes f32 [G][4], classes int32 [G])."""
+        dev = self.model.device
+        keep = [i for i, a in enumerate(d["annotations"]) if not a.get("iscrowd", 0)]
+        gt = torch.from_numpy(np.asarray(boxes, np.float64)[keep].astype(np.float32)).reshape(-1, 4).to(dev)
+        return gt, torch.as_tensor(classes)[keep].to(dev, torch.int32)
+
+
+class BoxTrainLoader(SamplingLoader):
     """Yields (roi_features [n][7][7][256], labels int32 [n], proposal_boxes f32 [n][4], gt_boxes f32 [n][4]) per batch of
     ``ims_per_batch`` images, endlessly, in a seeded shuffled order.  ``model``: a TrackRCNN (FPN) with the frozen detector's
     weights.  Per image: the image and annotation path of MaskTrainLoader (test size on the host, or the device path with
@@ -65,36 +99,16 @@ class BoxTrainLoader(MaskTrainLoader):
         if self.ims_per_batch * self.batch_size_per_image > bh.MAX_ROIS:
             raise ValueError("%d images x %d RoIs exceed the %d RoIs of one step (APSE_BOX_TRAIN_MAX_N)"
                              % (self.ims_per_batch, self.batch_size_per_image, bh.MAX_ROIS))
-        self.generator = torch.Generator(device=model.device)
-        self.generator.manual_seed(int(seed))
+        self.seed_generators(generator=seed)
         self.last_counts = []                 # (num_fg, num_bg) per image of the last batch
 
-    def state_dict(self):
-        sd = super().state_dict()
-        sd["generator"] = self.generator.get_state().clone()
-        return sd
-
-    def load_state_dict(self, sd):
-        super().load_state_dict(sd)
-        self.generator.set_state(sd["generator"].cpu())
-
-    def _sample(self, boxes, classes, d):
+    def _sample(self, boxes, polys, classes, d):
         model = self.model
-        keep = [i for i, a in enumerate(d["annotations"]) if not a.get("iscrowd", 0)]
-        gt = torch.from_numpy(np.asarray(boxes, np.float64)[keep].astype(np.float32)).reshape(-1, 4).to(model.device)
-        cls = torch.as_tensor(classes)[keep].to(model.device, torch.int32)
+        gt, cls = self.ground_truth(boxes, classes, d)
         props = model.train_proposals(1, *self.train_topk)[0][0] if self.train_topk else model.proposals_after_backbone(1)[0]
         sb, labels, matched, counts = label_and_sample_proposals(props, gt, cls, self.num_classes, self.batch_size_per_image,
                                                                  self.positive_fraction, self.generator, self.iou_thresh)
         return model.box_roi_features(sb), labels, sb, matched, counts
-
-    def image_item(self, d, flipped=False):
-        boxes, _, classes = self.prepare_image(d, flipped)
-        return self._sample(boxes, classes, d)
-
-    def augmented_item(self, d, size, params):
-        boxes, _, classes = self.prepare_augmented(d, size, params)
-        return self._sample(boxes, classes, d)
 
     def __next__(self):
         items = self.next_items()

@@ -2,13 +2,11 @@
 box head's proposals come from the RPN head as it is at that step (``TrackRCNN.set_rpn_head`` follows every optimiser step), at
 detectron2's training limits (``TrackRCNN.train_proposals``).
 """
-import numpy as np
 import torch
 
 from ..networks import box_head as bh
 from ..networks import rpn_head as rh
-from .box_train import label_and_sample_proposals
-from .COCO_utils import MaskTrainLoader
+from .box_train import SamplingLoader, label_and_sample_proposals
 from .rpn_train import label_and_sample_anchors
 
 
@@ -47,7 +45,7 @@ def box_losses_chunked(head, feats, labels, prop_boxes, gt_boxes, rows_per_image
     return out
 
 
-class JointTrainLoader(MaskTrainLoader):
+class JointTrainLoader(SamplingLoader):
     """Yields (rpn, box) per batch of ``ims_per_batch`` images, endlessly, in a seeded shuffled order:
 
     * rpn = (patches f32 [n][2304], slots int32 [n], labels int32 [n], anchor_boxes f32 [n][4], gt_boxes f32 [n][4]), the tuple
@@ -77,31 +75,15 @@ class JointTrainLoader(MaskTrainLoader):
                              % (self.ims_per_batch, self.rpn_batch_size_per_image, rh.MAX_ROWS))
         if self.box_batch_size_per_image > bh.MAX_ROIS:
             raise ValueError("%d RoIs per image exceed the %d of one chunk (APSE_BOX_TRAIN_MAX_N)" % (self.box_batch_size_per_image, bh.MAX_ROIS))
-        self.rpn_generator = torch.Generator(device=model.device)
-        self.rpn_generator.manual_seed(int(seed))
-        self.box_generator = torch.Generator(device=model.device)
-        self.box_generator.manual_seed(int(seed) + 1)
+        self.seed_generators(rpn_generator=seed, box_generator=int(seed) + 1)
         self.last_rpn_counts = []             # (num_pos, num_neg) per image of the last batch
         self.last_box_counts = []             # (num_fg, num_bg) per image of the last batch
         self.last_box_rows = []               # box rows per image of the last batch
         self.last_proposals = []              # the training proposals (boxes [count][4]) per image of the last batch
 
-    def state_dict(self):
-        sd = super().state_dict()
-        sd["rpn_generator"] = self.rpn_generator.get_state().clone()
-        sd["box_generator"] = self.box_generator.get_state().clone()
-        return sd
-
-    def load_state_dict(self, sd):
-        super().load_state_dict(sd)
-        self.rpn_generator.set_state(sd["rpn_generator"].cpu())
-        self.box_generator.set_state(sd["box_generator"].cpu())
-
-    def _sample(self, boxes, classes, d):
+    def _sample(self, boxes, polys, classes, d):
         model = self.model
-        keep = [i for i, a in enumerate(d["annotations"]) if not a.get("iscrowd", 0)]
-        gt = torch.from_numpy(np.asarray(boxes, np.float64)[keep].astype(np.float32)).reshape(-1, 4).to(model.device)
-        cls = torch.as_tensor(classes)[keep].to(model.device, torch.int32)
+        gt, cls = self.ground_truth(boxes, classes, d)
         sel, rlabels, rmatched, rcounts = label_and_sample_anchors(model, gt, self.rpn_batch_size_per_image, self.rpn_positive_fraction,
                                                                    self.rpn_generator, self.rpn_iou_thresholds)
         patches, slots, anchor_boxes, _ = model.rpn_patches(sel)
@@ -111,14 +93,6 @@ class JointTrainLoader(MaskTrainLoader):
         rpn = (patches, slots, rlabels, anchor_boxes, rmatched)
         box = (model.box_roi_features(sb), blabels, sb, bmatched)
         return rpn, box, rcounts, bcounts, props
-
-    def image_item(self, d, flipped=False):
-        boxes, _, classes = self.prepare_image(d, flipped)
-        return self._sample(boxes, classes, d)
-
-    def augmented_item(self, d, size, params):
-        boxes, _, classes = self.prepare_augmented(d, size, params)
-        return self._sample(boxes, classes, d)
 
     def __next__(self):
         items = self.next_items()

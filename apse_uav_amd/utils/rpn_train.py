@@ -7,8 +7,7 @@ import torch
 
 from ..networks import box_head as bh
 from ..networks import rpn_head as rh
-from .box_train import subsample_labels
-from .COCO_utils import MaskTrainLoader
+from .box_train import SamplingLoader, subsample_labels
 
 
 def label_and_sample_anchors(model, gt_boxes, batch_size_per_image=256, positive_fraction=0.5, generator=None,
@@ -28,7 +27,7 @@ def label_and_sample_anchors(model, gt_boxes, batch_size_per_image=256, positive
     return sel, lab01, matched, (int(pos.numel()), int(neg.numel()))
 
 
-class RpnTrainLoader(MaskTrainLoader):
+class RpnTrainLoader(SamplingLoader):
     """Yields (patches f32 [n][2304], slots int32 [n], labels int32 [n], anchor_boxes f32 [n][4], gt_boxes f32 [n][4]) per batch of
     ``ims_per_batch`` images, endlessly, in a seeded shuffled order.  ``model``: a TrackRCNN (FPN, f32) with the frozen detector's
     weights.  Per image: the image and annotation path of MaskTrainLoader (test size on the host, or the device path with
@@ -48,35 +47,16 @@ class RpnTrainLoader(MaskTrainLoader):
         if self.ims_per_batch * self.batch_size_per_image > rh.MAX_ROWS:
             raise ValueError("%d images x %d anchors exceed the %d rows of one step (APSE_BOX_TRAIN_MAX_N)"
                              % (self.ims_per_batch, self.batch_size_per_image, rh.MAX_ROWS))
-        self.generator = torch.Generator(device=model.device)
-        self.generator.manual_seed(int(seed))
+        self.seed_generators(generator=seed)
         self.last_counts = []                 # (num_pos, num_neg) per image of the last batch
 
-    def state_dict(self):
-        sd = super().state_dict()
-        sd["generator"] = self.generator.get_state().clone()
-        return sd
-
-    def load_state_dict(self, sd):
-        super().load_state_dict(sd)
-        self.generator.set_state(sd["generator"].cpu())
-
-    def _sample(self, boxes, d):
+    def _sample(self, boxes, polys, classes, d):
         model = self.model
-        keep = [i for i, a in enumerate(d["annotations"]) if not a.get("iscrowd", 0)]
-        gt = torch.from_numpy(np.asarray(boxes, np.float64)[keep].astype(np.float32)).reshape(-1, 4).to(model.device)
+        gt, _ = self.ground_truth(boxes, classes, d)
         sel, labels, matched, counts = label_and_sample_anchors(model, gt, self.batch_size_per_image, self.positive_fraction,
                                                                 self.generator, self.iou_thresholds)
         patches, slots, anchor_boxes, _ = model.rpn_patches(sel)
         return patches, slots, labels, anchor_boxes, matched, counts
-
-    def image_item(self, d, flipped=False):
-        boxes, _, _ = self.prepare_image(d, flipped)
-        return self._sample(boxes, d)
-
-    def augmented_item(self, d, size, params):
-        boxes, _, _ = self.prepare_augmented(d, size, params)
-        return self._sample(boxes, d)
 
     def __next__(self):
         items = self.next_items()

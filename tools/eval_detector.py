@@ -24,29 +24,9 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 
 
 def synthetic_dataset(root, n, seed=0, num_classes=4):
-    """n generated images (PNG) of three sizes with random box-polygon ground truth -> annotation file path."""
-    from PIL import Image
-    from apse_uav_amd.synthetic import SyntheticSequence
-    g = np.random.default_rng(seed)
-    sizes = [(270, 480), (240, 320), (300, 400)]
-    seqs = {s: SyntheticSequence("dynamic", *s) for s in sizes}
-    images, anns = [], []
-    os.makedirs(root, exist_ok=True)
-    for i in range(n):
-        h, w = sizes[int(g.integers(0, len(sizes)))]
-        name = "%06d.png" % i
-        Image.fromarray(seqs[(h, w)].frame(i)[:, :, ::-1].copy()).save(os.path.join(root, name))
-        images.append(dict(id=i + 1, file_name=name, height=h, width=w))
-        for _ in range(int(g.integers(1, 8))):
-            bw, bh = float(g.integers(8, w // 3)), float(g.integers(8, h // 3))
-            x, y = float(g.integers(0, w - int(bw))), float(g.integers(0, h - int(bh)))
-            anns.append(dict(id=len(anns) + 1, image_id=i + 1, category_id=int(g.integers(0, num_classes)), bbox=[x, y, bw, bh],
-                             area=bw * bh, iscrowd=int(g.random() < .02),
-                             segmentation=[[x, y, x + bw, y, x + bw, y + bh, x, y + bh]]))
-    path = os.path.join(root, "annotations.json")
-    with open(path, "w") as fh:
-        json.dump(dict(images=images, annotations=anns, categories=[dict(id=c, name="c%d" % c) for c in range(num_classes)]), fh)
-    return path
+    """apse_uav_amd.synthetic.synthetic_dataset (it lives in the package, where the fine-tune loop reaches it too)."""
+    from apse_uav_amd.synthetic import synthetic_dataset as impl
+    return impl(root, n, seed, num_classes)
 
 
 def main(argv=None):

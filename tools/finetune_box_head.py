@@ -23,205 +23,50 @@ import argparse
 import os
 import sys
 
-import numpy as np
-
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
-sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 
-RESULTS_FILE = "results.txt"
-HEADER = "\t\tAP\tAP_05\tAP0.75\tAP_s\tAP_m\tAP_l\tAR_1\tAR_10\tAR_100\tAR_s\tAR_m\tAR_l\n"
-MASK_PREDICTOR = "roi_heads.mask_head.predictor."
-
-
-def do_test(pred, dicts, coco_gt):
-    """bbox COCOeval stats (12 numbers) of the predictor's detections on ``dicts``; None when there is nothing to score."""
-    from PIL import Image
-    from apse_uav_amd.utils.coco_eval import CocoEvaluator
-    ev = CocoEvaluator(coco_gt)
-    total = 0
-    for d in dicts:
-        frame = np.asarray(Image.open(d["file_name"]).convert("RGB"))[:, :, ::-1].copy()
-        inst = pred(frame)[0]["instances"]
-        ev.add(d["image_id"], inst)
-        total += len(inst)
-    if total == 0:
-        return None
-    return [float(v) for v in ev.evaluate("bbox").stats]
+from apse_uav_amd.utils import finetune as ft                                   # noqa: E402
+from apse_uav_amd.utils.finetune import adapt_detector, holdout_split           # noqa: E402,F401
+from apse_uav_amd.utils.finetune import bbox_scores as do_test                  # noqa: E402
 
 
-def adapt_detector(detector, K):
-    """The frozen detector for K classes: when the checkpoint's class count differs, the per-class tensors outside the trained
-    layers (the mask predictor) are re-initialised as detectron2 leaves shape-mismatched keys (normal(std = 0.001), bias 0).
-    -> (state, True when the class count changed)."""
-    import torch
-    have = int(detector["roi_heads.box_predictor.cls_score.weight"].shape[0]) - 1
-    if have == K:
-        return detector, False
-    out = dict(detector)
-    if MASK_PREDICTOR + "weight" in out:
-        cin = int(out[MASK_PREDICTOR + "weight"].shape[1])
-        out[MASK_PREDICTOR + "weight"] = torch.nn.init.normal_(torch.zeros(K, cin, 1, 1), std=0.001)
-        out[MASK_PREDICTOR + "bias"] = torch.zeros(K)
-    return out, True
+class BoxTask(ft.Task):
+    what = "box-head"
+    num_classes = staticmethod(ft.trained_classes)
+    do_test = staticmethod(do_test)
+
+    def build_heads(self, args, cfg, detector, K):
+        from apse_uav_amd.networks.box_head import BoxHead
+        detector, changed = adapt_detector(detector, K)
+        head = BoxHead(K, "cuda")
+        head.load_state_dict(detector, keep_predictor=changed)          # another class count: fc1 / fc2 only, fresh predictors
+        self.heads = [head]
+        return detector
+
+    def merged_state(self, detector):
+        from apse_uav_amd.networks.box_head import merge_box_head
+        return merge_box_head(detector, self.heads[0].state_dict())
+
+    def make_loader(self, args, dicts, model, K, sizes):
+        from apse_uav_amd.utils.box_train import BoxTrainLoader
+        return BoxTrainLoader(dicts, model, args.ims_per_batch, args.seed, args.flip, augment=args.augment, num_classes=K,
+                              train_topk=tuple(int(v) for v in args.train_topk.split(",")) if args.train_topk else None, **sizes)
+
+    def losses(self, batch, loader, args):
+        return self.heads[0](*batch)
+
+    def counts(self, loader):
+        return "\tfg/bg: {}".format(loader.last_counts)
 
 
 def main(argv=None):
-    from finetune_segmentation import holdout_split
     ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
-    ap.add_argument("--images", default="")
-    ap.add_argument("--annotations", default="")
-    ap.add_argument("--weights", default="", help="detector (.pth / converted model-zoo file); its box branch is the start")
-    ap.add_argument("--classes", nargs="*", default=None, help="category names to train on (default: all)")
-    ap.add_argument("--out", required=True)
-    ap.add_argument("--name", default="R_50_FPN_UAV_BOX")
-    ap.add_argument("--iters", type=int, default=20000, help="MAX_ITER")
-    ap.add_argument("--checkpoint-period", type=int, default=10)
-    ap.add_argument("--ims-per-batch", type=int, default=2)
-    ap.add_argument("--lr", type=float, default=0.02)
-    ap.add_argument("--momentum", type=float, default=0.9)
-    ap.add_argument("--steps", type=int, nargs="*", default=[30000])
-    ap.add_argument("--gamma", type=float, default=0.1)
-    ap.add_argument("--warmup-iters", type=int, default=1000)
-    ap.add_argument("--warmup-factor", type=float, default=0.001)
-    ap.add_argument("--k-folds", type=int, default=1000)
-    ap.add_argument("--seed", type=int, default=0)
-    ap.add_argument("--flip", action="store_true", help="random horizontal flip")
-    ap.add_argument("--augment", action="store_true",
-                    help="the reference mapper's colour chain on the GPU: random brightness, saturation, contrast (0.9 .. 1.1 each) "
-                         "and lighting (0.2); the held-out images stay unaugmented")
-    ap.add_argument("--min-sizes", default="", metavar="S1,S2,...",
-                    help="multi-scale training: the short edge of every training image is drawn from these sizes "
-                         "(default: the test size)")
-    ap.add_argument("--max-size", type=int, default=0, help="cap of the long edge with --min-sizes / --augment (default: the test one)")
+    ft.add_common_arguments(ap, "R_50_FPN_UAV_BOX", "box branch")
     ap.add_argument("--train-topk", default="", metavar="PRE,POST",
                     help="train on the RPN's training-time selection, e.g. 2000,1000 as the reference's yaml (default: the "
                          "test-time selection)")
-    ap.add_argument("--stop-at", type=int, default=0, help="stop after this iteration's checkpoint (an interrupted run, for --resume)")
-    ap.add_argument("--resume", action="store_true")
-    ap.add_argument("--test-on-train", action="store_true", help="score the training images instead of the held-out ones")
-    ap.add_argument("--synthetic", type=int, default=0, metavar="N")
     args = ap.parse_args(argv)
-
-    import torch
-    from apse_uav_amd import optim
-    from apse_uav_amd.config import is_c4, setup_cfg
-    from apse_uav_amd.engines.track_predictor import TrackPredictor
-    from apse_uav_amd.networks.box_head import BoxHead, merge_box_head
-    from apse_uav_amd.utils import COCO_utils
-    from apse_uav_amd.utils.box_train import BoxTrainLoader
-    from apse_uav_amd.utils.coco import COCO
-    from apse_uav_amd.weights import load_detector_file, synthetic_detector_state
-
-    os.makedirs(args.out, exist_ok=True)
-    if args.synthetic:
-        from eval_detector import synthetic_dataset
-        args.images = os.path.join(args.out, "synthetic")
-        args.annotations = synthetic_dataset(args.images, args.synthetic)
-        detector = synthetic_detector_state(0, (1, 1, 1, 1), num_classes=4)
-    elif args.images and args.annotations and args.weights:
-        detector = load_detector_file(args.weights)
-    else:
-        ap.error("--images, --annotations and --weights are required (or --synthetic N)")
-
-    dicts = COCO_utils.generate_coco_dataset_dictionaries(args.annotations, args.images, args.classes, None, False)
-    have = int(detector["roi_heads.box_predictor.cls_score.weight"].shape[0]) - 1
-    K = len(args.classes) if args.classes else have
-    if max(a["category_id"] for d in dicts for a in d["annotations"]) >= K:
-        raise ValueError("the annotations map to more classes than the %d being trained" % K)
-    cfg = setup_cfg(num_classes=K)
-    cfg.APSE.MAX_BATCH = 1
-    cfg.APSE.DTYPE = "f32"
-    # the loop alternates between images of several sizes and every size has a context of its own: keep a few alive
-    cfg.APSE.CONTEXT_CACHE = max(int(cfg.APSE.get("CONTEXT_CACHE", 1)), 4)
-    if is_c4(cfg):
-        raise NotImplementedError("box-head training covers FPN models")
-    last_path = os.path.join(args.out, args.name + "_last.pth")
-    results_path = os.path.join(args.out, RESULTS_FILE)
-
-    torch.manual_seed(args.seed)
-    detector, changed = adapt_detector(detector, K)
-    head = BoxHead(K, "cuda")
-    head.load_state_dict(detector, keep_predictor=changed)          # another class count: fc1 / fc2 only, fresh predictors
-    params = list(head.parameters())
-    opt = optim.SGD(params, lr=args.lr, momentum=args.momentum)
-    sched = optim.WarmupMultiStepLR(opt, args.steps, args.gamma, args.warmup_factor, args.warmup_iters)
-    start_iter, best_p, best_r = 0, 0.0, 0.0
-    chk = None
-    if args.resume:
-        chk = torch.load(last_path, map_location="cpu", weights_only=False)
-        detector = {k: v for k, v in chk["model"].items()}           # the frozen part as the interrupted run had it
-        head.load_state_dict(chk["model"])
-        opt.load_state_dict(chk["optimizer"])
-        sched.load_state_dict(chk["scheduler"])
-        start_iter = int(chk["iteration"]) + 1
-        split, k_folds = chk["kfold_split"], chk["k_folds"]
-        best_p, best_r = chk["best_precision"], chk["best_recall"]
-        with open(results_path, "w") as fh:
-            fh.write(chk["training_results"])
-    else:
-        k_folds = args.k_folds
-        split = holdout_split(len(dicts), k_folds, args.seed)
-        with open(results_path, "w") as fh:
-            fh.write(HEADER)
-    train_ids, test_ids = split
-    train_dicts = [dicts[i] for i in train_ids]
-    test_dicts = train_dicts if args.test_on_train else [dicts[i] for i in test_ids]
-    gt = COCO.from_dataset(COCO_utils.detectron2_dataset_to_coco(test_dicts), verbose=False)
-
-    pred = TrackPredictor(cfg, state_dict=merge_box_head(detector, head.state_dict()))
-    min_sizes = tuple(int(v) for v in args.min_sizes.split(",")) if args.min_sizes else None
-    loader = BoxTrainLoader(train_dicts, pred.model, args.ims_per_batch, args.seed, args.flip, augment=args.augment,
-                            min_sizes=min_sizes, max_size=args.max_size or None, num_classes=K,
-                            train_topk=tuple(int(v) for v in args.train_topk.split(",")) if args.train_topk else None)
-    if chk is not None:
-        loader.load_state_dict(chk["loader"])
-
-    summary = {"losses": [], "tests": [], "num_classes": K}
-    summary["ap_before"] = do_test(pred, test_dicts, gt) if not args.resume else None
-    print("Training for {} iterations started".format(args.iters))
-    for iteration in range(start_iter, args.iters):
-        feats, labels, prop_boxes, gt_boxes = next(loader)
-        losses = head(feats, labels, prop_boxes, gt_boxes)
-        loss = losses["loss_cls"] + losses["loss_box_reg"]
-        opt.zero_grad()
-        loss.backward()
-        opt.step()
-        sched.step()
-        summary["losses"].append((float(losses["loss_cls"].detach()), float(losses["loss_box_reg"].detach())))
-        print("Iter. {}/{}:\tloss_cls: {}\tloss_box_reg: {}\tfg/bg: {}".format(iteration, args.iters, summary["losses"][-1][0],
-                                                                              summary["losses"][-1][1], loader.last_counts))
-        if iteration != 0 and iteration % args.checkpoint_period == 0:
-            head.push_into(pred)
-            res = do_test(pred, test_dicts, gt)
-            print("test results:", res)
-            if res is not None:
-                line = "{}/{}:\t".format(iteration, args.iters) + "\t".join("{:.3f}".format(v) for v in res)
-                if res[0] > best_p:
-                    best_p = res[0]
-                    line += " Best precision!"
-                if res[8] > best_r:
-                    best_r = res[8]
-                    line += " Best recall!"
-                with open(results_path, "a") as fh:
-                    fh.write(line + "\n")
-                summary["tests"].append((iteration, res))
-            with open(results_path) as fh:
-                chkpt = {"model": merge_box_head(detector, head.state_dict()), "optimizer": opt.state_dict(),
-                         "scheduler": sched.state_dict(), "iteration": iteration, "kfold_split": split, "k_folds": k_folds,
-                         "best_precision": best_p, "best_recall": best_r, "training_results": fh.read(),
-                         "loader": loader.state_dict()}
-            torch.save(chkpt, last_path)
-            if res is None or res[0] == best_p or not os.path.exists(os.path.join(args.out, args.name + "_bestAP.pth")):
-                torch.save(chkpt, os.path.join(args.out, args.name + "_bestAP.pth"))
-            if res is None or res[8] == best_r or not os.path.exists(os.path.join(args.out, args.name + "_bestAR.pth")):
-                torch.save(chkpt, os.path.join(args.out, args.name + "_bestAR.pth"))
-            if args.stop_at and iteration >= args.stop_at:
-                break
-    head.push_into(pred)
-    summary["ap_after"] = do_test(pred, test_dicts, gt)
-    summary["checkpoint"] = last_path
-    summary["state"] = {k: v.cpu() for k, v in head.state_dict().items()}
-    return summary
+    return ft.run(BoxTask(), args, ft.load_start(args, ap))
 
 
 if __name__ == "__main__":

@@ -21,19 +21,10 @@ import sys
 import numpy as np
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
-sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 
-RESULTS_FILE = "results.txt"
-HEADER = "\t\tAP\tAP_05\tAP0.75\tAP_s\tAP_m\tAP_l\tAR_1\tAR_10\tAR_100\tAR_s\tAR_m\tAR_l\n"
-
-
-def holdout_split(n, k_folds, seed):
-    """First fold of a seeded shuffle split into ``k_folds`` parts (the reference takes KFold(shuffle=True)'s first fold):
-    (train indices, test indices), both sorted."""
-    k = max(2, min(int(k_folds), n))
-    order = np.random.default_rng(seed).permutation(n)
-    n_test = max(1, n // k)
-    return sorted(int(i) for i in order[n_test:]), sorted(int(i) for i in order[:n_test])
+from apse_uav_amd.utils import finetune as ft                                   # noqa: E402
+from apse_uav_amd.networks.mask_head import PREFIX                              # noqa: E402
+from apse_uav_amd.utils.finetune import holdout_split                           # noqa: E402,F401
 
 
 def do_test(pred, dicts, coco_gt):
@@ -64,154 +55,55 @@ def do_test(pred, dicts, coco_gt):
     return [float(v) for v in ev.evaluate("segm").stats]
 
 
+class MaskTask(ft.Task):
+    what = "mask-head"
+    do_test = staticmethod(do_test)
+    precomputed_proposals = True        # the ground-truth boxes as proposals, as the reference's dictionaries have them
+    context_cache = None                # CONTEXT_CACHE is left to the loader (it raises it on the device path)
+    best_needs_score = True             # _bestAP / _bestAR only when the held-out images gave a score
+    resume_takes_detector = False       # --resume keeps the start detector as the frozen part
+    loader_state_optional = True        # checkpoints from before the loader's state was saved resume too
+
+    def num_classes(self, args, detector, dicts):
+        K = ft.detector_classes(detector)                               # the detector's classes (+ background)
+        if max(a["category_id"] for d in dicts for a in d["annotations"]) >= K:
+            raise ValueError("the annotations map to more classes than the detector's %d" % K)
+        return K
+
+    def build_heads(self, args, cfg, detector, K):
+        from apse_uav_amd.networks.mask_head import MaskHead
+        head = MaskHead(K, "cuda")
+        if any(k.startswith(PREFIX) for k in detector):
+            head.load_state_dict(detector)
+        self.heads = [head]
+        return detector
+
+    def merged_state(self, detector):
+        from apse_uav_amd.networks.mask_head import merge_full_mask_rcnn
+        return merge_full_mask_rcnn(detector, self.heads[0].state_dict())
+
+    def make_loader(self, args, dicts, model, K, sizes):
+        from apse_uav_amd.utils.COCO_utils import MaskTrainLoader
+        return MaskTrainLoader(dicts, model, args.ims_per_batch, args.seed, args.flip, args.cache_features, augment=args.augment,
+                               **sizes)
+
+    def losses(self, batch, loader, args):
+        return self.heads[0](*batch)
+
+    def report(self, losses, loader):
+        value = float(losses["loss_mask"])
+        return value, "loss: {}".format(value)
+
+
 def main(argv=None):
     ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
-    ap.add_argument("--images", default="")
-    ap.add_argument("--annotations", default="")
-    ap.add_argument("--weights", default="", help="box detector (.pth / converted model-zoo file); its mask head, if any, is the start")
-    ap.add_argument("--classes", nargs="*", default=None, help="category names to train on (default: all)")
-    ap.add_argument("--out", required=True)
-    ap.add_argument("--name", default="R_50_FPN_UAV_SEGM")
-    ap.add_argument("--iters", type=int, default=20000, help="MAX_ITER")
-    ap.add_argument("--checkpoint-period", type=int, default=10)
-    ap.add_argument("--ims-per-batch", type=int, default=2)
-    ap.add_argument("--lr", type=float, default=0.02)
-    ap.add_argument("--momentum", type=float, default=0.9)
-    ap.add_argument("--steps", type=int, nargs="*", default=[30000])
-    ap.add_argument("--gamma", type=float, default=0.1)
-    ap.add_argument("--warmup-iters", type=int, default=1000)
-    ap.add_argument("--warmup-factor", type=float, default=0.001)
-    ap.add_argument("--k-folds", type=int, default=1000)
-    ap.add_argument("--seed", type=int, default=0)
-    ap.add_argument("--flip", action="store_true", help="random horizontal flip")
-    ap.add_argument("--augment", action="store_true",
-                    help="the reference mapper's colour chain on the GPU: random brightness, saturation, contrast (0.9 .. 1.1 each) "
-                         "and lighting (0.2); the held-out images stay unaugmented")
-    ap.add_argument("--min-sizes", default="", metavar="S1,S2,...",
-                    help="multi-scale training: the short edge of every training image is drawn from these sizes, e.g. "
-                         "640,672,704,736,768,800 (default: the test size)")
-    ap.add_argument("--max-size", type=int, default=0, help="cap of the long edge with --min-sizes / --augment (default: the test one)")
+    ft.add_common_arguments(ap, "R_50_FPN_UAV_SEGM", "mask head, if any,")
     ap.add_argument("--cache-features", action="store_true")
-    ap.add_argument("--stop-at", type=int, default=0, help="stop after this iteration's checkpoint (an interrupted run, for --resume)")
-    ap.add_argument("--resume", action="store_true")
-    ap.add_argument("--test-on-train", action="store_true", help="score the training images instead of the held-out ones")
-    ap.add_argument("--synthetic", type=int, default=0, metavar="N")
     args = ap.parse_args(argv)
-
-    import torch
-    from apse_uav_amd import optim
-    from apse_uav_amd.config import is_c4, setup_cfg
-    from apse_uav_amd.engines.track_predictor import TrackPredictor
-    from apse_uav_amd.networks.mask_head import PREFIX, MaskHead, merge_full_mask_rcnn
-    from apse_uav_amd.utils import COCO_utils
-    from apse_uav_amd.utils.coco import COCO
-    from apse_uav_amd.weights import load_detector_file, synthetic_detector_state
-
-    os.makedirs(args.out, exist_ok=True)
+    detector = ft.load_start(args, ap)
     if args.synthetic:
-        from eval_detector import synthetic_dataset
-        args.images = os.path.join(args.out, "synthetic")
-        args.annotations = synthetic_dataset(args.images, args.synthetic)
-        detector = synthetic_detector_state(0, (1, 1, 1, 1), num_classes=4)
         detector = {k: v for k, v in detector.items() if not k.startswith(PREFIX)}          # a box detector: no mask head
-    elif args.images and args.annotations and args.weights:
-        detector = load_detector_file(args.weights)
-    else:
-        ap.error("--images, --annotations and --weights are required (or --synthetic N)")
-
-    dicts = COCO_utils.generate_coco_dataset_dictionaries(args.annotations, args.images, args.classes, None, True)
-    K = int(detector["roi_heads.box_predictor.cls_score.weight"].shape[0]) - 1        # the detector's classes (+ background)
-    if max(a["category_id"] for d in dicts for a in d["annotations"]) >= K:
-        raise ValueError("the annotations map to more classes than the detector's %d" % K)
-    cfg = setup_cfg(num_classes=K)
-    cfg.APSE.MAX_BATCH = 1
-    cfg.APSE.DTYPE = "f32"
-    if is_c4(cfg):
-        raise NotImplementedError("mask-head training covers FPN models")
-    last_path = os.path.join(args.out, args.name + "_last.pth")
-    results_path = os.path.join(args.out, RESULTS_FILE)
-
-    torch.manual_seed(args.seed)
-    head = MaskHead(K, "cuda")
-    if any(k.startswith(PREFIX) for k in detector):
-        head.load_state_dict(detector)
-    params = list(head.parameters())
-    opt = optim.SGD(params, lr=args.lr, momentum=args.momentum)
-    sched = optim.WarmupMultiStepLR(opt, args.steps, args.gamma, args.warmup_factor, args.warmup_iters)
-    start_iter, best_p, best_r = 0, 0.0, 0.0
-    chk = None
-    if args.resume:
-        chk = torch.load(last_path, map_location="cpu", weights_only=False)
-        head.load_state_dict(chk["model"])
-        opt.load_state_dict(chk["optimizer"])
-        sched.load_state_dict(chk["scheduler"])
-        start_iter = int(chk["iteration"]) + 1
-        split, k_folds = chk["kfold_split"], chk["k_folds"]
-        best_p, best_r = chk["best_precision"], chk["best_recall"]
-        with open(results_path, "w") as fh:
-            fh.write(chk["training_results"])
-    else:
-        k_folds = args.k_folds
-        split = holdout_split(len(dicts), k_folds, args.seed)
-        with open(results_path, "w") as fh:
-            fh.write(HEADER)
-    train_ids, test_ids = split
-    train_dicts = [dicts[i] for i in train_ids]
-    test_dicts = train_dicts if args.test_on_train else [dicts[i] for i in test_ids]
-    gt = COCO.from_dataset(COCO_utils.detectron2_dataset_to_coco(test_dicts), verbose=False)
-
-    full = merge_full_mask_rcnn(detector, head.state_dict())
-    pred = TrackPredictor(cfg, state_dict=full)
-    min_sizes = tuple(int(v) for v in args.min_sizes.split(",")) if args.min_sizes else None
-    loader = COCO_utils.MaskTrainLoader(train_dicts, pred.model, args.ims_per_batch, args.seed, args.flip, args.cache_features,
-                                        augment=args.augment, min_sizes=min_sizes, max_size=args.max_size or None)
-    if chk is not None and "loader" in chk:
-        loader.load_state_dict(chk["loader"])
-
-    summary = {"losses": [], "tests": [], "num_classes": K}
-    summary["ap_before"] = do_test(pred, test_dicts, gt) if not args.resume else None
-    print("Training for {} iterations started".format(args.iters))
-    for iteration in range(start_iter, args.iters):
-        feats, classes, targets = next(loader)
-        loss = head(feats, classes, targets)["loss_mask"]
-        opt.zero_grad()
-        loss.backward()
-        opt.step()
-        sched.step()
-        summary["losses"].append(float(loss))
-        print("Iter. {}/{}:\tloss: {}".format(iteration, args.iters, float(loss)))
-        if iteration != 0 and iteration % args.checkpoint_period == 0:
-            head.push_into(pred)
-            res = do_test(pred, test_dicts, gt)
-            print("test results:", res)
-            if res is not None:
-                line = "{}/{}:\t".format(iteration, args.iters) + "\t".join("{:.3f}".format(v) for v in res)
-                if res[0] > best_p:
-                    best_p = res[0]
-                    line += " Best precision!"
-                if res[8] > best_r:
-                    best_r = res[8]
-                    line += " Best recall!"
-                with open(results_path, "a") as fh:
-                    fh.write(line + "\n")
-                summary["tests"].append((iteration, res))
-            with open(results_path) as fh:
-                chkpt = {"model": merge_full_mask_rcnn(detector, head.state_dict()), "optimizer": opt.state_dict(),
-                         "scheduler": sched.state_dict(), "iteration": iteration, "kfold_split": split, "k_folds": k_folds,
-                         "best_precision": best_p, "best_recall": best_r, "training_results": fh.read(),
-                         "loader": loader.state_dict()}
-            torch.save(chkpt, last_path)
-            if res is not None and res[0] == best_p:
-                torch.save(chkpt, os.path.join(args.out, args.name + "_bestAP.pth"))
-            if res is not None and res[8] == best_r:
-                torch.save(chkpt, os.path.join(args.out, args.name + "_bestAR.pth"))
-            if args.stop_at and iteration >= args.stop_at:
-                break
-    head.push_into(pred)
-    summary["ap_after"] = do_test(pred, test_dicts, gt)
-    summary["checkpoint"] = last_path
-    summary["state"] = {k: v.cpu() for k, v in head.state_dict().items()}
-    return summary
+    return ft.run(MaskTask(), args, detector)
 
 
 if __name__ == "__main__":
