@@ -42,6 +42,50 @@ def roi_kernels():
     return lib
 
 
+# the 16-bit trunk front and the small kernels beside it (csrc/elementwise.hip, stem_pool16.hip, bottleneck16.hip), as
+# apse_kernels.h declares them; the fused kernels end with (stream, event before, event after) -- the events may be null
+TRUNK_KERNEL_SIG = {
+    "apse_k_round16": ([_vp, _vp, C.c_size_t, _i, _vp], _i),
+    "apse_k_subsample2": ([_vp, _vp, _i, _i, _i, _i, _i, _vp], _i),
+    "apse_k_nhwc_to_nchw": ([_vp, _vp, _i, _i, _i, _i, _vp], _i),
+    "apse_k_stem_pool16": ([_vp, _vp, _vp, _vp, _i, _i, _i, _i, _vp, _vp, _vp], _i),
+    "apse_k_bottleneck64_fused16": ([_vp] * 9 + [_i] * 5 + [_vp] * 3, _i),
+}
+
+
+def trunk_kernels():
+    """The loaded library with the trunk-front launchers' argument types set."""
+    lib = _lib.load()
+    for name, (args, ret) in TRUNK_KERNEL_SIG.items():
+        fn = getattr(lib, name)
+        fn.argtypes = args
+        fn.restype = ret
+    return lib
+
+
+def pack_filter(w_oihw, scale=None):
+    """OIHW filter (CPU tensor) -> (apse_conv_pack_weight's layout [Cout_p128][KH][roundup(KW * cin_p, 32)] as a numpy f32 array,
+    cin_p = the input channels padded to a power of two >= 4)."""
+    lib = _lib.load()
+    Cout, Cin, KH, KW = w_oihw.shape
+    cin_p = 4
+    while cin_p < Cin:
+        cin_p *= 2
+    d = _lib.ConvDesc()
+    d.Cin, d.Cout, d.KH, d.KW = cin_p, Cout, KH, KW
+    packed = np.zeros(lib.apse_conv_packed_elems(C.byref(d)), np.float32)
+    w = np.ascontiguousarray(w_oihw.numpy(), np.float32)
+    sc = None if scale is None else np.ascontiguousarray(scale.numpy(), np.float32)
+    _lib.check(lib.apse_conv_pack_weight(C.byref(d), _lib.ptr(w), Cin, _lib.ptr(sc) if sc is not None else None,
+                                         _lib.ptr(packed)), None, "pack")
+    return packed, cin_p
+
+
+def pack_filter16(w_oihw, dtype):
+    """``pack_filter`` rounded with torch to ``dtype``, on cuda:0 (the filters of the 16-bit kernels)"""
+    return torch.from_numpy(pack_filter(w_oihw)[0]).to(dtype).cuda().contiguous()
+
+
 def fpn_maps(tensors, dims, st, scales=(0.25, 0.125, 0.0625, 0.03125)):
     F = FpnMaps()
     for k in range(4):
@@ -66,20 +110,13 @@ def hip_conv2d(x_nchw, w_oihw, bias=None, stride=1, pad=0, relu=False, residual=
     dev = torch.device("cuda:0")
     B, Cin, H, W = x_nchw.shape
     Cout, _, KH, KW = w_oihw.shape
-    cin_p = 4
-    while cin_p < Cin:
-        cin_p *= 2
+    packed, cin_p = pack_filter(w_oihw, scale)
     d = _lib.ConvDesc()
     d.B, d.H, d.W, d.Cin = B, H, W, cin_p
     d.Cout, d.KH, d.KW, d.stride, d.pad = Cout, KH, KW, stride, pad
     d.relu, d.res_mode, d.cfg, d.splitk, d.prec, d.fuse_reduce = int(relu), res_mode, cfg, splitk, prec, fuse
     d.x_st, d.res_st, d.y_st = x_st, res_st, y_st
     tdt = {0: torch.float32, 1: torch.bfloat16, 2: torch.float16}
-    packed = np.zeros(lib.apse_conv_packed_elems(C.byref(d)), np.float32)
-    w = np.ascontiguousarray(w_oihw.numpy(), np.float32)
-    sc = None if scale is None else np.ascontiguousarray(scale.numpy(), np.float32)
-    _lib.check(lib.apse_conv_pack_weight(C.byref(d), _lib.ptr(w), Cin, _lib.ptr(sc) if sc is not None else None,
-                                         _lib.ptr(packed)), None, "pack")
     bias_p = torch.zeros(((Cout + 127) // 128) * 128)
     if bias is not None:
         bias_p[:Cout] = bias
