@@ -20,7 +20,7 @@ LIB_PATH = os.environ.get("APSE_HIP_LIB") or _TREE_LIB
 # APSE_HIP_LIB (load())
 TOOL_ENTRIES = ("apse_winograd_pack_filter", "apse_winograd_conv2d", "apse_lane_stats", "apse_rpn_select", "apse_box_inference",
                 "apse_c4_rpn_select", "apse_rpn_select_train", "apse_rpn_train_proposals_workspace_bytes", "apse_rpn_train_proposals",
-                "apse_set_rpn_head")
+                "apse_set_rpn_head", "apse_preprocess_frames_yuv", "apse_yuv_to_bgr", "apse_yuv_matrix_host", "apse_resize_normalize_yuv")
 
 APSE_OK = 0
 
@@ -207,6 +207,10 @@ SIGNATURES = {
     "apse_rpn_train_proposals_workspace_bytes": ([i, i], sz),
     "apse_rpn_train_proposals": ([vp, i, i, i, vp, vp, vp, vp, sz, vp], i),
     "apse_set_rpn_head": ([vp, vp, vp, vp, vp, vp, vp, vp], i),
+    "apse_preprocess_frames_yuv": ([vp, vp, i, i, i, i, vp], i),
+    "apse_yuv_to_bgr": ([vp, vp, i, i, i, i, i, i, vp], i),
+    "apse_yuv_matrix_host": ([i, C.POINTER(C.c_int * 6)], i),
+    "apse_resize_normalize_yuv": ([vp, i, i, i, vp, vp, vp, vp, vp, i, vp, vp, i, i, i, i, i, i, i, i, C.POINTER(f * 3), vp], i),
 }
 del vp, i, f, sz
 EXPORTS = list(SIGNATURES)

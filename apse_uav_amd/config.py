@@ -139,7 +139,10 @@ def get_cfg():
         # CONTEXT_CACHE: live contexts TrackRCNN keeps, one per (frame size, image size); 1 = rebuild at every size change
         # TAIL_LANE: a forward's selection / heads / results copy on the context's second stream, beside the next frame's trunk
         # (apse_config.tail_lane; the environment variable APSE_TAIL_LANE=0 switches it off for every context)
-        "APSE": {"DTYPE": "f32", "MAX_BATCH": 1, "FUSED_PREPROC": True, "STORAGE16": True, "CONTEXT_CACHE": 1, "TAIL_LANE": True},
+        # YUV_MATRIX: the conversion of INPUT.FORMAT "NV12" / "I420" frames (structures/yuv_frame.py): cv601 (OpenCV's
+        # COLOR_YUV2BGR_NV12 constants), bt601, bt709, bt601-full, bt709-full
+        "APSE": {"DTYPE": "f32", "MAX_BATCH": 1, "FUSED_PREPROC": True, "STORAGE16": True, "CONTEXT_CACHE": 1, "TAIL_LANE": True,
+                 "YUV_MATRIX": "cv601"},
     })
 
 

@@ -7,6 +7,7 @@
 
 struct UndistortParams;   // preproc_pixel.h
 struct LabTables;
+struct YuvSource;
 
 // Slot length of the NMS keep lists (keep_idx [B][ncat][APSE_NMS_SLOT]): boxes per category, <= 1000 by construction
 #define APSE_NMS_SLOT 1024
@@ -97,7 +98,7 @@ int apse_k_round16(const float* x, uint16_t* y, size_t n, int dtype, hipStream_t
 int apse_k_pil_resize(const uint8_t* src, uint8_t* tmp, void* out, int out_st, uint8_t* resized_u8, const int* hb, const int* hc,
                       int hk, const int* vb, const int* vc, int vk, int B, int H, int W, int OH, int OW, int PH, int PW,
                       const float* mean, const UndistortParams* cam, const LabTables* lut, const void* cam_map, const int* hcT, int tmp_pitch,
-                      hipStream_t s);
+                      const YuvSource* yuv, hipStream_t s);
 int apse_k_chw_norm(const float* img, void* out, int out_st, int B, int OH, int OW, int PH, int PW, const float* mean, hipStream_t s);
 int apse_k_maxpool3x3s2(const void* x, void* y, int B, int H, int W, int C, int st, hipStream_t s);
 int apse_k_subsample2(const void* x, void* y, int B, int H, int W, int C, int st, hipStream_t s);
@@ -105,6 +106,7 @@ int apse_k_nhwc_to_nchw(const void* x, float* y, int B, int HW, int C, int st, h
 // ---- preproc.hip
 int apse_k_undistort_build_map_compact(const UndistortParams* p, void* map, int* overflow_dev, hipStream_t s);
 int apse_k_undistort_gamma(const UndistortParams* p, const uint8_t* src, uint8_t* dst, const LabTables* lab, int B, hipStream_t s);
+int apse_k_yuv_to_bgr(const YuvSource* p, const uint8_t* src, uint8_t* dst, int B, hipStream_t s);
 // ---- stem_pool16.hip, bottleneck16.hip
 int apse_k_stem_pool16(const void* x, const uint16_t* w16, const float* bias, void* y, int B, int IH, int IW, int prec,
                        hipStream_t s, hipEvent_t ev0, hipEvent_t ev1);

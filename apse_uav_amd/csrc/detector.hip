@@ -383,8 +383,34 @@ int apse_preprocess_frames(apse_ctx* c, const uint8_t* frames, int batch, void* 
     const apse_config& g = c->cfg;
     int rc = apse_k_pil_resize(frames, c->rs_tmp, c->t["input"].p, c->t["input"].st, nullptr, c->hb, c->hc, c->hk, c->vb, c->vc, c->vk, batch,
                                g.frame_h, g.frame_w, g.image_h, g.image_w, c->PH, c->PW, g.pixel_mean, c->cam_on ? &c->cam : nullptr, c->cam_lut, c->cam_map_ok ? c->cam_map : nullptr,
-                               c->hcT, c->rs_pitch, (hipStream_t)stream);
+                               c->hcT, c->rs_pitch, nullptr, (hipStream_t)stream);
     return rc ? fail(c, rc, "pil resize launch failed") : APSE_OK;
+}
+
+int apse_preprocess_frames_yuv(apse_ctx* c, const uint8_t* frames, int batch, int pitch, int format, int matrix, void* stream) {
+    NEED_READY(c, batch);
+    if (!c->hb) return fail(c, APSE_E_STATE, "resize tables not set");
+    if (!frames) return fail(c, APSE_E_INVALID, "null frames");
+    const apse_config& g = c->cfg;
+    YuvSource y;
+    const char* why = yuv_source_fill(y, g.frame_h, g.frame_w, pitch, format, matrix);
+    if (why) return fail(c, APSE_E_INVALID, why);
+    if (c->cam_on) {
+        // convert, then preprocess_img: the converter writes BGR frames the fused undistort + gamma pass then gathers from (a YUV
+        // form of the 2x2 gather would save 25 MB of the ~37 MB this moves per 4K frame, on a path one launch long)
+        if (!c->yuv_bgr) {
+            hipSetDevice(g.device);
+            c->yuv_bgr = dalloc<uint8_t>(c, (size_t)g.max_batch * g.frame_h * g.frame_w * 3 + 16, false);
+            if (!c->yuv_bgr) return fail(c, APSE_E_NOMEM, "YUV -> BGR scratch frames alloc");
+        }
+        int rc = apse_k_yuv_to_bgr(&y, frames, c->yuv_bgr, batch, (hipStream_t)stream);
+        if (rc) return fail(c, rc, "yuv_to_bgr launch failed");
+        return apse_preprocess_frames(c, c->yuv_bgr, batch, stream);
+    }
+    int rc = apse_k_pil_resize(frames, c->rs_tmp, c->t["input"].p, c->t["input"].st, nullptr, c->hb, c->hc, c->hk, c->vb, c->vc, c->vk, batch,
+                               g.frame_h, g.frame_w, g.image_h, g.image_w, c->PH, c->PW, g.pixel_mean, nullptr, nullptr, nullptr,
+                               c->hcT, c->rs_pitch, &y, (hipStream_t)stream);
+    return rc ? fail(c, rc, "pil resize (YUV) launch failed: batch of 2 GiB or more?") : APSE_OK;
 }
 
 int apse_preprocess_images(apse_ctx* c, const float* images, int batch, void* stream) {

@@ -72,6 +72,7 @@ struct apse_ctx {
     int* mrf_idx = nullptr; size_t mrf_cap = 0;               // apse_mask_roi_features: image index per RoI + live count (grown on demand)
     bool box_maxc_clean = false;
     UndistortParams cam; bool cam_on = false; LabTables* cam_lut = nullptr; void* cam_map = nullptr; bool cam_map_ok = false;     // apse_set_camera: fused undistort + gamma in apse_preprocess_frames
+    uint8_t* yuv_bgr = nullptr;      // apse_preprocess_frames_yuv with a camera set: the converted BGR frames [max_batch][frame_h][frame_w][3] (first use)
     int hint_total = 8;      // detections seen in the previous forward: sizes the GRID of the packed-list GEMMs, nothing else
     hipEvent_t read_ev = nullptr; void* read_pending = nullptr;      // apse_read_results_begin / _end
     // apse_set_detections: two pinned staging blocks, each guarded by the event behind its H2D copies, so the call only enqueues

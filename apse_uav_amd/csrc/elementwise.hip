@@ -143,12 +143,58 @@ __device__ __forceinline__ uint8_t* pil_stage_row(uint8_t* row, const uint8_t* _
     return row;
 }
 
-// Any filter length: each thread produces output samples (ox, c) one after the other.
+// YUV 4:2:0 source (NV12 with a pitch / packed I420, preproc_pixel.h): the row is COMPUTED while staging, like the camera form --
+// the block of source row y reads luma row y and chroma row y >> 1 and writes the row's W * 3 BGR bytes into the LDS row it owns,
+// so the consumers behind it see the bytes of the BGR path on the converted frame, and a converted frame (25 MB at 4K, twice
+// the 12 MB that come in) is never written.  A thread converts four pixels at a time: four luma bytes, the two chroma samples
+// under them, three LDS dwords out.  Rows start at any byte (an odd pitch, an offset pointer), so every fetch goes through
+// pp_load4 on a descriptor based at the dword that holds the batch's first byte, whose range ends at the dword that holds its
+// last byte (src_bytes, from the launcher: both dwords lie inside pages of the allocation): nothing outside is fetched, the
+// luma bytes past the row end that the last thread's dword picks up are not used, and its pixels leave byte by byte.
 template <bool FUSED>
+__device__ __forceinline__ uint8_t* pil_stage_row(uint8_t* row, const uint8_t* __restrict__ src, int y, int b, int W, size_t src_img_stride,
+                                                  const YuvSource& yuv, const LabTables* __restrict__, const uint32_t* __restrict__,
+                                                  unsigned src_bytes) {
+    static_assert(FUSED, "a YUV row is computed while staging: the FUSED forms of the kernels (no row slack, grid (H, B))");
+    const int m0 = (int)(reinterpret_cast<uintptr_t>(src) & 3);
+    const __amdgpu_buffer_rsrc_t rs = __builtin_amdgcn_make_buffer_rsrc(const_cast<uint8_t*>(src) - m0, 0, (int)src_bytes, 0x00020000);
+    const int fo = m0 + (int)((size_t)b * src_img_stride);
+    const int CH = (yuv.H + 1) >> 1, CW = (W + 1) >> 1, cy = y >> 1;
+    const bool nv12 = yuv.format == 0;
+    const int lo = fo + y * (nv12 ? yuv.pitch : W);
+    const int uo = nv12 ? fo + (yuv.H + cy) * yuv.pitch : fo + yuv.H * W + cy * CW, vo = uo + CH * CW;
+    uint32_t* r4 = reinterpret_cast<uint32_t*>(row);
+    for (int x0 = threadIdx.x * 4; x0 < W; x0 += 4 * blockDim.x) {
+        const uint32_t y4 = pp_load4(rs, lo + x0);
+        int U0, V0, U1, V1;
+        if (nv12) {
+            const uint32_t c = pp_load4(rs, uo + x0);
+            U0 = c & 0xffu; V0 = (c >> 8) & 0xffu; U1 = (c >> 16) & 0xffu; V1 = c >> 24;
+        } else {
+            const uint32_t u = pp_load4(rs, uo + (x0 >> 1)), v = pp_load4(rs, vo + (x0 >> 1));
+            U0 = u & 0xffu; U1 = (u >> 8) & 0xffu; V0 = v & 0xffu; V1 = (v >> 8) & 0xffu;
+        }
+        uint32_t o3[3];
+        yuv_quad_bgr(yuv.m, y4, U0, V0, U1, V1, o3);
+        if (x0 + 4 <= W) {
+            r4[(x0 >> 2) * 3 + 0] = o3[0]; r4[(x0 >> 2) * 3 + 1] = o3[1]; r4[(x0 >> 2) * 3 + 2] = o3[2];
+        } else {
+#pragma unroll
+            for (int k = 0; k < 9; ++k)
+                if (k < (W - x0) * 3) row[x0 * 3 + k] = (uint8_t)(o3[k >> 2] >> (8 * (k & 3)));
+        }
+    }
+    return row;
+}
+
+// Any filter length: each thread produces output samples (ox, c) one after the other.
+// CAM: what the FUSED staging computes the row from -- the camera (UndistortParams) or a YUV source (YuvSource); the argument has
+// the type's own size, so the BGR instantiations keep their kernel arguments and their code.
+template <bool FUSED, typename CAM = UndistortParams>
 __global__ __launch_bounds__(256) void pil_resize_h(const uint8_t* __restrict__ src, uint8_t* __restrict__ tmp,
                                                     const int* __restrict__ bounds, const int* __restrict__ coef,
                                                     int H, int W, int OW, int ksize, size_t src_img_stride,
-                                                    size_t tmp_img_stride, const UndistortParams cam, const LabTables* __restrict__ lut,
+                                                    size_t tmp_img_stride, const CAM cam, const LabTables* __restrict__ lut,
                                                     const uint32_t* __restrict__ cam_map, int tp, unsigned src_bytes) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
     const int y = blockIdx.x, b = blockIdx.y;
@@ -171,11 +217,11 @@ __global__ __launch_bounds__(256) void pil_resize_h(const uint8_t* __restrict__ 
 // slots of TWO pixels are requested together (their addresses depend on ox only; slots past the pixel's count read as 0),
 // so a block makes ~3 round trips instead of ~32.  The output row is collected in LDS and leaves in 16-byte stores.
 // Same integer arithmetic in the same order: bit-identical output.
-template <bool FUSED>
+template <bool FUSED, typename CAM = UndistortParams>
 __global__ __launch_bounds__(256) void pil_resize_h8(const uint8_t* __restrict__ src, uint8_t* __restrict__ tmp,
                                                      const int2* __restrict__ bounds, const int* __restrict__ coef,
                                                      int H, int W, int OW, int ksize, size_t src_img_stride,
-                                                     size_t tmp_img_stride, const UndistortParams cam, const LabTables* __restrict__ lut,
+                                                     size_t tmp_img_stride, const CAM cam, const LabTables* __restrict__ lut,
                                                      const uint32_t* __restrict__ cam_map, const int* __restrict__ coefT, int tp,
                                                      unsigned src_bytes, int nb) {
     // coefT (optional): the taps tap-major, [8][OW], zero past a pixel's count.  A wave's load of tap j is then 256 consecutive
@@ -486,7 +532,8 @@ int apse_k_round16(const float* x, uint16_t* y, size_t n, int dtype, hipStream_t
 int apse_k_pil_resize(const uint8_t* src, uint8_t* tmp, void* out, int out_st, uint8_t* resized_u8, const int* hb, const int* hc,
                       int hk, const int* vb, const int* vc, int vk, int B, int H, int W, int OH, int OW, int PH, int PW,
                       const float* mean, const UndistortParams* cam, const LabTables* lut, const void* cam_map, const int* hcT, int tmp_pitch,
-                      hipStream_t s) {
+                      const YuvSource* yuv, hipStream_t s) {
+    // yuv (optional): src is a batch of NV12 / I420 frames of that geometry instead of BGR; not together with a camera
     // tmp_pitch: row pitch of tmp in bytes (0: OW * 3); a multiple of 4 selects the dword vertical pass
     const int tp = tmp_pitch > 0 ? tmp_pitch : OW * 3;
     if (tp < OW * 3) return APSE_E_INVALID;
@@ -499,7 +546,8 @@ int apse_k_pil_resize(const uint8_t* src, uint8_t* tmp, void* out, int out_st, u
     // LDS: the staged row (W*3 bytes, + PIL_ROW_SLACK when its rows are not dword-aligned), the fused form's Lab tables (static),
     // and in the batched form 32 zero tap slots and the output row.  The widest frame fits every form but the batched one with
     // a wide output row: that one falls back to the per-sample form.
-    const size_t slack = !fused && pil_row_unaligned(src, W) ? PIL_ROW_SLACK : 0;
+    if (yuv && (fused || yuv->H != H || yuv->W != W)) return APSE_E_INVALID;
+    const size_t slack = !fused && !yuv && pil_row_unaligned(src, W) ? PIL_ROW_SLACK : 0;
     const size_t lds1 = (size_t)W * 3 + (slack ? 32 : 0), lds_static = fused ? sizeof(LabTables) : 0;
     const size_t lds8 = (((size_t)W * 3 + 32 + slack + 15) & ~(size_t)15) + (size_t)OW * 3 + 32;
     static_assert(((size_t)APSE_MAX_FRAME_W * 3 + 32 + PIL_ROW_SLACK + 15) / 16 * 16 + sizeof(LabTables) + 16 <= APSE_LDS_BYTES,
@@ -514,7 +562,19 @@ int apse_k_pil_resize(const uint8_t* src, uint8_t* tmp, void* out, int out_st, u
     const size_t src_total = (size_t)B * H * W * 3;
     const uint32_t* map2 = src_total < 0x7ffffff0ull ? reinterpret_cast<const uint32_t*>(cam_map) : nullptr;
     const unsigned sb = (unsigned)(src_total < 0x7ffffff0ull ? (src_total + 3) & ~(size_t)3 : 0);
-    if (h8 && fused)
+    if (yuv) {
+        // 32-bit byte offsets into the batch, counted from the dword that holds its first byte; the range ends with the dword
+        // that holds its last byte
+        const size_t fb = yuv_frame_bytes(*yuv), span = (reinterpret_cast<uintptr_t>(src) & 3) + (size_t)B * fb;
+        if (span >= 0x7ffffff0ull) return APSE_E_INVALID;
+        const unsigned yb = (unsigned)((span + 3) & ~(size_t)3);
+        if (h8)
+            hipLaunchKernelGGL((pil_resize_h8<true, YuvSource>), dim3(H, B), dim3(256), lds8, s, src, tmp, hb2, hc, H, W, OW, hk, fb, (size_t)H * tp,
+                               *yuv, (const LabTables*)nullptr, (const uint32_t*)nullptr, hcT, tp, yb, 0);
+        else
+            hipLaunchKernelGGL((pil_resize_h<true, YuvSource>), dim3(H, B), dim3(256), lds1, s, src, tmp, hb, hc, H, W, OW, hk, fb, (size_t)H * tp,
+                               *yuv, (const LabTables*)nullptr, (const uint32_t*)nullptr, tp, yb);
+    } else if (h8 && fused)
         hipLaunchKernelGGL(pil_resize_h8<true>, dim3(((H + 7) / 8) * 8 * B), dim3(256), lds8, s, src, tmp, hb2, hc, H, W, OW, hk, (size_t)H * W * 3,
                            (size_t)H * tp, *cam, lut, map2, hcT, tp, sb, B);
     else if (h8)

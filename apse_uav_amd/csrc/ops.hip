@@ -452,7 +452,38 @@ size_t apse_lab_tables_host(const uint8_t* lut256, void* out, size_t cap) {
 int apse_resize_normalize(const uint8_t* frames, uint8_t* tmp, float* out, uint8_t* resized, const int* hb, const int* hc, int hk,
                           const int* vb, const int* vc, int vk, int B, int H, int W, int OH, int OW, int PH, int PW,
                           const float* mean3, void* stream) {
-    return apse_k_pil_resize(frames, tmp, out, 0, resized, hb, hc, hk, vb, vc, vk, B, H, W, OH, OW, PH, PW, mean3, nullptr, nullptr, nullptr, nullptr, 0, (hipStream_t)stream);
+    return apse_k_pil_resize(frames, tmp, out, 0, resized, hb, hc, hk, vb, vc, vk, B, H, W, OH, OW, PH, PW, mean3, nullptr, nullptr, nullptr, nullptr, 0, nullptr, (hipStream_t)stream);
+}
+
+// The geometry checks of every YUV entry: the frame-size limits, then the layout (yuv_source_fill)
+static int yuv_source_checked(YuvSource& y, int H, int W, int pitch, int format, int matrix) {
+    if (H < 1 || W < 1 || H > APSE_MAX_FRAME_H || W > APSE_MAX_FRAME_W) return apse_fail_global(APSE_E_INVALID, "YUV frame size outside 1..APSE_MAX_FRAME_H x 1..APSE_MAX_FRAME_W");
+    const char* why = yuv_source_fill(y, H, W, pitch, format, matrix);
+    return why ? apse_fail_global(APSE_E_INVALID, why) : APSE_OK;
+}
+
+int apse_yuv_to_bgr(const uint8_t* src, uint8_t* dst, int B, int H, int W, int pitch, int format, int matrix, void* stream) {
+    if (!src || !dst || B < 1) return apse_fail_global(APSE_E_INVALID, "apse_yuv_to_bgr: null pointer or empty batch");
+    YuvSource y;
+    int rc = yuv_source_checked(y, H, W, pitch, format, matrix);
+    if (rc) return rc;
+    return apse_k_yuv_to_bgr(&y, src, dst, B, (hipStream_t)stream);
+}
+
+int apse_yuv_matrix_host(int matrix, int* out6) {
+    if (matrix < 0 || matrix >= YUV_NMATRIX || !out6) return APSE_E_INVALID;
+    const YuvMatrix& m = YUV_MATRICES[matrix];
+    out6[0] = m.yoff; out6[1] = m.cy; out6[2] = m.cvr; out6[3] = m.cvg; out6[4] = m.cug; out6[5] = m.cub;
+    return APSE_OK;
+}
+
+int apse_resize_normalize_yuv(const uint8_t* frames, int pitch, int format, int matrix, uint8_t* tmp, float* out, uint8_t* resized,
+                              const int* hb, const int* hc, int hk, const int* vb, const int* vc, int vk, int B, int H, int W, int OH,
+                              int OW, int PH, int PW, const float* mean3, void* stream) {
+    YuvSource y;
+    int rc = yuv_source_checked(y, H, W, pitch, format, matrix);
+    if (rc) return rc;
+    return apse_k_pil_resize(frames, tmp, out, 0, resized, hb, hc, hk, vb, vc, vk, B, H, W, OH, OW, PH, PW, mean3, nullptr, nullptr, nullptr, nullptr, 0, &y, (hipStream_t)stream);
 }
 
 }  // extern "C"

@@ -75,6 +75,48 @@ struct UndistortParams {
     int do_undistort, do_gamma;
 };
 
+// ---- YUV 4:2:0 frames (NV12 with a row pitch, packed I420) -> BGR.  One definition for the stand-alone operator (preproc.hip)
+// and the row staging of the horizontal resize pass (elementwise.hip); tests/yuv_ref.py restates it in numpy (int32, >>, clip).
+// Chroma is sited nearest: pixel (x, y) takes the sample (x >> 1, y >> 1), as OpenCV's COLOR_YUV2BGR_NV12 does.  With
+// u = U - 128, v = V - 128, yy = max(0, Y - yoff) * cy:
+//   R = sat8((yy + cvr v + 2^19) >> 20), G = sat8((yy + cvg v + cug u + 2^19) >> 20), B = sat8((yy + cub u + 2^19) >> 20)
+// (>> floors).  |yy| <= 2.92e8, |cvg v + cug u| <= 1.62e8, |cub u| <= 2.84e8: every sum fits int32.
+struct YuvMatrix { int yoff, cy, cvr, cvg, cug, cub; };
+#define YUV_NMATRIX 5
+// cv601: OpenCV's ITUR_BT_601_* constants.  The others: rint(2^20 x) of the exact expressions in Kr, Kb (0.299 / 0.114 for
+// BT.601, 0.2126 / 0.0722 for BT.709) with the 255 / 219 and 255 / 224 range scales (limited) or none (full range);
+// tests/test_yuv_host.py recomputes them.
+static const YuvMatrix YUV_MATRICES[YUV_NMATRIX] = {
+    {16, 1220542, 1673527, -852492, -409993, 2116026},     // APSE_YUV_CV601
+    {16, 1220945, 1673555, -852458, -410793, 2115221},     // APSE_YUV_BT601
+    {16, 1220945, 1879825, -558796, -223607, 2215014},     // APSE_YUV_BT709
+    {0, 1048576, 1470104, -748826, -360853, 1858077},      // APSE_YUV_BT601_FULL
+    {0, 1048576, 1651297, -490864, -196424, 1945738},      // APSE_YUV_BT709_FULL
+};
+// A batch of frames of one geometry as the kernels read it.  format 0 (NV12): H luma rows of `pitch` bytes, then CH = (H + 1) / 2
+// rows of `pitch` bytes holding CW = (W + 1) / 2 interleaved (U, V) pairs; any pitch >= max(W, 2 CW).  format 1 (I420): packed
+// H x W luma, CH x CW U, CH x CW V; W and H even, pitch == W.
+struct YuvSource {
+    YuvMatrix m;
+    int H, W, pitch, format;
+};
+static inline size_t yuv_frame_bytes(const YuvSource& s) {
+    const size_t CH = (size_t)(s.H + 1) / 2, CW = (size_t)(s.W + 1) / 2;
+    return s.format == 0 ? ((size_t)s.H + CH) * (size_t)s.pitch : (size_t)s.H * s.W + 2 * CH * CW;
+}
+// nullptr when the geometry is valid, else what is wrong with it (the frame-size limits are the caller's)
+static inline const char* yuv_source_fill(YuvSource& s, int H, int W, int pitch, int format, int matrix) {
+    if (matrix < 0 || matrix >= YUV_NMATRIX) return "unknown YUV matrix";
+    if (format != 0 && format != 1) return "unknown YUV format (0 NV12, 1 I420)";
+    if (H < 1 || W < 1) return "empty frame";
+    if (format == 0 && (pitch < W || pitch < 2 * ((W + 1) / 2))) return "NV12 pitch below max(W, 2 * ((W + 1) / 2))";
+    if (format == 1 && ((H | W) & 1)) return "I420 needs an even width and height";
+    if (format == 1 && pitch != W) return "I420 is packed: pitch must equal W";
+    s.m = YUV_MATRICES[matrix];
+    s.H = H; s.W = W; s.pitch = pitch; s.format = format;
+    return nullptr;
+}
+
 #ifdef __HIPCC__
 __device__ __forceinline__ int pp_sat8i(int v) { return v < 0 ? 0 : (v > 255 ? 255 : v); }
 // inverse of f() on a Q15 argument (may be negative): t > 0.206893 ? t^3 : (t - 16 / 116) / 7.787, Q15 result, floor rounding
@@ -207,5 +249,32 @@ __device__ __forceinline__ void undistort_from_taps(const UndistortParams& p, ui
 #undef PP_B
     c0 = acc[0] >> 15; c1 = acc[1] >> 15; c2 = acc[2] >> 15;
     c0 = c0 > 255 ? 255 : c0; c1 = c1 > 255 ? 255 : c1; c2 = c2 > 255 ? 255 : c2;
+}
+
+// The chroma terms of a 2x1 / 2x2 block (rounding constant included), computed once per chroma sample
+struct YuvChroma { int r, g, b; };
+__device__ __forceinline__ YuvChroma yuv_chroma(const YuvMatrix& m, int U, int V) {
+    const int u = U - 128, v = V - 128;
+    return YuvChroma{m.cvr * v + (1 << 19), m.cvg * v + m.cug * u + (1 << 19), m.cub * u + (1 << 19)};
+}
+// One pixel, packed as the three bytes B | G << 8 | R << 16
+__device__ __forceinline__ uint32_t yuv_pixel_bgr(const YuvMatrix& m, int Y, const YuvChroma& c) {
+    const int d = Y - m.yoff, yy = (d < 0 ? 0 : d) * m.cy;
+    return (uint32_t)pp_sat8i((yy + c.b) >> 20) | ((uint32_t)pp_sat8i((yy + c.g) >> 20) << 8) | ((uint32_t)pp_sat8i((yy + c.r) >> 20) << 16);
+}
+// Four pixels of one row from their four luma bytes (y4, pixel k in byte k) and the two chroma samples under them: 12 BGR bytes
+__device__ __forceinline__ void yuv_quad_bgr(const YuvMatrix& m, uint32_t y4, int U0, int V0, int U1, int V1, uint32_t out[3]) {
+    const YuvChroma c0 = yuv_chroma(m, U0, V0), c1 = yuv_chroma(m, U1, V1);
+    const uint32_t p0 = yuv_pixel_bgr(m, (int)(y4 & 0xffu), c0), p1 = yuv_pixel_bgr(m, (int)((y4 >> 8) & 0xffu), c0);
+    const uint32_t p2 = yuv_pixel_bgr(m, (int)((y4 >> 16) & 0xffu), c1), p3 = yuv_pixel_bgr(m, (int)(y4 >> 24), c1);
+    out[0] = p0 | (p1 << 24); out[1] = (p1 >> 8) | (p2 << 16); out[2] = (p2 >> 16) | (p3 << 8);
+}
+// Four bytes at byte offset `off` of a range-checked buffer: one aligned dword, or two funnel-shifted.  Bytes outside read 0.
+__device__ __forceinline__ uint32_t pp_load4(__amdgpu_buffer_rsrc_t rs, int off) {
+    const int a = off & ~3, sh = (off & 3) * 8;
+    const uint32_t lo = __builtin_amdgcn_raw_buffer_load_b32(rs, a, 0, 0);
+    if (!sh) return lo;
+    const uint32_t hi = __builtin_amdgcn_raw_buffer_load_b32(rs, a + 4, 0, 0);
+    return (lo >> sh) | (hi << (32 - sh));
 }
 #endif

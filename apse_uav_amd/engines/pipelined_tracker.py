@@ -26,6 +26,7 @@ import numpy as np
 import torch
 
 from ..networks.track_rcnn import TrackRCNN
+from ..structures.yuv_frame import YuvBatch, YuvFrame
 from .rcnn_tracker import RcnnTracker, instances_from_record, require_embeddings_metric
 from .track_predictor import FrameUploader
 
@@ -69,16 +70,19 @@ class PipelinedRcnnTracker:
         k = self._submitted % self.depth
         st = self.streams[k]
         slot = None
-        if torch.is_tensor(frame):
+        if isinstance(frame, YuvFrame) and frame.is_cuda:              # a decoder surface (cfg.INPUT.FORMAT NV12 / I420): read in place
+            dev = YuvBatch.of([frame])
+            st.wait_stream(torch.cuda.current_stream(self.device))
+            frame.data.record_stream(st)
+        elif torch.is_tensor(frame) and frame.dim() >= 3:
             dev = frame.reshape((1,) + tuple(frame.shape[-3:]))
             st.wait_stream(torch.cuda.current_stream(self.device))     # whatever produced the tensor
             dev.record_stream(st)                                      # the allocator must not recycle it under us
         else:
             slot = self._uploader.begin([frame], st)                   # same staging / channel-order logic as TrackPredictor
-            dev = slot.dev
+            dev = slot.frames
         with torch.cuda.stream(st):
-            if self.tracker.predictor.frame_preprocessor is not None:
-                dev = self.tracker.predictor.frame_preprocessor(dev)
+            dev = self.tracker.predictor._unfused(dev)                 # the separate-kernel camera form, if set
             self.models[k].preprocess_frames(dev)
             if slot is not None:
                 FrameUploader.release(slot, st)

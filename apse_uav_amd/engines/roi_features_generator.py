@@ -21,6 +21,7 @@ import torch
 from .. import _lib
 from ..config import is_c4
 from ..networks.track_rcnn import TrackRCNN
+from ..structures.yuv_frame import YuvBatch, YuvFrame
 from ..utils import rle
 from ..weights import load_detector_file, synthetic_detector_state, blocks_from_state
 
@@ -92,10 +93,16 @@ class RoiFeaturesGenerator:
         rois = torch.zeros((n, C, self.roi_size, self.roi_size), dtype=torch.float32, device=self.device)
         if n == 0:
             return ids, rois
-        if self._staging is None or self._staging.shape != (1, height, width, 3):
-            self._staging = torch.empty((1, height, width, 3), dtype=torch.uint8).pin_memory()
-        self._staging[0].copy_(torch.from_numpy(np.ascontiguousarray(original_image)))
-        frame = self._staging.to(self.device, non_blocking=True)
+        if isinstance(original_image, YuvFrame):          # NV12 / I420 (structures/yuv_frame.py): converted inside the resize staging
+            data = original_image.data
+            if not original_image.is_cuda:
+                data = torch.from_numpy(data).to(self.device)
+            frame = YuvBatch(data[None], height, width, original_image.pitch, original_image.format)
+        else:
+            if self._staging is None or self._staging.shape != (1, height, width, 3):
+                self._staging = torch.empty((1, height, width, 3), dtype=torch.uint8).pin_memory()
+            self._staging[0].copy_(torch.from_numpy(np.ascontiguousarray(original_image)))
+            frame = self._staging.to(self.device, non_blocking=True)
         m = self.model
         m.preprocess_frames(frame)
         s = _lib.stream_ptr()

@@ -18,6 +18,7 @@ import numpy as np
 import torch
 
 from ..networks.track_rcnn import TrackRCNN
+from ..structures.yuv_frame import FORMATS as YUV_FORMATS, YuvBatch, YuvFrame, as_yuv, matrix_index
 from ..weights import load_detector_file
 
 
@@ -37,7 +38,7 @@ def _host_copy(dst, src):
 
 
 class _Slot:
-    __slots__ = ("pinned", "pinned_np", "dev", "h2d_done", "consumed", "consumed_pending", "key")
+    __slots__ = ("pinned", "pinned_np", "dev", "h2d_done", "consumed", "consumed_pending", "key", "yuv")
 
     def __init__(self, shape, device):
         self.pinned = torch.empty(shape, dtype=torch.uint8).pin_memory()
@@ -47,6 +48,12 @@ class _Slot:
         self.consumed = torch.cuda.Event()
         self.consumed_pending = False        # True: handed out, the consumer's event has not been recorded yet
         self.key = None
+        self.yuv = None                      # YUV input: the YuvBatch over ``dev`` (what the consumers are handed)
+
+    @property
+    def frames(self):
+        """What the resize reads: the BGR tensor [B, H, W, 3], or the YuvBatch over the slot's (B, rows, pitch) buffer."""
+        return self.dev if self.yuv is None else self.yuv
 
 
 class FrameUploader:
@@ -63,19 +70,45 @@ class FrameUploader:
         self._slots = [None] * self.nslots
         self._k = -1
 
-    def begin(self, frames, stream):
-        B = len(frames)
+    @staticmethod
+    def band_rows(rows, bands):
+        """The row bands [(lo, hi), ...] a frame of ``rows`` rows is staged and sent in."""
+        nb = bands if rows >= 8 * bands else 1
+        step = (rows + nb - 1) // nb
+        return [(lo, min(lo + step, rows)) for lo in range(0, rows, step)]
+
+    def slot_shape(self, frames):
+        """Shape of the staging buffers for ``frames``: (B, H, W, 3) for BGR / RGB; (B, rows, pitch) for NV12 / I420, whose row
+        bands then cover the luma rows and the chroma rows behind them alike.  Second value: the frames as ``YuvFrame``s, or None."""
+        if self.input_format in YUV_FORMATS:
+            yf = [as_yuv(f, self.input_format) for f in frames]
+            for f in yf:
+                if f.format != self.input_format:
+                    raise ValueError("a %s frame under INPUT.FORMAT = %s" % (f.format, self.input_format))
+                if f.geometry != yf[0].geometry:
+                    raise ValueError("frames of one batch must have the same size, pitch and format")
+                if f.is_cuda:
+                    raise ValueError("a batch mixes host and device frames: device-resident YuvFrames are read in place, not uploaded")
+            return (len(yf), yf[0].rows, yf[0].pitch), yf
         H, W = frames[0].shape[:2]
-        shape = (B, H, W, 3)
+        for f in frames:
+            if isinstance(f, YuvFrame) or getattr(f, "ndim", 3) != 3:
+                raise ValueError("INPUT.FORMAT = %s takes HxWx3 uint8 frames; set it to NV12 / I420 for YUV frames" % self.input_format)
+            if f.shape[:2] != (H, W):
+                raise ValueError("frames of one batch must have the same size")
+        return (len(frames), H, W, 3), None
+
+    def begin(self, frames, stream):
+        shape, yuv = self.slot_shape(frames)
+        src = frames if yuv is None else [f.data for f in yuv]
+        H = shape[1]                                  # rows to copy per frame
         self._k = (self._k + 1) % self.nslots
         sl = self._slots[self._k]
         if sl is None or tuple(sl.pinned.shape) != shape:
             sl = self._slots[self._k] = _Slot(shape, self.device)
         else:
             sl.h2d_done.synchronize()                 # the pinned buffer's previous H2D has left the host
-        for f in frames:
-            if f.shape[:2] != (H, W):
-                raise ValueError("frames of one batch must have the same size")
+        sl.yuv = None if yuv is None else YuvBatch(sl.dev, yuv[0].height, yuv[0].width, yuv[0].pitch, yuv[0].format)
         if sl.consumed_pending:                       # a caller that never released the slot: be conservative
             sl.consumed.record(torch.cuda.current_stream(self.device))
             sl.consumed_pending = False
@@ -83,13 +116,11 @@ class FrameUploader:
             stream.wait_event(sl.consumed)            # device buffer: its last reader (the resize kernels) is done
             # staged and sent in row bands: while band k crosses PCIe, the host threads copy band k + 1 into the pinned buffer
             # (a 4K frame: ~1 ms of host copy + ~0.5 ms of DMA, overlapped instead of back to back)
-            nb = self.BANDS if H >= 8 * self.BANDS else 1
-            step = (H + nb - 1) // nb
-            for i, f in enumerate(frames):
+            bands = self.band_rows(H, self.BANDS)
+            for i, f in enumerate(src):
                 if self.input_format == "RGB":        # track_predictor.py:43-45: the model wants BGR
                     f = f[:, :, ::-1]
-                for lo in range(0, H, step):
-                    hi = min(lo + step, H)
+                for lo, hi in bands:
                     _host_copy(sl.pinned_np[i, lo:hi], f[lo:hi])      # strided source (the RGB flip) is handled by numpy
                     sl.dev[i, lo:hi].copy_(sl.pinned[i, lo:hi], non_blocking=True)
             sl.h2d_done.record(stream)
@@ -117,11 +148,14 @@ class TrackPredictor:
         elif cfg.MODEL.WEIGHTS:
             self.model.load_state_dict(load_detector_file(cfg.MODEL.WEIGHTS))
         self.input_format = cfg.INPUT.FORMAT
-        assert self.input_format in ["RGB", "BGR"], self.input_format
+        assert self.input_format in ["RGB", "BGR", "NV12", "I420"], self.input_format
+        self.yuv_matrix = str(self.cfg.APSE.get("YUV_MATRIX", "cv601"))
+        matrix_index(self.yuv_matrix)         # an unknown name is refused here, not at the first frame
         self.frame_preprocessor = None        # optional FramePreprocessor (cfg.APSE.FUSED_PREPROC / set_camera)
         self._uploader = None
         self._copy_stream = None
         self._prefetched = None
+        self._resident = None                 # announced device-resident YuvFrames (prefetch): pre-staged, never uploaded
         self._last_slot = None
 
     def set_camera(self, cam_params, gamma=2.0, fused=None):
@@ -154,13 +188,29 @@ class TrackPredictor:
         copy stream, so the 24.9 MB H2D overlaps the GPU work already enqueued.  The next call must pass the SAME array
         object(s), unmodified since this call (the match is by identity: the bytes were staged here); anything else is uploaded
         afresh."""
+        self._resident = None
         if frames is None:
             return
         frames = list(frames) if isinstance(frames, (list, tuple)) else [frames]
+        if self._on_device(frames):
+            self._resident = frames           # decoder surfaces already on the device: nothing to upload, only to pre-stage
+            return
         self._prefetched = self._up().begin(frames, self._copy_stream)
 
+    @staticmethod
+    def _on_device(frames):
+        return all(isinstance(f, YuvFrame) and f.is_cuda for f in frames)
+
     def _upload(self, frames):
-        """list of HxWx3 uint8 arrays -> CUDA tensor [B, H, W, 3] (BGR), resident or in flight on the current stream."""
+        """list of HxWx3 uint8 arrays -> CUDA tensor [B, H, W, 3] (BGR), resident or in flight on the current stream.  Under
+        INPUT.FORMAT NV12 / I420: list of ``YuvFrame``s (or bare 2-D arrays) -> ``YuvBatch``; device-resident ``YuvFrame``s are
+        consumed in place (one frame: no copy; the caller keeps it alive until the resize is enqueued)."""
+        if self.input_format in YUV_FORMATS and self._on_device(frames):
+            if self._prefetched is not None:
+                FrameUploader.release(self._prefetched, self._copy_stream)
+                self._prefetched = None
+            self._last_slot = None
+            return self._unfused(self._device_batch(frames))
         up = self._up()
         cur = torch.cuda.current_stream(self.model.device)
         sl, self._prefetched = self._prefetched, None
@@ -171,11 +221,25 @@ class TrackPredictor:
                 FrameUploader.release(sl, self._copy_stream)          # a prefetch that was never used
             sl = up.begin(frames, cur)
         self._last_slot = sl
-        dev = sl.dev
+        dev = self._unfused(sl.frames)
         if self.frame_preprocessor is not None:
-            dev = self.frame_preprocessor(dev)
             FrameUploader.release(sl)
         return dev
+
+    def _device_batch(self, frames):
+        for f in frames:
+            if f.format != self.input_format:
+                raise ValueError("a %s frame under INPUT.FORMAT = %s" % (f.format, self.input_format))
+        return YuvBatch.of(frames)
+
+    def _unfused(self, dev):
+        """The separate-kernel camera form (set_camera(fused=False)): YUV frames are converted first, then pre-processed."""
+        if self.frame_preprocessor is None:
+            return dev
+        if isinstance(dev, YuvBatch):
+            from ..utils.preprocess import yuv_to_bgr
+            dev = yuv_to_bgr(dev, self.yuv_matrix)
+        return self.frame_preprocessor(dev)
 
     def _frames_consumed(self):
         """The resize kernels reading the uploaded frame are enqueued: its device buffer may be refilled after them."""
@@ -187,18 +251,24 @@ class TrackPredictor:
         """The announced next frame(s) are on their way to the device: enqueue their resize + normalise BEHIND the current forward
         (and behind its results copy), so that the next call starts with the network itself.  The input tensor is free by then
         (the stem read it at the start of this forward); nothing else of this forward is touched."""
+        res, self._resident = self._resident, None
+        key = self.model._ctx_key
+        if res is not None and self.frame_preprocessor is None and self.input_format in YUV_FORMATS and key is not None:
+            batch = self._device_batch(res)   # announced frames that live on the device: the same, without a slot
+            if tuple(batch.shape[1:3]) == tuple(key[0]) and batch.shape[0] <= int(self.cfg.APSE.MAX_BATCH):
+                self.model.preprocess_frames(batch, tag=res)
+            return
         sl = self._prefetched
         if sl is None or self.frame_preprocessor is not None:
             return
-        key = self.model._ctx_key
-        if key is None or tuple(sl.dev.shape[1:3]) != tuple(key[0]) or sl.dev.shape[0] > int(self.cfg.APSE.MAX_BATCH):
+        if key is None or tuple(sl.frames.shape[1:3]) != tuple(key[0]) or sl.dev.shape[0] > int(self.cfg.APSE.MAX_BATCH):
             # an announced frame of ANOTHER size: staging it would rebuild the context while this frame's results copy is still
             # pending (read_begin .. read_end).  Leave the slot to the next call's normal upload path (it still finds the frame
             # resident); no pre-stage, hence no run-ahead.
             return
         self._prefetched = None
         torch.cuda.current_stream(self.model.device).wait_event(sl.h2d_done)
-        self.model.preprocess_frames(sl.dev, tag=sl.key)
+        self.model.preprocess_frames(sl.frames, tag=sl.key)
         FrameUploader.release(sl)
 
     def _predict(self, frames, given=None, want_masks=True, upcoming=None, rpn_levels=31, run_ahead=False):

@@ -15,6 +15,7 @@ import torch
 from .. import _lib
 from ..structures.instances import Boxes, Instances
 from ..structures.window_mask import MaskList, WindowMask
+from ..structures.yuv_frame import FORMATS, YuvBatch, YuvFrame, matrix_index
 from ..utils import resample
 from ..config import check_c4_supported, is_c4
 from ..weights import blocks_from_state, is_c4_state
@@ -307,13 +308,28 @@ class TrackRCNN:
     def preprocess_frames(self, frames, tag=None):
         """frames: uint8 CUDA tensor [B, H, W, 3] (BGR).  Fused PIL-exact resize + normalise + pad.  ``tag``: what the network
         input now holds, for a caller that stages the NEXT frame's input behind the current forward (TrackPredictor._prestage);
-        any other write of the input clears it."""
-        B, H, W, _ = frames.shape
+        any other write of the input clears it.  Or a ``YuvBatch`` / device ``YuvFrame`` (structures/yuv_frame.py): NV12 / I420
+        frames, converted with ``cfg.APSE.YUV_MATRIX`` inside the resize's row staging (``apse_preprocess_frames_yuv``) -- the
+        network input holds the bytes of the BGR path on ``utils.preprocess.yuv_to_bgr`` of the same frames."""
+        yuv = None
+        if isinstance(frames, YuvFrame):
+            frames = YuvBatch.of([frames])
+        if isinstance(frames, YuvBatch):
+            yuv, frames = frames, frames.dev
+            if not frames.is_cuda:
+                raise _lib.ApseError("preprocess_frames needs device frames: upload a host YuvFrame first (TrackPredictor does)")
+            B, H, W, _ = yuv.shape
+        else:
+            B, H, W, _ = frames.shape
         ih, iw = resample.resize_shortest_edge(H, W, self.cfg.INPUT.MIN_SIZE_TEST, self.cfg.INPUT.MAX_SIZE_TEST)
         self._ensure_ctx((H, W), (ih, iw))
         self._input_tag = None
         self._running_tag = None
-        self._call("apse_preprocess_frames", _lib.ptr(frames.contiguous()), B, _lib.stream_ptr())
+        if yuv is not None:
+            self._call("apse_preprocess_frames_yuv", _lib.ptr(frames), B, yuv.pitch, FORMATS[yuv.format],
+                       matrix_index(self.cfg.APSE.get("YUV_MATRIX", "cv601")), _lib.stream_ptr())
+        else:
+            self._call("apse_preprocess_frames", _lib.ptr(frames.contiguous()), B, _lib.stream_ptr())
         self._input_tag = tag
         return B
 

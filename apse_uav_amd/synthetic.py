@@ -147,3 +147,64 @@ def write_synthetic_mots(root, seqs=("0000", "0001"), frames=14, height=160, wid
     with open(seqmap, "w") as f:
         f.write("\n".join(lines_map) + "\n")
     return seqmap
+
+
+# ---- YUV 4:2:0 test input (what a decoder would hand out): host numpy, float coefficients.  Test and dry-run input only --
+# nothing pins these bytes; the conversion BACK is the library's (structures/yuv_frame.py, tests/yuv_ref.py).
+_YUV_KRKB = {"cv601": (0.299, 0.114, False), "bt601": (0.299, 0.114, False), "bt709": (0.2126, 0.0722, False),
+             "bt601-full": (0.299, 0.114, True), "bt709-full": (0.2126, 0.0722, True)}
+
+
+def _bgr_to_yuv420(frame, matrix):
+    """HxWx3 uint8 BGR -> (Y [H][W], U [CH][CW], V [CH][CW]) uint8: rint of the float transform, chroma the mean of each 2x2 block
+    (edge blocks of an odd frame average the pixels that exist)."""
+    kr, kb, full = _YUV_KRKB[matrix]
+    f = np.asarray(frame, np.float64)
+    b, g, r = f[..., 0], f[..., 1], f[..., 2]
+    y = kr * r + (1.0 - kr - kb) * g + kb * b
+    u, v = (b - y) / (2.0 * (1.0 - kb)), (r - y) / (2.0 * (1.0 - kr))
+    H, W = y.shape
+    CH, CW = (H + 1) // 2, (W + 1) // 2
+
+    def pool(c):
+        p = np.pad(c, ((0, 2 * CH - H), (0, 2 * CW - W)), mode="edge")
+        return p.reshape(CH, 2, CW, 2).mean(axis=(1, 3))
+    sy, oy, sc = (1.0, 0.0, 1.0) if full else (219.0 / 255.0, 16.0, 224.0 / 255.0)
+    q = lambda a: np.clip(np.rint(a), 0, 255).astype(np.uint8)
+    return q(y * sy + oy), q(pool(u) * sc + 128.0), q(pool(v) * sc + 128.0)
+
+
+def bgr_to_nv12(frame, matrix="cv601", pitch=None):
+    """HxWx3 uint8 BGR -> a ``YuvFrame`` (NV12, host) of the same size; ``pitch`` (default: the width rounded up to even) pads the
+    rows like a decoder surface, with a byte pattern that is not zero."""
+    from .structures.yuv_frame import YuvFrame
+    Y, U, V = _bgr_to_yuv420(frame, matrix)
+    H, W = Y.shape
+    CH, CW = U.shape
+    pitch = max(W, 2 * CW) if pitch is None else int(pitch)
+    data = np.full((H + CH, pitch), 0x5a, np.uint8)
+    data[:H, :W] = Y
+    data[H:, 0:2 * CW:2] = U
+    data[H:, 1:2 * CW:2] = V
+    return YuvFrame(data, W, "NV12")
+
+
+def bgr_to_i420(frame, matrix="cv601"):
+    """HxWx3 uint8 BGR (even H and W) -> a ``YuvFrame`` (I420, host)."""
+    from .structures.yuv_frame import YuvFrame
+    Y, U, V = _bgr_to_yuv420(frame, matrix)
+    H, W = Y.shape
+    if (H | W) & 1:
+        raise ValueError("I420 needs an even width and height, got %dx%d" % (W, H))
+    data = np.concatenate([Y.reshape(-1), U.reshape(-1), V.reshape(-1)]).reshape(3 * H // 2, W)
+    return YuvFrame(data, W, "I420")
+
+
+def encoded_source(get_frame, input_format="BGR", matrix="cv601"):
+    """A BGR frame source ``t -> HxWx3`` as one that yields frames in ``input_format`` ("BGR": unchanged; "NV12" / "I420":
+    encoded with the functions above) -- how the tools feed synthetic sequences to a run with cfg.INPUT.FORMAT = NV12 / I420."""
+    fmt = str(input_format).upper()
+    if fmt == "BGR":
+        return get_frame
+    enc = {"NV12": bgr_to_nv12, "I420": bgr_to_i420}[fmt]
+    return lambda t: enc(get_frame(t), matrix)

@@ -48,3 +48,21 @@ class FramePreprocessor:
         """numpy HxWx3 uint8 -> numpy, like the reference function."""
         d = torch.from_numpy(np.ascontiguousarray(frame)).cuda()[None]
         return self(d)[0].cpu().numpy()
+
+
+def yuv_to_bgr(frame, matrix="cv601"):
+    """A ``YuvFrame`` (host or device; structures/yuv_frame.py) or a ``YuvBatch`` -> uint8 CUDA tensor BGR [H, W, 3] ([B, H, W, 3]
+    for a batch), by the stand-alone converter (``apse_yuv_to_bgr``): the bytes the fused resize staging computes on the fly."""
+    from ..structures.yuv_frame import FORMATS, YuvBatch, YuvFrame, matrix_index
+    single = isinstance(frame, YuvFrame)
+    if single:
+        data = frame.data if frame.is_cuda else torch.from_numpy(frame.data).cuda()
+        frame = YuvBatch(data[None], frame.height, frame.width, frame.pitch, frame.format)
+    if not frame.dev.is_cuda:
+        raise _lib.ApseError("yuv_to_bgr needs CUDA frames (no CPU fallback)")
+    B, H, W, _ = frame.shape
+    out = torch.empty((B, H, W, 3), dtype=torch.uint8, device=frame.dev.device)
+    rc = _lib.load().apse_yuv_to_bgr(_lib.ptr(frame.dev), _lib.ptr(out), B, H, W, frame.pitch, FORMATS[frame.format],
+                                     matrix_index(matrix), _lib.stream_ptr())
+    _lib.check(rc, None, "apse_yuv_to_bgr: " + _lib.load().apse_last_error(None).decode())
+    return out[0] if single else out

@@ -15,6 +15,7 @@ import torch
 
 from .. import _lib
 from ..structures import device_windows as dw
+from ..structures.yuv_frame import YuvFrame
 
 MAX_ITEMS_PER_IMAGE = 100
 _GOLDEN = 0.6180339887498949
@@ -119,9 +120,13 @@ class TrackVisualizer:
         self.device = dw.default_device(device)
         self._uploader = None
         self._breaks = {}
+        self.yuv_matrix = "cv601"             # conversion of YuvFrame input (cfg.APSE.YUV_MATRIX of the run that made the frames)
 
     def _frame(self, frame, inplace):
         """-> (source [1, H, W, 3] device, output [1, H, W, 3] device, uploader slot or None)."""
+        if isinstance(frame, YuvFrame):                   # NV12 / I420: drawn on its BGR conversion (a new device frame)
+            from .preprocess import yuv_to_bgr
+            frame = yuv_to_bgr(frame, self.yuv_matrix)
         if isinstance(frame, np.ndarray):
             if inplace:
                 raise ValueError("inplace=True needs a device frame")

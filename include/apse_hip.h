@@ -164,6 +164,15 @@ int apse_set_camera(apse_ctx* ctx, const double* m9, const double* dist, int ndi
 /* ResizeShortestEdge.apply_image (PIL bilinear) + preprocess_image: u8 BGR frames [B][frame_h][frame_w][3]
  * -> internal normalised, /32-padded network input (track_predictor.py:48-49, track_rcnn.py:35). */
 int apse_preprocess_frames(apse_ctx* ctx, const uint8_t* frames_dev, int batch, void* stream);
+/* The same from YUV 4:2:0 frames, as video decoders hand them out: `batch` contiguous frames of the context's frame_h x frame_w
+ * in `format` (APSE_FMT_*) with row pitch `pitch` bytes, converted with `matrix` (APSE_YUV_*).  The conversion runs inside the
+ * horizontal resize pass while it stages a source row (luma row y, chroma row y >> 1 -> the row's BGR bytes in LDS), so the
+ * network input holds the bytes apse_preprocess_frames builds from apse_yuv_to_bgr's output, and no BGR frame is written.
+ * With a camera set (apse_set_camera) the frames are first converted into BGR frames owned by the context (allocated at the
+ * first such call), then pre-processed as BGR: "convert, then preprocess_img".  Same contract as apse_preprocess_frames
+ * otherwise (stream, tail lane, arch 1).  APSE_E_INVALID: a layout outside the rules at APSE_FMT_*, an unknown matrix, a batch
+ * of 2 GiB or more. */
+int apse_preprocess_frames_yuv(apse_ctx* ctx, const uint8_t* frames_dev, int batch, int pitch, int format, int matrix, void* stream);
 /* Same from already-resized f32 CHW images [B][3][image_h][image_w] (the reference's model input). */
 int apse_preprocess_images(apse_ctx* ctx, const float* images_dev, int batch, void* stream);
 /* ResNet-101 + FPN (track_rcnn.py:42); C4: stem + res2..res4. */
@@ -342,6 +351,35 @@ size_t apse_lab_tables_host(const uint8_t* lut256_host, void* out, size_t cap);
 int apse_resize_normalize(const uint8_t* frames_dev, uint8_t* tmp_dev, float* out_nhwc4_dev, uint8_t* resized_u8_dev,
                           const int* hb_dev, const int* hc_dev, int hk, const int* vb_dev, const int* vc_dev, int vk, int B,
                           int H, int W, int OH, int OW, int PH, int PW, const float* mean3_host, void* stream);
+
+/* ---- YUV 4:2:0 frames.  With CH = (H + 1) / 2 and CW = (W + 1) / 2:
+ *   APSE_FMT_NV12  H luma rows of `pitch` bytes, then CH rows of `pitch` bytes holding CW interleaved (U, V) pairs.  Any
+ *                  pitch >= max(W, 2 CW) (decoder surfaces are padded), odd W and H allowed; a frame is (H + CH) * pitch bytes.
+ *   APSE_FMT_I420  packed: H x W luma, a CH x CW U plane, a CH x CW V plane.  W and H even, pitch == W.
+ * A batch is contiguous frames of one geometry, at any byte alignment.  Conversion (csrc/preproc_pixel.h; tests/yuv_ref.py is
+ * the numpy restatement): pixel (x, y) takes Y at (x, y) and the chroma sample (x >> 1, y >> 1) -- nearest siting, as
+ * OpenCV's COLOR_YUV2BGR_NV12; u = U - 128, v = V - 128, yy = max(0, Y - yoff) * CY,
+ *   R = sat8((yy + CVR v + 2^19) >> 20), G = sat8((yy + CVG v + CUG u + 2^19) >> 20), B = sat8((yy + CUB u + 2^19) >> 20)
+ * in int32 with a flooring shift.  (yoff, CY, CVR, CVG, CUG, CUB) per matrix: apse_yuv_matrix_host.  APSE_YUV_CV601 holds
+ * OpenCV's ITUR_BT_601 constants; the others are rint(2^20 x) of the BT.601 / BT.709 expressions, limited (16..235) or full
+ * range.  4K H.264 from a DJI camera is APSE_YUV_BT709. */
+#define APSE_FMT_NV12 0
+#define APSE_FMT_I420 1
+#define APSE_YUV_CV601 0
+#define APSE_YUV_BT601 1
+#define APSE_YUV_BT709 2
+#define APSE_YUV_BT601_FULL 3
+#define APSE_YUV_BT709_FULL 4
+/* B frames -> u8 BGR [B][H][W][3].  Reads nothing outside the B frames; src and dst at any byte alignment.  Frame sizes as
+ * apse_resize_normalize; APSE_E_INVALID (text in apse_last_error(NULL)) for a size, layout or matrix outside the rules. */
+int apse_yuv_to_bgr(const uint8_t* src_dev, uint8_t* dst_dev, int B, int H, int W, int pitch, int format, int matrix, void* stream);
+/* Host only: the six integers (yoff, CY, CVR, CVG, CUG, CUB) of a matrix. */
+int apse_yuv_matrix_host(int matrix, int* out6);
+/* apse_resize_normalize from YUV frames: the conversion fused into the row staging, as in apse_preprocess_frames_yuv. */
+int apse_resize_normalize_yuv(const uint8_t* frames_dev, int pitch, int format, int matrix, uint8_t* tmp_dev, float* out_nhwc4_dev,
+                              uint8_t* resized_u8_dev, const int* hb_dev, const int* hc_dev, int hk, const int* vb_dev,
+                              const int* vc_dev, int vk, int B, int H, int W, int OH, int OW, int PH, int PW,
+                              const float* mean3_host, void* stream);
 
 /* ---- host-only: native replay of the sequential association from per-frame records (rank 0 of a sharded run).
  * Same rules as RcnnTracker.associate_detections_to_objects / ObjectInstances / generate_log_oneline

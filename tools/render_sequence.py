@@ -41,6 +41,11 @@ def main(argv=None):
     ap.add_argument("--resize", default="", help="WxH of the written PNGs (Pillow bilinear); default: frame size")
     ap.add_argument("--out-dir", default="", help="PNG directory (default: no files written)")
     ap.add_argument("--reps", type=int, default=50, help="repetitions of each timed render")
+    ap.add_argument("--input-format", default="bgr", choices=["bgr", "nv12", "i420"],
+                    help="frame format handed to the tracker (cfg.INPUT.FORMAT); nv12 / i420: the BGR frames are encoded on the "
+                         "host first (apse_uav_amd/synthetic.py), as a stand-in for a video decoder's output")
+    ap.add_argument("--yuv-matrix", default="cv601", choices=["cv601", "bt601", "bt709", "bt601-full", "bt709-full"],
+                    help="YUV -> BGR conversion of nv12 / i420 input (cfg.APSE.YUV_MATRIX)")
     args = ap.parse_args(argv)
     if not torch.cuda.is_available():
         sys.exit("render_sequence.py: no GPU visible (the renderer has no CPU fallback)")
@@ -52,6 +57,8 @@ def main(argv=None):
     from apse_uav_amd.weights import UAV4K_R101_CLS_BIAS, synthetic_association_state, synthetic_detector_state
     H, W = [int(v) for v in args.size.split("x")]
     cfg = setup_cfg()
+    cfg.INPUT.FORMAT = args.input_format.upper()
+    cfg.APSE.YUV_MATRIX = args.yuv_matrix
     tracker = RcnnTracker(cfg, (H, W), synthetic_association_state(1),
                           detector_state=synthetic_detector_state(0, cls_bias=UAV4K_R101_CLS_BIAS))
     seq = SyntheticSequence(args.kind, H, W)
@@ -60,13 +67,17 @@ def main(argv=None):
         from run_sequence import synthetic_given_fn
         given_fn = synthetic_given_fn(seq, H, W, cfg.INPUT.MIN_SIZE_TEST, cfg.INPUT.MAX_SIZE_TEST)
     vis = TrackVisualizer({"thing_classes": ["car", "truck", "bus", "van"]})
+    vis.yuv_matrix = args.yuv_matrix
+    from apse_uav_amd.synthetic import encoded_source
+    from apse_uav_amd.utils.preprocess import yuv_to_bgr
+    get_frame = encoded_source(seq.frame, cfg.INPUT.FORMAT, args.yuv_matrix)
     if args.out_dir:
         os.makedirs(args.out_dir, exist_ok=True)
     size = tuple(int(v) for v in args.resize.split("x")) if args.resize else None
     step_ms, oop_ms, inp_ms, counts = [], [], [], []
     t0 = time.perf_counter()
     for t in range(args.frames):
-        frame = seq.frame(t)
+        frame = get_frame(t)                  # BGR, or its NV12 / I420 encoding: tracked and drawn as it is
         a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
         a.record()
         if given_fn is not None:
@@ -84,7 +95,7 @@ def main(argv=None):
             if size:
                 im = im.resize(size, Image.BILINEAR)
             im.save(os.path.join(args.out_dir, "image_%04d.png" % (t + 1)))
-        dev = torch.from_numpy(frame).to("cuda")
+        dev = torch.from_numpy(frame).to("cuda") if cfg.INPUT.FORMAT == "BGR" else yuv_to_bgr(frame, args.yuv_matrix)
         oop_ms.append(_events_ms(lambda: vis.draw_instance_predictions(dev, objs), args.reps))
         inp_ms.append(_events_ms(lambda: vis.draw_instance_predictions(dev, objs, inplace=True), args.reps))
     dt = time.perf_counter() - t0

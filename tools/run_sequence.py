@@ -9,6 +9,7 @@ Frame-sharded over N GPUs (BASELINE config 4), either form:
     torchrun --nproc-per-node N tools/run_sequence.py --gpus N --frames 64 --out seq.csv
 --start-frame S skips the first S frames like the reference loop does (visualize_uav.py:172-190): they are read and
 dropped, the CSV's frame column keeps the absolute frame index.
+--input-format nv12 | i420 hands the tracker YUV 4:2:0 frames (what a decoder gives; --yuv-matrix names the conversion).
 --preproc runs preprocess_img (undistort + Lab gamma, visualize_uav.py:56-71) fused into the resize; --given-boxes feeds the
 synthetic vehicles' boxes through the reference's detected_instances entry (track_rcnn.py:52-54).  BASELINE configs[2] / [3]:
     python tools/run_sequence.py [--gpus 8] --kind dynamic --frames 64 --dtype bf16 --batch 4 --preproc [--given-boxes]
@@ -145,6 +146,11 @@ def main(argv=None):
                          "RPN / box branch -- the deterministic form of configs 1-4 (SURVEY 8d)")
     ap.add_argument("--in-flight", type=int, default=1,
                     help="single process: frames in flight on separate streams (engines/pipelined_tracker.py); 1 = plain loop")
+    ap.add_argument("--input-format", default="bgr", choices=["bgr", "nv12", "i420"],
+                    help="frame format handed to the tracker (cfg.INPUT.FORMAT): nv12 / i420 frames are what a video decoder gives; "
+                         "here the BGR source frames are encoded on the host first (apse_uav_amd/synthetic.py)")
+    ap.add_argument("--yuv-matrix", default="cv601", choices=["cv601", "bt601", "bt709", "bt601-full", "bt709-full"],
+                    help="YUV -> BGR conversion of nv12 / i420 input (cfg.APSE.YUV_MATRIX)")
     args = ap.parse_args(argv)
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:        # no launcher: start the ranks (nothing has touched the GPU yet)
@@ -184,7 +190,11 @@ def main(argv=None):
     cfg = setup_cfg(device="cuda:%d" % local)
     cfg.APSE.MAX_BATCH = args.batch
     cfg.APSE.DTYPE = args.dtype
+    cfg.INPUT.FORMAT = args.input_format.upper()
+    cfg.APSE.YUV_MATRIX = args.yuv_matrix
     n, get_frame = frame_source(args, H, W)
+    from apse_uav_amd.synthetic import encoded_source
+    get_frame = encoded_source(get_frame, cfg.INPUT.FORMAT, args.yuv_matrix)
     first = min(max(args.start_frame, 0), n)
     given_fn = None
     if args.given_boxes:

@@ -55,6 +55,11 @@ def main(argv=None):
     ap.add_argument("--detector-state", default="", help="torch.load-able detector state dict")
     ap.add_argument("--association-state", default="", help="torch.load-able association head state dict")
     ap.add_argument("--metric", default="embeddings", choices=["embeddings", "mask_iou"], help="association metric")
+    ap.add_argument("--input-format", default="bgr", choices=["bgr", "nv12", "i420"],
+                    help="frame format handed to the tracker (cfg.INPUT.FORMAT); nv12 / i420: the BGR frames are encoded on the "
+                         "host first (apse_uav_amd/synthetic.py), as a stand-in for a video decoder's output")
+    ap.add_argument("--yuv-matrix", default="cv601", choices=["cv601", "bt601", "bt709", "bt601-full", "bt709-full"],
+                    help="YUV -> BGR conversion of nv12 / i420 input (cfg.APSE.YUV_MATRIX)")
     args = ap.parse_args(argv)
     import torch
     from PIL import Image
@@ -64,6 +69,7 @@ def main(argv=None):
     from apse_uav_amd.engines.rcnn_tracker import RcnnTracker
     from apse_uav_amd.utils.mots_eval import MotsEvaluator, render_idmap
     from apse_uav_amd.utils.mots_evaluation import parse_mots_seqmap
+    from apse_uav_amd.synthetic import encoded_source
     from apse_uav_amd.weights import synthetic_association_state, synthetic_detector_state
     det = torch.load(args.detector_state) if args.detector_state else synthetic_detector_state(0)
     assoc = torch.load(args.association_state) if args.association_state else synthetic_association_state(1)
@@ -79,7 +85,11 @@ def main(argv=None):
         names = image_files(seq_path)
         first = np.asarray(Image.open(os.path.join(seq_path, names[0])).convert("RGB"))
         size = first.shape[:2]
-        tracker = RcnnTracker(setup_cfg(), size, assoc, association_metric=args.metric, detector_state=det)
+        cfg = setup_cfg()
+        cfg.INPUT.FORMAT = args.input_format.upper()
+        cfg.APSE.YUV_MATRIX = args.yuv_matrix
+        tracker = RcnnTracker(cfg, size, assoc, association_metric=args.metric, detector_state=det)
+        encode = encoded_source(lambda f: f, cfg.INPUT.FORMAT, args.yuv_matrix)
         out_dir = os.path.join(args.output, seq)
         if not args.no_write:
             os.makedirs(out_dir, exist_ok=True)
@@ -90,7 +100,7 @@ def main(argv=None):
         for name in names:
             print(name, end="\r")
             frame = np.ascontiguousarray(np.asarray(Image.open(os.path.join(seq_path, name)).convert("RGB"))[:, :, ::-1])
-            objects = tracker.next_frame(frame)                  # BGR, as cv2.imread gives the reference
+            objects = tracker.next_frame(encode(frame))          # BGR, as cv2.imread gives the reference (or its YUV encoding)
             frame_idx = tracker.frame_count - 1
             if evaluator is not None:
                 evaluator.add_frame(frame_idx, objects, size)
