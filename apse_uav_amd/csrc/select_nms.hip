@@ -10,10 +10,24 @@
 //                                                             nms_percat, rank_final
 //   FastRCNNOutputs.inference / fast_rcnn_inference_single_image -> box_candidates,
 //                                                             nms_percat, rank_final
+//
+// Every rule has one definition, shared by the three entries (FPN inference, C4 inference, FPN training):
+//   decode_box           Box2BoxTransform.apply_deltas + clip          (RPN anchors with weights 1, box head with its own)
+//   decode_selected      key -> pixel, anchor -> decode -> nonempty flag -> stores -> running max coordinate
+//   radix_select_kth     k-th smallest composite key of a head map too long for one sort
+//   block_ordered_pos    ordered compaction of a flagged list
+//   nms_matrix<MAX>      the suppression bit matrix: the only IoU in the file
+//   resolve_diag         the greedy step of every scan
+//   rank_merge<MAX>      final ranking of the kept lists (count_below: the binary search of every merge)
+// One NMS, three slot lengths: NMS_MAX (FPN and box head, one slot per category and image, matrix scanned from LDS),
+// C4_NMS_MAX (one slot per image) and TR_MAX (one per level and image), the long two scanned from HBM.
 #include "apse_kernels.h"
 
 #define TK_N 4096          // elements sorted per block in the top-k tournament
 #define NMS_MAX APSE_NMS_SLOT   // boxes per category (<= 1000 by construction); the host sizes the keep lists by the same constant
+#define C4_SORT_N 8192     // C4: keys sorted in LDS per image (>= rpn_pre_topk <= 6000)
+#define C4_NMS_MAX 6144    // C4: boxes of the image's one NMS slot (>= 6000)
+#define TR_MAX 2048        // training: keys of a level's list and boxes of its NMS slot (APSE_RPN_TRAIN_MAX_PRE_TOPK, include/apse_hip.h)
 
 __device__ __forceinline__ uint32_t mono_key(float f) {   // order-preserving float -> uint
     uint32_t u = __float_as_uint(f);
@@ -30,6 +44,13 @@ __device__ __forceinline__ uint64_t comp_key(float score, uint32_t idx) {
     return ((uint64_t)(~mono_key(score)) << 32) | idx;
 }
 __device__ __forceinline__ float comp_score(uint64_t k) { return mono_inv(~(uint32_t)(k >> 32)); }
+
+// Number of keys below `key` in the ascending list ko[0 .. n): the rank a merge adds for that list.
+__device__ __forceinline__ int count_below(const uint64_t* ko, int n, uint64_t key) {
+    int lo = 0, hi = n;
+    while (lo < hi) { const int mid = (lo + hi) >> 1; if (ko[mid] < key) lo = mid + 1; else hi = mid; }
+    return lo;
+}
 
 __device__ __forceinline__ uint64_t readlane64(uint64_t v, int l) {   // l must be wave-uniform
     const uint32_t lo = __builtin_amdgcn_readlane((int)(uint32_t)v, l);
@@ -97,6 +118,114 @@ __device__ __forceinline__ void block_bitonic_sort(uint64_t* a, int tid) {
     __syncthreads();
 }
 
+// ---------------------------------------------------------------- box decoding
+struct Box4 { float x0, y0, x1, y1; };
+
+// Box2BoxTransform.apply_deltas on one box (an anchor or a proposal) and four deltas d[0..3] with weights (wx, wy, ww, wh),
+// then Boxes.clip to the image.  Each product and sum is rounded on its own, in this order; with weight 1 the division is
+// exact.
+__device__ __forceinline__ Box4 decode_box(float bx0, float by0, float bx1, float by1, const float* __restrict__ d, float wx,
+                                           float wy, float ww, float wh, float scale_clamp, float img_h, float img_w) {
+    const float w = bx1 - bx0, h = by1 - by0;
+    const float cx = bx0 + 0.5f * w, cy = by0 + 0.5f * h;
+    float dx = d[0] / wx, dy = d[1] / wy, dw = d[2] / ww, dh = d[3] / wh;
+    dw = dw > scale_clamp ? scale_clamp : dw;
+    dh = dh > scale_clamp ? scale_clamp : dh;
+    const float pcx = dx * w + cx, pcy = dy * h + cy;
+    const float pw = expf(dw) * w, ph = expf(dh) * h;
+    Box4 q = {pcx - 0.5f * pw, pcy - 0.5f * ph, pcx + 0.5f * pw, pcy + 0.5f * ph};
+    q.x0 = fminf(fmaxf(q.x0, 0.f), img_w);
+    q.y0 = fminf(fmaxf(q.y0, 0.f), img_h);
+    q.x1 = fminf(fmaxf(q.x1, 0.f), img_w);
+    q.y1 = fminf(fmaxf(q.y1, 0.f), img_h);
+    return q;
+}
+__device__ __forceinline__ uint32_t max_coord_bits(const Box4& q) {   // all >= 0 after the clip: uint order = float order
+    return __float_as_uint(fmaxf(fmaxf(q.x0, q.x1), fmaxf(q.y0, q.y1)));
+}
+
+// One selected RPN anchor -> entry o of the decoded list.  The key's index is e = pixel * A + anchor on a map of width W whose
+// rows (`head`: this image's, `ld` floats each) hold A logits and then A x 4 deltas; the anchor is the cell anchor base[a] moved
+// to the pixel.  Decode with weights 1, nonempty flag, the score as the key carries it (a zero is +0 whatever its sign), and,
+// where the entry has one (`maxc`), the running max coordinate of the image's flagged boxes.
+template <int A>
+__device__ __forceinline__ void decode_selected(uint64_t key, int W, int stride, const float (*base)[4],
+                                                const float* __restrict__ head, int ld, float img_h, float img_w,
+                                                float scale_clamp, size_t o, float* __restrict__ boxes,
+                                                float* __restrict__ scores, int* __restrict__ valid, uint32_t* maxc) {
+    const uint32_t e = (uint32_t)key;
+    const int pix = e / A, an = e - pix * A;
+    const int y = pix / W, x = pix - y * W;
+    const float sx = (float)(x * stride), sy = (float)(y * stride);
+    const Box4 q = decode_box(sx + base[an][0], sy + base[an][1], sx + base[an][2], sy + base[an][3],
+                              head + (size_t)pix * ld + A + an * 4, 1.0f, 1.0f, 1.0f, 1.0f, scale_clamp, img_h, img_w);
+    const int ok = ((q.x1 - q.x0) > 0.f) && ((q.y1 - q.y0) > 0.f);
+    boxes[o * 4 + 0] = q.x0; boxes[o * 4 + 1] = q.y0; boxes[o * 4 + 2] = q.x1; boxes[o * 4 + 3] = q.y1;
+    scores[o] = comp_score(key);
+    valid[o] = ok;
+    if (maxc && ok) atomicMax(maxc, max_coord_bits(q));
+}
+
+// k-th smallest (1 <= k <= n) of the n distinct composite keys key_of(0 .. n-1), by a 1024-thread block: radix select, eight
+// bits per pass from the top, a histogram per wave in hist[16][256].  Returns a bound with exactly k keys <= it: the k-th key
+// itself after the last pass, or, as soon as the bin that holds it lies wholly inside the top k, that bin's last possible key
+// (random scores: after the four score bytes).  Ends on a barrier.
+template <class KeyOf>
+__device__ __forceinline__ uint64_t radix_select_kth(int n, int k, KeyOf key_of, unsigned* hist, int tid) {
+    __shared__ uint64_t prefix_s;
+    __shared__ unsigned rank_s;
+    __shared__ int done_s;
+    const int wave = tid >> 6;
+    if (tid == 0) { prefix_s = 0ull; rank_s = (unsigned)(k - 1); done_s = 0; }
+    __syncthreads();
+    for (int pass = 0; pass < 8; ++pass) {                 // the keys are distinct: the last pass ends with one key in the bin
+        const int shift = 56 - 8 * pass;
+        const uint64_t prefix = prefix_s;
+        for (int i = tid; i < 16 * 256; i += 1024) hist[i] = 0u;
+        __syncthreads();
+        for (int e = tid; e < n; e += 1024) {
+            const uint64_t key = key_of(e);
+            if (pass == 0 || (key >> (shift + 8)) == (prefix >> (shift + 8))) atomicAdd(&hist[wave * 256 + (int)((key >> shift) & 255u)], 1u);
+        }
+        __syncthreads();
+        if (tid < 256) {
+            unsigned t = 0;
+            for (int w = 0; w < 16; ++w) t += hist[w * 256 + tid];
+            hist[tid] = t;                                                 // wave 0's row now holds the totals
+        }
+        __syncthreads();
+        if (tid == 0) {
+            unsigned r = rank_s;
+            int d = 0;
+            for (; d < 255 && r >= hist[d]; ++d) r -= hist[d];
+            rank_s = r;
+            const uint64_t p = prefix | ((uint64_t)d << shift);
+            // the whole bin is inside the top k: every key up to the bin's last possible one is selected
+            if (r + 1u == hist[d]) { prefix_s = p | ((1ull << shift) - 1ull); done_s = 1; }
+            else prefix_s = p;
+        }
+        __syncthreads();
+        if (done_s) break;                                                 // block-uniform
+    }
+    return prefix_s;
+}
+
+// Ordered compaction by a 1024-thread block, one call per 1024 candidates: the position of this thread's flagged candidate =
+// the flagged ones of earlier calls (running total in wsum[16], zeroed by the caller before a barrier) + those of lower threads
+// in this call.  Ends on a barrier with the total advanced, so wsum[16] is the count after the last call.
+__device__ __forceinline__ int block_ordered_pos(bool f, int* wsum, int tid) {
+    const int lane = tid & 63, wave = tid >> 6;
+    const uint64_t bal = __ballot(f);
+    if (lane == 0) wsum[wave] = __popcll(bal);
+    __syncthreads();
+    int off = wsum[16];
+    for (int w = 0; w < wave; ++w) off += wsum[w];
+    __syncthreads();
+    if (tid == 0) { int t = wsum[16]; for (int w = 0; w < 16; ++w) t += wsum[w]; wsum[16] = t; }
+    __syncthreads();
+    return off + __popcll(bal & ((1ull << lane) - 1ull));
+}
+
 // ---------------------------------------------------------------- RPN top-k tournament
 // RpnLevel, RpnLevels, TopkJob: apse_kernels.h (filled by plan.hip)
 
@@ -144,19 +273,14 @@ __global__ __launch_bounds__(1024) void rpn_topk_stage(const RpnLevels* __restri
             int rank = tid;
             for (int o = 0; o < ns; ++o) {
                 if (o == s) continue;
-                int lo = 0, hi = cnt[o];
-                const uint64_t* ko = a + o * 1024;
-                while (lo < hi) { const int mid = (lo + hi) >> 1; if (ko[mid] < key) lo = mid + 1; else hi = mid; }
-                rank += lo;
+                rank += count_below(a + o * 1024, cnt[o], key);
             }
             if (rank < K) dst[rank] = key;
         }
     }
 }
 
-// Decode the selected anchors of every level: Box2BoxTransform.apply_deltas (weights 1,1,1,1),
-// clip to the image, nonempty flag, and the running max coordinate of the kept boxes.
-// out arrays are [B][5*pre_topk].  scores: the logit as the sort key carries it (a zero is +0 whatever its sign).
+// Decode the selected anchors of every level (decode_selected).  out arrays are [B][5*pre_topk].
 __global__ __launch_bounds__(256) void rpn_decode(const RpnLevels* __restrict__ Lp, const uint64_t* __restrict__ lists, int nslots,
                                                   const int* __restrict__ final_slot, float img_h, float img_w,
                                                   float scale_clamp, float* __restrict__ boxes, float* __restrict__ scores,
@@ -169,34 +293,8 @@ __global__ __launch_bounds__(256) void rpn_decode(const RpnLevels* __restrict__ 
     const size_t o = (size_t)b * 5 * pre_topk + (size_t)l * pre_topk + i;
     if (i >= lv.k || !((level_mask >> l) & 1)) { valid[o] = 0; scores[o] = 0.f; return; }
     const uint64_t key = lists[((size_t)b * nslots + final_slot[l]) * 1024 + i];
-    const uint32_t e = (uint32_t)key;
-    const float sc = comp_score(key);
-    const int pix = e / 3, an = e - pix * 3;
-    const int y = pix / lv.W, x = pix - y * lv.W;
-    const float sx = (float)(x * lv.stride), sy = (float)(y * lv.stride);
-    const float ax0 = sx + lv.base[an][0], ay0 = sy + lv.base[an][1];
-    const float ax1 = sx + lv.base[an][2], ay1 = sy + lv.base[an][3];
-    const float* d = lv.head + ((size_t)b * lv.H * lv.W + pix) * head_ld + 3 + an * 4;
-    const float w = ax1 - ax0, h = ay1 - ay0;
-    const float cx = ax0 + 0.5f * w, cy = ay0 + 0.5f * h;
-    float dx = d[0] / 1.0f, dy = d[1] / 1.0f, dw = d[2] / 1.0f, dh = d[3] / 1.0f;
-    dw = dw > scale_clamp ? scale_clamp : dw;
-    dh = dh > scale_clamp ? scale_clamp : dh;
-    const float pcx = dx * w + cx, pcy = dy * h + cy;
-    const float pw = expf(dw) * w, ph = expf(dh) * h;
-    float x0 = pcx - 0.5f * pw, y0 = pcy - 0.5f * ph, x1 = pcx + 0.5f * pw, y1 = pcy + 0.5f * ph;
-    x0 = fminf(fmaxf(x0, 0.f), img_w);
-    y0 = fminf(fmaxf(y0, 0.f), img_h);
-    x1 = fminf(fmaxf(x1, 0.f), img_w);
-    y1 = fminf(fmaxf(y1, 0.f), img_h);
-    const int ok = ((x1 - x0) > 0.f) && ((y1 - y0) > 0.f);
-    boxes[o * 4 + 0] = x0; boxes[o * 4 + 1] = y0; boxes[o * 4 + 2] = x1; boxes[o * 4 + 3] = y1;
-    scores[o] = sc;
-    valid[o] = ok;
-    if (ok) {
-        const float m = fmaxf(fmaxf(x0, x1), fmaxf(y0, y1));   // all >= 0 after the clip
-        atomicMax(maxc + b, __float_as_uint(m));
-    }
+    decode_selected<3>(key, lv.W, lv.stride, lv.base, lv.head + (size_t)b * lv.H * lv.W * head_ld, head_ld, img_h, img_w,
+                       scale_clamp, o, boxes, scores, valid, maxc + b);
 }
 
 // ---------------------------------------------------------------- per-category NMS
@@ -204,39 +302,48 @@ __global__ __launch_bounds__(256) void rpn_decode(const RpnLevels* __restrict__ 
 // cat_div ? e / cat_div : e % cat_mod.  Within a category, entries are ordered by (score desc,
 // entry index asc); IoU is evaluated on boxes shifted by cat * (max_coord + 1) in f32 (torchvision
 // batched_nms); `iou > thr` suppresses.  torchvision numbers the categories the call is given: with cat_mask != 0 (the RPN's
-// level mask) category c counts as the number of mask bits below c, with cat_mask == 0 as c itself.  Three launches:
-//   nms_prepare : one block per (category, image): ordered compaction + sort -> sorted shifted boxes
+// level mask) category c counts as the number of mask bits below c, with cat_mask == 0 as c itself.
+// One slot per list, of MAX boxes (NMS_MAX, C4_NMS_MAX or TR_MAX), and three launches:
+//   prepare     : one block per slot -> the list's boxes in order, shifted, with areas, entry ids and the count n
+//                 (nms_prepare / nms_prepare_list sort a category's entries; long_nms_prepare compacts a sorted list)
 //   nms_matrix  : 64x64 tiles of the upper-triangular suppression bit matrix, one wave each
-//   nms_scan    : one block per (category, image): greedy scan, 64 rows at a time
-// scratch per (image, category): entry[1024] int, box[4][1024] f32, area[1024] f32, mask[1024][16] u64, n.
-struct NmsScratch {
+//   scan        : one block per slot: greedy scan, 64 rows at a time (nms_scan with the matrix in LDS; the long slots from HBM)
+// A slot: entry[MAX] int, box[4][MAX] f32, area[MAX] f32, mask[MAX][MAX / 64] u64, n.
+struct NmsSlots {
     int* entry; float* box; float* area; uint64_t* mask; int* n;
 };
 
-// Sorted keys -> the category's slot of the NMS scratch: boxes shifted by cat * (max_coord + 1) in f32 (torchvision batched_nms
-// numbers the categories that are present in the call: `cat` is the slot's rank among them), their areas, entry ids, count.
+// Entry e of `boxes` -> row `pos` of a slot: shifted by `off`, with its area.
+template <int MAX>
+__device__ __forceinline__ void slot_put(const NmsSlots& S, size_t slot, int pos, uint32_t e, const float* __restrict__ boxes,
+                                         float off) {
+    float* bx = S.box + slot * 4 * MAX;
+    const float x0 = boxes[e * 4 + 0] + off, y0 = boxes[e * 4 + 1] + off;
+    const float x1 = boxes[e * 4 + 2] + off, y1 = boxes[e * 4 + 3] + off;
+    bx[pos] = x0; bx[MAX + pos] = y0; bx[2 * MAX + pos] = x1; bx[3 * MAX + pos] = y1;
+    S.area[slot * MAX + pos] = (x1 - x0) * (y1 - y0);
+    S.entry[slot * MAX + pos] = (int)e;
+}
+// The batched_nms shift of category `cat` (its rank among the categories present in the call): cat * (max_coord + 1) in f32.
+__device__ __forceinline__ float cat_shift(int cat, uint32_t maxc_bits) {
+    return (float)cat * (__uint_as_float(maxc_bits) + 1.0f);
+}
+
+// Sorted keys -> the category's slot.
 __device__ __forceinline__ void nms_store_sorted(const uint64_t* keys, int n, int cat, uint32_t maxc_bits,
-                                                 const float* __restrict__ boxes, NmsScratch S, size_t slot, int tid) {
-    const float off = (float)cat * (__uint_as_float(maxc_bits) + 1.0f);
-    float* bx = S.box + slot * 4 * NMS_MAX;
-    if (tid < n) {
-        const uint32_t e = (uint32_t)keys[tid];
-        const float x0 = boxes[e * 4 + 0] + off, y0 = boxes[e * 4 + 1] + off;
-        const float x1 = boxes[e * 4 + 2] + off, y1 = boxes[e * 4 + 3] + off;
-        bx[tid] = x0; bx[NMS_MAX + tid] = y0; bx[2 * NMS_MAX + tid] = x1; bx[3 * NMS_MAX + tid] = y1;
-        S.area[slot * NMS_MAX + tid] = (x1 - x0) * (y1 - y0);
-        S.entry[slot * NMS_MAX + tid] = (int)e;
-    }
+                                                 const float* __restrict__ boxes, NmsSlots S, size_t slot, int tid) {
+    const float off = cat_shift(cat, maxc_bits);
+    if (tid < n) slot_put<NMS_MAX>(S, slot, tid, (uint32_t)keys[tid], boxes, off);
     if (tid == 0) S.n[slot] = n;
 }
 
 __global__ __launch_bounds__(1024) void nms_prepare(const float* __restrict__ boxes, const float* __restrict__ scores,
                                                     const int* __restrict__ valid, int n_total, int cat_div, int cat_mod,
-                                                    const uint32_t* __restrict__ maxc, NmsScratch S, int ncat, int cat_mask,
+                                                    const uint32_t* __restrict__ maxc, NmsSlots S, int ncat, int cat_mask,
                                                     int presorted) {
     __shared__ uint64_t keys[NMS_MAX];
     __shared__ int wsum[17];
-    const int c = blockIdx.x, b = blockIdx.y, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int c = blockIdx.x, b = blockIdx.y, tid = threadIdx.x;
     boxes += (size_t)b * n_total * 4;
     scores += (size_t)b * n_total;
     valid += (size_t)b * n_total;
@@ -251,17 +358,10 @@ __global__ __launch_bounds__(1024) void nms_prepare(const float* __restrict__ bo
             const int cat = cat_div ? e / cat_div : e % cat_mod;
             f = (cat == c) && valid[e];
         }
-        const uint64_t bal = __ballot(f);
-        if (lane == 0) wsum[wave] = __popcll(bal);
-        __syncthreads();
-        int off = wsum[16];
-        for (int w = 0; w < wave; ++w) off += wsum[w];
-        const int pos = off + __popcll(bal & ((1ull << lane) - 1ull));
+        const int pos = block_ordered_pos(f, wsum, tid);
         if (f && pos < NMS_MAX) keys[pos] = comp_key(scores[e], (uint32_t)e);
-        __syncthreads();
-        if (tid == 0) { int t = wsum[16]; for (int w = 0; w < 16; ++w) t += wsum[w]; wsum[16] = t; }
-        __syncthreads();
     }
+    __syncthreads();
     int n = wsum[16];
     n = n < NMS_MAX ? n : NMS_MAX;
     // presorted: the entries of a category already come in (score desc, entry asc) order -- the RPN stage, whose entry
@@ -271,13 +371,36 @@ __global__ __launch_bounds__(1024) void nms_prepare(const float* __restrict__ bo
     nms_store_sorted(keys, n, cat_mask ? __popc(cat_mask & ((1 << c) - 1)) : c, maxc[b], boxes, S, slot, tid);
 }
 
+// Long lists (C4, training): grid (lists per image, B), list l of image b = entries l * pre .. l * pre + pre - 1 of `boxes`,
+// which are in (score desc, anchor asc) order already; the flagged ones keep it.  The category of a list is its rank among the
+// lists of cat_mask; C4's one list has no max coordinate (maxc null) and shift 0.
+template <int MAX>
+__global__ __launch_bounds__(1024) void long_nms_prepare(const float* __restrict__ boxes, const int* __restrict__ valid, int pre,
+                                                         const uint32_t* __restrict__ maxc, int cat_mask, NmsSlots S) {
+    __shared__ int wsum[17];
+    const int l = blockIdx.x, nl = gridDim.x, b = blockIdx.y, tid = threadIdx.x;
+    const size_t slot = (size_t)b * nl + l;
+    boxes += (size_t)b * nl * pre * 4;
+    valid += (size_t)b * nl * pre;
+    const float off = maxc ? cat_shift(__popc(cat_mask & ((1 << l) - 1)), maxc[b]) : 0.f;
+    if (tid == 0) wsum[16] = 0;
+    __syncthreads();
+    for (int base = 0; base < pre; base += 1024) {
+        const int i = base + tid, e = l * pre + i;
+        const bool f = i < pre && valid[e];
+        const int pos = block_ordered_pos(f, wsum, tid);
+        if (f && pos < MAX) slot_put<MAX>(S, slot, pos, (uint32_t)e, boxes, off);
+    }
+    if (tid == 0) S.n[slot] = wsum[16] < MAX ? wsum[16] : MAX;
+}
+
 // Wide box inference (K > 8): the same as nms_prepare, but category c of image b reads only its own candidate list
 // (written by box_candidates_wide: clist[b][c][0 .. ccnt[b][c]) = entry ids, in arrival order) instead of scanning all P * K
 // entries.  The sort makes the arrival order irrelevant (the keys are distinct).  The block leaves its count at zero for the
 // next forward.
 __global__ __launch_bounds__(1024) void nms_prepare_list(const float* __restrict__ boxes, const float* __restrict__ scores,
                                                          int n_total, const int* __restrict__ clist, int* __restrict__ ccnt,
-                                                         int list_stride, const uint32_t* __restrict__ maxc, NmsScratch S,
+                                                         int list_stride, const uint32_t* __restrict__ maxc, NmsSlots S,
                                                          int ncat) {
     __shared__ uint64_t keys[NMS_MAX];
     const int c = blockIdx.x, b = blockIdx.y, tid = threadIdx.x;
@@ -296,26 +419,30 @@ __global__ __launch_bounds__(1024) void nms_prepare_list(const float* __restrict
     nms_store_sorted(keys, n, c, maxc[b], boxes, S, slot, tid);
 }
 
-// grid (16 column chunks, 16 row chunks, ncat*B), 64 threads: thread t owns row 64*ic + t.
-__global__ __launch_bounds__(64) void nms_matrix(NmsScratch S, float thr) {
+// grid (MAX / 64 column chunks, MAX / 64 row chunks, slots), 64 threads: thread t owns row 64*ic + t of a tile on or right of
+// the diagonal.  A live tile's rows i >= n (i <= MAX - 1: inside the slot) get a zero word that no scan reads: every scan
+// stops at row n.  The store stays because with it the 1024 tile, the one on the frame's path, is the code it has always
+// been; it costs the last row chunk's tiles at most 63 words each.
+template <int MAX>
+__global__ __launch_bounds__(64) void nms_matrix(NmsSlots S, float thr) {
     __shared__ float cb[5][64];
     const int jc = blockIdx.x, ic = blockIdx.y;
     const size_t slot = blockIdx.z;
     const int n = S.n[slot];
     if (jc < ic || 64 * ic >= n || 64 * jc >= n) return;
     const int t = threadIdx.x;
-    const float* bx = S.box + slot * 4 * NMS_MAX;
-    const float* ar = S.area + slot * NMS_MAX;
+    const float* bx = S.box + slot * 4 * MAX;
+    const float* ar = S.area + slot * MAX;
     const int j = 64 * jc + t;
     if (j < n) {
-        cb[0][t] = bx[j]; cb[1][t] = bx[NMS_MAX + j]; cb[2][t] = bx[2 * NMS_MAX + j]; cb[3][t] = bx[3 * NMS_MAX + j];
+        cb[0][t] = bx[j]; cb[1][t] = bx[MAX + j]; cb[2][t] = bx[2 * MAX + j]; cb[3][t] = bx[3 * MAX + j];
         cb[4][t] = ar[j];
     }
     __syncthreads();
     const int i = 64 * ic + t;
     uint64_t bits = 0;
     if (i < n) {
-        const float ix0 = bx[i], iy0 = bx[NMS_MAX + i], ix1 = bx[2 * NMS_MAX + i], iy1 = bx[3 * NMS_MAX + i];
+        const float ix0 = bx[i], iy0 = bx[MAX + i], ix1 = bx[2 * MAX + i], iy1 = bx[3 * MAX + i];
         const float ia = ar[i];
         const int jend = (n - 64 * jc) < 64 ? (n - 64 * jc) : 64;
         for (int jj = 0; jj < jend; ++jj) {
@@ -328,7 +455,7 @@ __global__ __launch_bounds__(64) void nms_matrix(NmsScratch S, float thr) {
             if (ovr > thr) bits |= (1ull << jj);
         }
     }
-    S.mask[(slot * NMS_MAX + i) * 16 + jc] = bits;
+    S.mask[(slot * MAX + i) * (MAX / 64) + jc] = bits;
 }
 
 __device__ __forceinline__ uint64_t wave_or64(uint64_t v) {
@@ -336,9 +463,25 @@ __device__ __forceinline__ uint64_t wave_or64(uint64_t v) {
     return v;
 }
 
+// The greedy step, by wave 0 of a scan: lane l holds the diagonal word of row l of a 64-row chunk (`diag`: which later rows of
+// the chunk row l suppresses), `rem` the rows that kept rows of earlier chunks removed.  Returns the rows kept (wave-uniform).
+// Only rows that are still alive are visited: the next kept row is the lowest clear bit of `rem` above the last one (a removed
+// row never suppresses anything), so the loop runs once per KEPT row, not per row.
+__device__ __forceinline__ uint64_t resolve_diag(uint64_t diag, uint64_t rem, int rows_here) {
+    uint64_t keepbits = 0;
+    uint64_t alive = ~rem & (rows_here == 64 ? ~0ull : ((1ull << rows_here) - 1ull));
+    while (alive) {
+        const int r = __builtin_ctzll(alive);
+        keepbits |= (1ull << r);
+        rem |= readlane64(diag, r) | (1ull << r);
+        alive &= ~rem;
+    }
+    return keepbits;
+}
+
 // Greedy scan, one block per (category, image).  Wave 0 resolves the 64 rows of a chunk on the
 // diagonal word (scalar readlanes), then wave w ORs the kept rows' word w into the removed bitmap.
-__global__ __launch_bounds__(1024) void nms_scan(NmsScratch S, int* __restrict__ keep_idx, int* __restrict__ keep_cnt) {
+__global__ __launch_bounds__(1024) void nms_scan(NmsSlots S, int* __restrict__ keep_idx, int* __restrict__ keep_cnt) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
     uint64_t* mask = reinterpret_cast<uint64_t*>(smem);          // [n][16]
     __shared__ uint64_t removed[16];
@@ -362,17 +505,7 @@ __global__ __launch_bounds__(1024) void nms_scan(NmsScratch S, int* __restrict__
         if (wave == 0) {
             const int row = 64 * ch + lane;
             const uint64_t diag = row < n ? mask[(size_t)row * 16 + ch] : 0ull;
-            uint64_t rem = removed[ch];
-            uint64_t keepbits = 0;
-            // visit only rows that are still alive: the next kept row is the lowest clear bit of `rem` above the
-            // last one (a removed row never suppresses anything), so the loop runs once per KEPT row, not per row
-            uint64_t alive = ~rem & (rows_here == 64 ? ~0ull : ((1ull << rows_here) - 1ull));
-            while (alive) {
-                const int r = __builtin_ctzll(alive);
-                keepbits |= (1ull << r);
-                rem |= readlane64(diag, r) | (1ull << r);
-                alive &= ~rem;
-            }
+            const uint64_t keepbits = resolve_diag(diag, removed[ch], rows_here);
             if ((keepbits >> lane) & 1ull) out[kept + __popcll(keepbits & ((1ull << lane) - 1ull))] = entry[row];
             kept += __popcll(keepbits);
             if (lane == 0) keepbits_s = keepbits;
@@ -390,11 +523,94 @@ __global__ __launch_bounds__(1024) void nms_scan(NmsScratch S, int* __restrict__
     if (tid == 0) keep_cnt[slot] = kept;
 }
 
-// Final ranking by merging: each category's kept list is already sorted by (score desc, entry asc),
+// Greedy scan of a long slot by one 1024-thread block, the bit matrix read from HBM (only words on and right of the diagonal
+// of rows < n: those nms_matrix wrote).  Wave 0 resolves the 64 rows of a chunk on the diagonal word; then the waves OR the
+// kept rows' words right of the diagonal into the removed bitmap.  The scan ends as soon as `post` rows are kept: the kept
+// list is in processing order, so that is keep[:post] of the full scan.  keep[0 .. post) (LDS or HBM) receives the kept
+// entries; returns their count (block-uniform, <= post), behind a barrier.
+template <int MAX>
+__device__ __forceinline__ int long_nms_scan(const NmsSlots& S, size_t slot, int post, int* keep) {
+    constexpr int WORDS = MAX / 64;
+    __shared__ uint64_t removed[WORDS];
+    __shared__ uint64_t keepbits_s;
+    __shared__ int kept_s;
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int n = S.n[slot];
+    const int nw = (n + 63) >> 6;
+    const uint64_t* gm = S.mask + slot * MAX * WORDS;
+    const int* entry = S.entry + slot * MAX;
+    for (int i = tid; i < WORDS; i += 1024) removed[i] = 0ull;
+    if (tid == 0) kept_s = 0;
+    __syncthreads();
+    int kept = 0;                                   // wave 0's running count
+    for (int ch = 0; ch < nw; ++ch) {
+        const int rows_here = (n - 64 * ch) < 64 ? (n - 64 * ch) : 64;
+        if (wave == 0) {
+            const int row = 64 * ch + lane;
+            const uint64_t diag = row < n ? gm[(size_t)row * WORDS + ch] : 0ull;
+            const uint64_t keepbits = resolve_diag(diag, removed[ch], rows_here);
+            const int pos = kept + __popcll(keepbits & ((1ull << lane) - 1ull));
+            if (((keepbits >> lane) & 1ull) && pos < post) keep[pos] = entry[row];
+            kept += __popcll(keepbits);
+            if (lane == 0) { keepbits_s = keepbits; kept_s = kept; }
+        }
+        __syncthreads();
+        if (kept_s >= post) break;                  // block-uniform
+        const uint64_t kb = keepbits_s;
+        for (int w = ch + 1 + wave; w < nw; w += 16) {
+            uint64_t v = 0;
+            if (lane < rows_here && ((kb >> lane) & 1ull)) v = gm[(size_t)(64 * ch + lane) * WORDS + w];
+            v = wave_or64(v);
+            if (lane == 0) removed[w] |= v;
+        }
+        __syncthreads();
+    }
+    return kept_s < post ? kept_s : post;
+}
+
+// C4: grid (B), slot = image.  The kept list stays in LDS and becomes the proposals [B][post]: boxes, scores, entry = rank in
+// the decoded list; zeros and -1 past the count; the per-image count.  post <= 1024.
+__global__ __launch_bounds__(1024) void long_nms_scan_proposals(NmsSlots S, const float* __restrict__ dboxes,
+                                                                const float* __restrict__ dscores, int pre, int post,
+                                                                float* __restrict__ out_boxes, float* __restrict__ out_scores,
+                                                                int* __restrict__ out_entry, int* __restrict__ out_count) {
+    __shared__ int keep[1024];
+    const int b = blockIdx.x, tid = threadIdx.x;
+    const int cnt = long_nms_scan<C4_NMS_MAX>(S, b, post, keep);
+    dboxes += (size_t)b * pre * 4;
+    dscores += (size_t)b * pre;
+    for (int i = tid; i < post; i += 1024) {
+        float* ob = out_boxes + ((size_t)b * post + i) * 4;
+        if (i < cnt) {
+            const int e = keep[i];
+            ob[0] = dboxes[e * 4 + 0]; ob[1] = dboxes[e * 4 + 1]; ob[2] = dboxes[e * 4 + 2]; ob[3] = dboxes[e * 4 + 3];
+            out_scores[(size_t)b * post + i] = dscores[e];
+            out_entry[(size_t)b * post + i] = e;
+        } else {
+            ob[0] = ob[1] = ob[2] = ob[3] = 0.f;
+            out_scores[(size_t)b * post + i] = 0.f;
+            out_entry[(size_t)b * post + i] = -1;
+        }
+    }
+    if (tid == 0) out_count[b] = cnt;
+}
+
+// Training: grid (5, B), slot = image * 5 + level.  The kept list goes to keep_idx [slot][TR_MAX] for rank_merge: an element
+// behind `post` others of its own sorted list has a merged rank >= post, so the merge never misses what the early stop left out.
+__global__ __launch_bounds__(1024) void long_nms_scan_keep(NmsSlots S, int post, int* __restrict__ keep_idx,
+                                                           int* __restrict__ keep_cnt) {
+    const size_t slot = (size_t)blockIdx.y * gridDim.x + blockIdx.x;
+    const int cnt = long_nms_scan<TR_MAX>(S, slot, post, keep_idx + slot * TR_MAX);
+    if (threadIdx.x == 0) keep_cnt[slot] = cnt;
+}
+
+// Final ranking by merging: each category's kept list (up to MAX entries) is already sorted by (score desc, entry asc),
 // so the global rank of an element is its own position plus, for every other list, the number of
 // keys that precede it (binary search).  No barriers after the load; first K ranks are written.
 // Grid (image, category): every block loads all lists of its image (the searches need them) and ranks the elements of ITS
 // list -- the ncat x 4 dependent binary searches of one block were 8 of this launch's 21 us at batch 1.
+// ncat <= 8; ncat * MAX keys of dynamic LDS (64 KiB for eight lists of NMS_MAX, 80 KiB for the five of TR_MAX).
+template <int MAX>
 __global__ __launch_bounds__(1024) void rank_merge(const float* __restrict__ boxes, const float* __restrict__ scores,
                                                    int n_total, const int* __restrict__ keep_idx,
                                                    const int* __restrict__ keep_cnt, int ncat, int K,
@@ -402,7 +618,7 @@ __global__ __launch_bounds__(1024) void rank_merge(const float* __restrict__ box
                                                    int* __restrict__ out_entry, int* __restrict__ out_count,
                                                    uint32_t* __restrict__ zero_word) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
-    uint64_t* keys = reinterpret_cast<uint64_t*>(smem);      // [ncat][NMS_MAX]
+    uint64_t* keys = reinterpret_cast<uint64_t*>(smem);      // [ncat][MAX]
     const int b = blockIdx.x, c = blockIdx.y, tid = threadIdx.x;
     if (zero_word && c == 0 && tid == 0) zero_word[b] = 0u;      // next stage's max-coordinate cell
     __shared__ int cnt[8];
@@ -412,21 +628,25 @@ __global__ __launch_bounds__(1024) void rank_merge(const float* __restrict__ box
     __syncthreads();
     int total = 0;
     for (int o = 0; o < ncat; ++o) {
-        const int* src = keep_idx + ((size_t)b * ncat + o) * NMS_MAX;
-        if (tid < cnt[o]) { const int e = src[tid]; keys[o * NMS_MAX + tid] = comp_key(scores[e], (uint32_t)e); }
+        const int* src = keep_idx + ((size_t)b * ncat + o) * MAX;
+#pragma unroll
+        for (int s = 0; s < MAX / 1024; ++s) {               // thread t owns positions t, t + 1024, .. of every list
+            const int i = tid + 1024 * s;
+            if (i < cnt[o]) { const int e = src[i]; keys[o * MAX + i] = comp_key(scores[e], (uint32_t)e); }
+        }
         total += cnt[o];
     }
     __syncthreads();
     const int nout = total < K ? total : K;
-    if (tid < cnt[c]) {
-        const uint64_t key = keys[c * NMS_MAX + tid];
-        int rank = tid;
+#pragma unroll
+    for (int s = 0; s < MAX / 1024; ++s) {
+        const int i = tid + 1024 * s;
+        if (i >= cnt[c]) continue;
+        const uint64_t key = keys[c * MAX + i];
+        int rank = i;
         for (int o = 0; o < ncat; ++o) {
             if (o == c) continue;
-            int lo = 0, hi = cnt[o];
-            const uint64_t* ko = keys + o * NMS_MAX;
-            while (lo < hi) { const int mid = (lo + hi) >> 1; if (ko[mid] < key) lo = mid + 1; else hi = mid; }
-            rank += lo;
+            rank += count_below(keys + o * MAX, cnt[o], key);
         }
         if (rank < K) {
             const uint32_t e = (uint32_t)key;
@@ -467,35 +687,24 @@ __global__ __launch_bounds__(256) void box_candidates(const float* __restrict__ 
     float ex[8], sum = 0.f;
     for (int k = 0; k <= K; ++k) { ex[k] = expf(lg[k] - mx); sum += ex[k]; }
     const float* pb = props + roi * 4;
-    const float w = pb[2] - pb[0], h = pb[3] - pb[1];
-    const float cx = pb[0] + 0.5f * w, cy = pb[1] + 0.5f * h;
+    const float px0 = pb[0], py0 = pb[1], px1 = pb[2], py1 = pb[3];
     for (int k = 0; k < K; ++k) {
         const size_t slot = roi * K + k;
         const float p = ex[k] / sum;
         if (probs_out) probs_out[roi * (K + 1) + k] = p;
-        const float* d = lg + (K + 1) + 4 * k;
-        float dx = d[0] / wx, dy = d[1] / wy, dw = d[2] / ww, dh = d[3] / wh;
-        dw = dw > scale_clamp ? scale_clamp : dw;
-        dh = dh > scale_clamp ? scale_clamp : dh;
-        const float pcx = dx * w + cx, pcy = dy * h + cy;
-        const float pw = expf(dw) * w, ph = expf(dh) * h;
-        float x0 = pcx - 0.5f * pw, y0 = pcy - 0.5f * ph, x1 = pcx + 0.5f * pw, y1 = pcy + 0.5f * ph;
-        x0 = fminf(fmaxf(x0, 0.f), img_w);
-        y0 = fminf(fmaxf(y0, 0.f), img_h);
-        x1 = fminf(fmaxf(x1, 0.f), img_w);
-        y1 = fminf(fmaxf(y1, 0.f), img_h);
+        const Box4 q = decode_box(px0, py0, px1, py1, lg + (K + 1) + 4 * k, wx, wy, ww, wh, scale_clamp, img_h, img_w);
         const int ok = live && (p > thresh);
-        cboxes[slot * 4 + 0] = x0; cboxes[slot * 4 + 1] = y0; cboxes[slot * 4 + 2] = x1; cboxes[slot * 4 + 3] = y1;
+        cboxes[slot * 4 + 0] = q.x0; cboxes[slot * 4 + 1] = q.y0; cboxes[slot * 4 + 2] = q.x1; cboxes[slot * 4 + 3] = q.y1;
         cscores[slot] = p;
         cvalid[slot] = ok;
-        if (ok) atomicMax(maxc + b, __float_as_uint(fmaxf(fmaxf(x0, x1), fmaxf(y0, y1))));
+        if (ok) atomicMax(maxc + b, max_coord_bits(q));
     }
     if (probs_out) probs_out[roi * (K + 1) + K] = ex[K] / sum;
 }
 
 // Wide form (K > 8, up to 127 classes): one wave per ROI, lane l owns logits l and l + 64 (class k, or the background at k = K).
 // Softmax max and sum are wave reductions (xor butterflies: every lane ends with the same bits, whatever the launch), then each
-// lane decodes, clips and filters its classes exactly as box_candidates does.  Same outputs in the same layout (slot
+// lane decodes (decode_box), clips and filters its classes.  The outputs and layout of box_candidates (slot
 // roi * K + k, probs_out, maxc), plus a class-major list of the passing entries: clist[b][k][pos] = r * K + k with pos from
 // ccnt[b][k] (arrival order; nms_prepare_list sorts, and zeroes the counts again).
 __global__ __launch_bounds__(256) void box_candidates_wide(const float* __restrict__ pred, int ld, int K,
@@ -519,8 +728,7 @@ __global__ __launch_bounds__(256) void box_candidates_wide(const float* __restri
     float sum = e0 + e1;
     for (int o = 32; o > 0; o >>= 1) sum += __shfl_xor(sum, o);
     const float* pb = props + roi * 4;
-    const float w = pb[2] - pb[0], h = pb[3] - pb[1];
-    const float cx = pb[0] + 0.5f * w, cy = pb[1] + 0.5f * h;
+    const float px0 = pb[0], py0 = pb[1], px1 = pb[2], py1 = pb[3];
     uint32_t m = 0u;
     bool any = false;
 #pragma unroll
@@ -532,23 +740,13 @@ __global__ __launch_bounds__(256) void box_candidates_wide(const float* __restri
         if (probs_out) probs_out[roi * (K + 1) + k] = p;
         if (k == K) continue;                            // background: probability only
         const size_t slot = roi * K + k;
-        const float* d = lg + (K + 1) + 4 * k;
-        float dx = d[0] / wx, dy = d[1] / wy, dw = d[2] / ww, dh = d[3] / wh;
-        dw = dw > scale_clamp ? scale_clamp : dw;
-        dh = dh > scale_clamp ? scale_clamp : dh;
-        const float pcx = dx * w + cx, pcy = dy * h + cy;
-        const float pw = expf(dw) * w, ph = expf(dh) * h;
-        float x0 = pcx - 0.5f * pw, y0 = pcy - 0.5f * ph, x1 = pcx + 0.5f * pw, y1 = pcy + 0.5f * ph;
-        x0 = fminf(fmaxf(x0, 0.f), img_w);
-        y0 = fminf(fmaxf(y0, 0.f), img_h);
-        x1 = fminf(fmaxf(x1, 0.f), img_w);
-        y1 = fminf(fmaxf(y1, 0.f), img_h);
+        const Box4 q = decode_box(px0, py0, px1, py1, lg + (K + 1) + 4 * k, wx, wy, ww, wh, scale_clamp, img_h, img_w);
         const int ok = live && (p > thresh);
-        cboxes[slot * 4 + 0] = x0; cboxes[slot * 4 + 1] = y0; cboxes[slot * 4 + 2] = x1; cboxes[slot * 4 + 3] = y1;
+        cboxes[slot * 4 + 0] = q.x0; cboxes[slot * 4 + 1] = q.y0; cboxes[slot * 4 + 2] = q.x1; cboxes[slot * 4 + 3] = q.y1;
         cscores[slot] = p;
         cvalid[slot] = ok;
         if (ok) {
-            const uint32_t mk = __float_as_uint(fmaxf(fmaxf(x0, x1), fmaxf(y0, y1)));   // >= 0 after the clip: uint order = float order
+            const uint32_t mk = max_coord_bits(q);
             m = mk > m ? mk : m;
             any = true;
             const size_t ci = (size_t)b * K + k;
@@ -620,268 +818,57 @@ __global__ __launch_bounds__(1024) void rank_sort_wide(const float* __restrict__
     if (tid == 0) out_count[b] = nout;
 }
 
-// ---------------------------------------------------------------- C4: single-level RPN selection and long-list NMS
+// ---------------------------------------------------------------- long lists: C4 and training-time selection
 // detectron2's C4 RPN (Res5ROIHeads models) runs on one stride-16 map with 15 anchors per cell and keeps the top
-// PRE_NMS_TOPK_TEST = 6000 logits of up to H * W * 15 (59220 at 47 x 84) before an NMS over that one list.  The FPN
-// tournament (4096-key chunks, 1024-slot lists) and the 1024-box NMS slots do not reach that far, so this path has its own:
-//   c4_rpn_select : one block per image.  Radix select of the k-th smallest composite key (comp_key: score descending,
-//                   anchor index ascending -- distinct keys, so "key <= kth" is exactly k elements), compaction of those
-//                   k into LDS, one bitonic sort of <= 8192 keys, then Box2BoxTransform decode + clip + nonempty flag.
-//   c4_nms_prepare: ordered compaction of the valid decoded boxes (they arrive sorted) into the long NMS slot.
-//   c4_nms_matrix : 64 x 64 tiles of the suppression bit matrix (the same IoU arithmetic as nms_matrix).
-//   c4_nms_scan   : greedy scan, 64 rows per step, the bit matrix read from HBM; stops once post_topk boxes are kept
-//                   (keep[:post_topk] of the full scan), then writes the proposals.
-#define C4_SORT_N 8192      // keys sorted in LDS per image (>= rpn_pre_topk <= 6000)
-#define C4_NMS_MAX 6144     // boxes of the long NMS slot (>= 6000)
-#define C4_NMS_WORDS (C4_NMS_MAX / 64)
+// PRE_NMS_TOPK_TEST = 6000 logits of up to H * W * 15 (59220 at 47 x 84) before an NMS over that one list; training keeps
+// PRE_NMS_TOPK_TRAIN = 2000 per FPN level (up to TR_MAX) and POST_NMS_TOPK_TRAIN = 1000 of the merge.  The tournament's
+// 4096-key chunks and 1024-key lists do not reach that far, so one block selects a whole list: radix_select_kth (the keys are
+// distinct, so "key <= bound" is exactly k elements), compaction of those k into LDS, one bitonic sort, decode_selected on the
+// sorted keys.  Then the NMS above on a long slot -- long_nms_prepare, nms_matrix, long_nms_scan -- and, for the five lists of
+// training, rank_merge<TR_MAX>.
 
-
+// C4: one block per image, n = H * W * 15 keys -> dec_* [B][pre] (k = min(pre, n) live entries, the rest flagged off).
 __global__ __launch_bounds__(1024) void c4_rpn_select(const C4Rpn R, float img_h, float img_w, float scale_clamp,
                                                      float* __restrict__ boxes, float* __restrict__ scores,
                                                      int* __restrict__ valid, int pre) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
     uint64_t* a = reinterpret_cast<uint64_t*>(smem);                    // [C4_SORT_N]
     unsigned* hist = reinterpret_cast<unsigned*>(smem + C4_SORT_N * 8);  // [16 waves][256]
-    __shared__ uint64_t prefix_s;
-    __shared__ unsigned rank_s, fill_s;
-    const int b = blockIdx.x, tid = threadIdx.x, wave = tid >> 6;
+    __shared__ unsigned fill_s;
+    const int b = blockIdx.x, tid = threadIdx.x;
     const float* head = R.head + (size_t)b * R.H * R.W * R.ld;
     const int n = R.n, k = R.k;
     auto key_of = [&](int e) -> uint64_t {
         const int pix = e / 15, an = e - pix * 15;
         return comp_key(head[(size_t)pix * R.ld + an], (uint32_t)e);
     };
-    // radix select, 8 bits per pass from the top: after pass p the top 8 (p + 1) bits of the k-th smallest key are known
-    if (tid == 0) { prefix_s = 0; rank_s = (unsigned)(k - 1); }
-    for (int pass = 0; pass < 8; ++pass) {
-        const int shift = 56 - 8 * pass;
-        for (int i = tid; i < 16 * 256; i += 1024) hist[i] = 0u;
-        __syncthreads();
-        const uint64_t prefix = prefix_s;
-        for (int e = tid; e < n; e += 1024) {
-            const uint64_t key = key_of(e);
-            if (pass == 0 || (key >> (shift + 8)) == (prefix >> (shift + 8))) atomicAdd(&hist[wave * 256 + (int)((key >> shift) & 255u)], 1u);
-        }
-        __syncthreads();
-        if (tid < 256) {
-            unsigned t = 0;
-            for (int w = 0; w < 16; ++w) t += hist[w * 256 + tid];
-            hist[tid] = t;                                                 // wave 0's row now holds the totals
-        }
-        __syncthreads();
-        if (tid == 0) {
-            unsigned r = rank_s;
-            int d = 0;
-            for (; d < 255 && r >= hist[d]; ++d) r -= hist[d];
-            rank_s = r;
-            prefix_s = prefix | ((uint64_t)d << shift);
-            fill_s = 0u;
-        }
-        __syncthreads();
-    }
-    const uint64_t kth = prefix_s;
+    if (tid == 0) fill_s = 0u;
+    const uint64_t kth = radix_select_kth(n, k, key_of, hist, tid);
     for (int i = tid; i < C4_SORT_N; i += 1024) a[i] = ~0ull;
     __syncthreads();
     for (int e = tid; e < n; e += 1024) {
         const uint64_t key = key_of(e);
-        if (key <= kth) a[atomicAdd(&fill_s, 1u)] = key;                   // exactly k keys (distinct keys)
+        if (key <= kth) a[atomicAdd(&fill_s, 1u)] = key;                   // exactly k <= pre < C4_SORT_N keys
     }
     __syncthreads();
     block_bitonic_sort<C4_SORT_N / 1024>(a, tid);
     for (int i = tid; i < pre; i += 1024) {
         const size_t o = (size_t)b * pre + i;
         if (i >= k) { valid[o] = 0; scores[o] = 0.f; continue; }
-        const uint64_t key = a[i];
-        const uint32_t e = (uint32_t)key;
-        const int pix = e / 15, an = e - pix * 15;
-        const int y = pix / R.W, x = pix - y * R.W;
-        const float sx = (float)(x * R.stride), sy = (float)(y * R.stride);
-        const float ax0 = sx + R.base[an][0], ay0 = sy + R.base[an][1];
-        const float ax1 = sx + R.base[an][2], ay1 = sy + R.base[an][3];
-        const float* d = head + (size_t)pix * R.ld + 15 + an * 4;
-        const float w = ax1 - ax0, h = ay1 - ay0;
-        const float cx = ax0 + 0.5f * w, cy = ay0 + 0.5f * h;
-        float dx = d[0] / 1.0f, dy = d[1] / 1.0f, dw = d[2] / 1.0f, dh = d[3] / 1.0f;
-        dw = dw > scale_clamp ? scale_clamp : dw;
-        dh = dh > scale_clamp ? scale_clamp : dh;
-        const float pcx = dx * w + cx, pcy = dy * h + cy;
-        const float pw = expf(dw) * w, ph = expf(dh) * h;
-        float x0 = pcx - 0.5f * pw, y0 = pcy - 0.5f * ph, x1 = pcx + 0.5f * pw, y1 = pcy + 0.5f * ph;
-        x0 = fminf(fmaxf(x0, 0.f), img_w);
-        y0 = fminf(fmaxf(y0, 0.f), img_h);
-        x1 = fminf(fmaxf(x1, 0.f), img_w);
-        y1 = fminf(fmaxf(y1, 0.f), img_h);
-        boxes[o * 4 + 0] = x0; boxes[o * 4 + 1] = y0; boxes[o * 4 + 2] = x1; boxes[o * 4 + 3] = y1;
-        scores[o] = comp_score(key);
-        valid[o] = ((x1 - x0) > 0.f) && ((y1 - y0) > 0.f);
+        decode_selected<15>(a[i], R.W, R.stride, R.base, head, R.ld, img_h, img_w, scale_clamp, o, boxes, scores, valid, nullptr);
     }
 }
 
-// One long NMS slot per image: box [4][C4_NMS_MAX], area, entry, n; mask [C4_NMS_MAX][C4_NMS_WORDS] u64.
-struct C4Nms { float* box; float* area; int* entry; int* n; uint64_t* mask; };
-
-// The decoded list is in (score desc, anchor asc) order already; the valid boxes keep that order (a single category: the
-// batched_nms offset is 0 * (max + 1) = 0, so the boxes go in unshifted).
-__global__ __launch_bounds__(1024) void c4_nms_prepare(const float* __restrict__ boxes, const int* __restrict__ valid, int pre,
-                                                      C4Nms S) {
-    __shared__ int wsum[17];
-    const int b = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    boxes += (size_t)b * pre * 4;
-    valid += (size_t)b * pre;
-    float* bx = S.box + (size_t)b * 4 * C4_NMS_MAX;
-    if (tid == 0) wsum[16] = 0;
-    __syncthreads();
-    for (int base = 0; base < pre; base += 1024) {
-        const int e = base + tid;
-        const bool f = e < pre && valid[e];
-        const uint64_t bal = __ballot(f);
-        if (lane == 0) wsum[wave] = __popcll(bal);
-        __syncthreads();
-        int off = wsum[16];
-        for (int w = 0; w < wave; ++w) off += wsum[w];
-        const int pos = off + __popcll(bal & ((1ull << lane) - 1ull));
-        if (f && pos < C4_NMS_MAX) {
-            const float x0 = boxes[e * 4 + 0], y0 = boxes[e * 4 + 1], x1 = boxes[e * 4 + 2], y1 = boxes[e * 4 + 3];
-            bx[pos] = x0; bx[C4_NMS_MAX + pos] = y0; bx[2 * C4_NMS_MAX + pos] = x1; bx[3 * C4_NMS_MAX + pos] = y1;
-            S.area[(size_t)b * C4_NMS_MAX + pos] = (x1 - x0) * (y1 - y0);
-            S.entry[(size_t)b * C4_NMS_MAX + pos] = e;
-        }
-        __syncthreads();
-        if (tid == 0) { int t = wsum[16]; for (int w = 0; w < 16; ++w) t += wsum[w]; wsum[16] = t; }
-        __syncthreads();
-    }
-    if (tid == 0) S.n[b] = wsum[16] < C4_NMS_MAX ? wsum[16] : C4_NMS_MAX;
-}
-
-// grid (C4_NMS_WORDS column chunks, C4_NMS_WORDS row chunks, B), 64 threads: thread t owns row 64 * ic + t.
-__global__ __launch_bounds__(64) void c4_nms_matrix(C4Nms S, float thr) {
-    __shared__ float cb[5][64];
-    const int jc = blockIdx.x, ic = blockIdx.y, b = blockIdx.z;
-    const int n = S.n[b];
-    if (jc < ic || 64 * ic >= n || 64 * jc >= n) return;
-    const int t = threadIdx.x;
-    const float* bx = S.box + (size_t)b * 4 * C4_NMS_MAX;
-    const float* ar = S.area + (size_t)b * C4_NMS_MAX;
-    const int j = 64 * jc + t;
-    if (j < n) {
-        cb[0][t] = bx[j]; cb[1][t] = bx[C4_NMS_MAX + j]; cb[2][t] = bx[2 * C4_NMS_MAX + j]; cb[3][t] = bx[3 * C4_NMS_MAX + j];
-        cb[4][t] = ar[j];
-    }
-    __syncthreads();
-    const int i = 64 * ic + t;
-    if (i >= n) return;
-    uint64_t bits = 0;
-    const float ix0 = bx[i], iy0 = bx[C4_NMS_MAX + i], ix1 = bx[2 * C4_NMS_MAX + i], iy1 = bx[3 * C4_NMS_MAX + i];
-    const float ia = ar[i];
-    const int jend = (n - 64 * jc) < 64 ? (n - 64 * jc) : 64;
-    for (int jj = 0; jj < jend; ++jj) {
-        if (64 * jc + jj <= i) continue;
-        const float xx0 = fmaxf(ix0, cb[0][jj]), yy0 = fmaxf(iy0, cb[1][jj]);
-        const float xx1 = fminf(ix1, cb[2][jj]), yy1 = fminf(iy1, cb[3][jj]);
-        const float ww = fmaxf(0.f, xx1 - xx0), hh = fmaxf(0.f, yy1 - yy0);
-        const float inter = ww * hh;
-        const float ovr = inter / (ia + cb[4][jj] - inter);
-        if (ovr > thr) bits |= (1ull << jj);
-    }
-    S.mask[((size_t)b * C4_NMS_MAX + i) * C4_NMS_WORDS + jc] = bits;
-}
-
-// Greedy scan, one block per image.  Wave 0 resolves the 64 rows of a chunk on the diagonal word; then the waves OR the kept
-// rows' words right of the diagonal into the removed bitmap.  The scan ends as soon as `post` rows are kept: the kept list is in
-// processing order, so that is keep[:post] of the full scan.  Output: proposals [B][post] (boxes, scores, entry = rank in the
-// decoded list; zeros and -1 past the count) and the per-image count.
-__global__ __launch_bounds__(1024) void c4_nms_scan(C4Nms S, const float* __restrict__ dboxes, const float* __restrict__ dscores,
-                                                   int pre, int post, float* __restrict__ out_boxes, float* __restrict__ out_scores,
-                                                   int* __restrict__ out_entry, int* __restrict__ out_count) {
-    __shared__ uint64_t removed[C4_NMS_WORDS];
-    __shared__ uint64_t keepbits_s;
-    __shared__ int kept_s;
-    __shared__ int keep[1024];
-    const int b = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const int n = S.n[b];
-    const int nw = (n + 63) >> 6;
-    const uint64_t* gm = S.mask + (size_t)b * C4_NMS_MAX * C4_NMS_WORDS;
-    const int* entry = S.entry + (size_t)b * C4_NMS_MAX;
-    for (int i = tid; i < C4_NMS_WORDS; i += 1024) removed[i] = 0ull;
-    if (tid == 0) kept_s = 0;
-    __syncthreads();
-    int kept = 0;                                   // wave 0's running count
-    for (int ch = 0; ch < nw; ++ch) {
-        const int rows_here = (n - 64 * ch) < 64 ? (n - 64 * ch) : 64;
-        if (wave == 0) {
-            const int row = 64 * ch + lane;
-            const uint64_t diag = row < n ? gm[(size_t)row * C4_NMS_WORDS + ch] : 0ull;
-            uint64_t rem = removed[ch];
-            uint64_t keepbits = 0;
-            uint64_t alive = ~rem & (rows_here == 64 ? ~0ull : ((1ull << rows_here) - 1ull));
-            while (alive) {
-                const int r = __builtin_ctzll(alive);
-                keepbits |= (1ull << r);
-                rem |= readlane64(diag, r) | (1ull << r);
-                alive &= ~rem;
-            }
-            const int pos = kept + __popcll(keepbits & ((1ull << lane) - 1ull));
-            if (((keepbits >> lane) & 1ull) && pos < post) keep[pos] = entry[row];
-            kept += __popcll(keepbits);
-            if (lane == 0) { keepbits_s = keepbits; kept_s = kept; }
-        }
-        __syncthreads();
-        if (kept_s >= post) break;                  // block-uniform
-        const uint64_t kb = keepbits_s;
-        for (int w = ch + 1 + wave; w < nw; w += 16) {
-            uint64_t v = 0;
-            if (lane < rows_here && ((kb >> lane) & 1ull)) v = gm[(size_t)(64 * ch + lane) * C4_NMS_WORDS + w];
-            v = wave_or64(v);
-            if (lane == 0) removed[w] |= v;
-        }
-        __syncthreads();
-    }
-    const int cnt = kept_s < post ? kept_s : post;
-    dboxes += (size_t)b * pre * 4;
-    dscores += (size_t)b * pre;
-    for (int i = tid; i < post; i += 1024) {
-        float* ob = out_boxes + ((size_t)b * post + i) * 4;
-        if (i < cnt) {
-            const int e = keep[i];
-            ob[0] = dboxes[e * 4 + 0]; ob[1] = dboxes[e * 4 + 1]; ob[2] = dboxes[e * 4 + 2]; ob[3] = dboxes[e * 4 + 3];
-            out_scores[(size_t)b * post + i] = dscores[e];
-            out_entry[(size_t)b * post + i] = e;
-        } else {
-            ob[0] = ob[1] = ob[2] = ob[3] = 0.f;
-            out_scores[(size_t)b * post + i] = 0.f;
-            out_entry[(size_t)b * post + i] = -1;
-        }
-    }
-    if (tid == 0) out_count[b] = cnt;
-}
-
-// ---------------------------------------------------------------- training-time FPN selection
-// find_top_rpn_proposals with the training limits (PRE_NMS_TOPK_TRAIN 2000 per level, POST_NMS_TOPK_TRAIN 1000): the rules of the
-// FPN path above, but lists of up to TR_MAX = 2048 keys per (level, image), which the 1024-slot tournament lists, the 1024-box
-// NMS slot and the 64 KiB rank merge do not hold.  One slot per (level, image), slot = image * 5 + level:
-//   train_rpn_select : one block per slot.  A level of more than TR_MAX anchors: radix select of the k-th smallest composite
-//                      key, as c4_rpn_select does, leaving as soon as the remaining bin is wholly inside the top k (random
-//                      scores: after the four score bytes); then one bitonic sort of <= 2048 keys in LDS, the key list, and
-//                      rpn_decode's arithmetic on the sorted anchors (decode, clip, nonempty flag, running max coordinate).
-//   train_nms_prepare: ordered compaction of the slot's valid boxes (they arrive sorted), shifted by cat * (max_coord + 1).
-//   train_nms_matrix : 64 x 64 tiles of the suppression bit matrix in HBM, [2048][32] u64 per slot (nms_matrix's arithmetic).
-//   train_nms_scan   : greedy scan per slot; stops once post_topk rows are kept (an element behind post_topk others of its own
-//                      sorted list has a merged rank >= post_topk, so the merge below never sees it).
-//   train_rank_merge : rank merge over the five kept lists (80 KiB of keys in LDS), first post_topk.
-// The FPN and C4 kernels above are not touched by this path.
-#define TR_MAX 2048         // keys of a level's list and boxes of an NMS slot (APSE_RPN_TRAIN_MAX_PRE_TOPK, include/apse_hip.h)
-#define TR_WORDS (TR_MAX / 64)
-
+// Training: grid (5, B), one block per (level, image), n = H * W * 3 keys -> the key list (keys_out may be null) and dec_*
+// [B][5 * pre], with the image's running max coordinate.  A level of at most TR_MAX anchors is sorted whole.
 __global__ __launch_bounds__(1024) void train_rpn_select(const RpnLevels L, float img_h, float img_w, float scale_clamp,
                                                         uint64_t* __restrict__ keys_out, float* __restrict__ boxes,
                                                         float* __restrict__ scores, int* __restrict__ valid,
                                                         uint32_t* __restrict__ maxc, int level_mask) {
     __shared__ uint64_t a[TR_MAX];
     __shared__ unsigned hist[16 * 256];                                  // [16 waves][256]
-    __shared__ uint64_t prefix_s;
-    __shared__ unsigned rank_s, fill_s;
-    __shared__ int done_s;
-    const int l = blockIdx.x, b = blockIdx.y, tid = threadIdx.x, wave = tid >> 6;
+    __shared__ unsigned fill_s;
+    const int l = blockIdx.x, b = blockIdx.y, tid = threadIdx.x;
     const RpnLevel& lv = L.lv[l];
     const int head_ld = L.head_ld, pre = L.pre_topk;
     const float* head = lv.head + (size_t)b * lv.H * lv.W * head_ld;
@@ -890,39 +877,8 @@ __global__ __launch_bounds__(1024) void train_rpn_select(const RpnLevels L, floa
         const int pix = e / 3, an = e - pix * 3;
         return comp_key(head[(size_t)pix * head_ld + an], (uint32_t)e);
     };
-    if (tid == 0) { prefix_s = ~0ull; rank_s = (unsigned)(k - 1); fill_s = 0u; done_s = 0; }
-    __syncthreads();
-    // radix select, 8 bits per pass from the top.  The keys are distinct, so the last pass always ends with one key in the bin
-    for (int pass = 0; pass < 8 && n > TR_MAX; ++pass) {
-        const int shift = 56 - 8 * pass;
-        const uint64_t prefix = pass == 0 ? 0ull : prefix_s;
-        for (int i = tid; i < 16 * 256; i += 1024) hist[i] = 0u;
-        __syncthreads();
-        for (int e = tid; e < n; e += 1024) {
-            const uint64_t key = key_of(e);
-            if (pass == 0 || (key >> (shift + 8)) == (prefix >> (shift + 8))) atomicAdd(&hist[wave * 256 + (int)((key >> shift) & 255u)], 1u);
-        }
-        __syncthreads();
-        if (tid < 256) {
-            unsigned t = 0;
-            for (int w = 0; w < 16; ++w) t += hist[w * 256 + tid];
-            hist[tid] = t;                                                 // wave 0's row now holds the totals
-        }
-        __syncthreads();
-        if (tid == 0) {
-            unsigned r = rank_s;
-            int d = 0;
-            for (; d < 255 && r >= hist[d]; ++d) r -= hist[d];
-            rank_s = r;
-            const uint64_t p = prefix | ((uint64_t)d << shift);
-            // the whole bin is inside the top k: every key up to the bin's last possible one is selected
-            if (r + 1u == hist[d]) { prefix_s = p | ((1ull << shift) - 1ull); done_s = 1; }
-            else prefix_s = p;
-        }
-        __syncthreads();
-        if (done_s) break;                                                 // block-uniform
-    }
-    const uint64_t kth = prefix_s;                                         // all ones for a level that fits the list whole
+    if (tid == 0) fill_s = 0u;
+    const uint64_t kth = n > TR_MAX ? radix_select_kth(n, k, key_of, hist, tid) : ~0ull;
     for (int i = tid; i < TR_MAX; i += 1024) a[i] = ~0ull;
     __syncthreads();
     for (int e = tid; e < n; e += 1024) {
@@ -936,209 +892,9 @@ __global__ __launch_bounds__(1024) void train_rpn_select(const RpnLevels L, floa
         const size_t o = (size_t)b * 5 * pre + (size_t)l * pre + i;
         if (keys_out) keys_out[o] = i < k ? a[i] : ~0ull;
         if (i >= k || !on) { valid[o] = 0; scores[o] = 0.f; continue; }
-        const uint64_t key = a[i];
-        const uint32_t e = (uint32_t)key;
-        const float sc = comp_score(key);
-        const int pix = e / 3, an = e - pix * 3;
-        const int y = pix / lv.W, x = pix - y * lv.W;
-        const float sx = (float)(x * lv.stride), sy = (float)(y * lv.stride);
-        const float ax0 = sx + lv.base[an][0], ay0 = sy + lv.base[an][1];
-        const float ax1 = sx + lv.base[an][2], ay1 = sy + lv.base[an][3];
-        const float* d = head + (size_t)pix * head_ld + 3 + an * 4;
-        const float w = ax1 - ax0, h = ay1 - ay0;
-        const float cx = ax0 + 0.5f * w, cy = ay0 + 0.5f * h;
-        float dx = d[0] / 1.0f, dy = d[1] / 1.0f, dw = d[2] / 1.0f, dh = d[3] / 1.0f;
-        dw = dw > scale_clamp ? scale_clamp : dw;
-        dh = dh > scale_clamp ? scale_clamp : dh;
-        const float pcx = dx * w + cx, pcy = dy * h + cy;
-        const float pw = expf(dw) * w, ph = expf(dh) * h;
-        float x0 = pcx - 0.5f * pw, y0 = pcy - 0.5f * ph, x1 = pcx + 0.5f * pw, y1 = pcy + 0.5f * ph;
-        x0 = fminf(fmaxf(x0, 0.f), img_w);
-        y0 = fminf(fmaxf(y0, 0.f), img_h);
-        x1 = fminf(fmaxf(x1, 0.f), img_w);
-        y1 = fminf(fmaxf(y1, 0.f), img_h);
-        const int ok = ((x1 - x0) > 0.f) && ((y1 - y0) > 0.f);
-        boxes[o * 4 + 0] = x0; boxes[o * 4 + 1] = y0; boxes[o * 4 + 2] = x1; boxes[o * 4 + 3] = y1;
-        scores[o] = sc;
-        valid[o] = ok;
-        if (ok) {
-            const float m = fmaxf(fmaxf(x0, x1), fmaxf(y0, y1));   // all >= 0 after the clip
-            atomicMax(maxc + b, __float_as_uint(m));
-        }
+        decode_selected<3>(a[i], lv.W, lv.stride, lv.base, head, head_ld, img_h, img_w, scale_clamp, o, boxes, scores, valid,
+                           maxc + b);
     }
-}
-
-// Per slot: box [4][TR_MAX] (shifted), area, entry, n; mask [TR_MAX][TR_WORDS] u64; keep [TR_MAX] and its count.
-struct TrainNms { float* box; float* area; int* entry; int* n; uint64_t* mask; int* keep; int* keep_cnt; };
-
-// grid (5, B).  Level l's entries l * pre .. l * pre + pre - 1 are in (score desc, anchor asc) order already; the valid ones
-// keep it.  The category of a level is its rank among the levels of the mask (torchvision numbers the categories it is given).
-__global__ __launch_bounds__(1024) void train_nms_prepare(const float* __restrict__ boxes, const int* __restrict__ valid, int pre,
-                                                         const uint32_t* __restrict__ maxc, int level_mask, TrainNms S) {
-    __shared__ int wsum[17];
-    const int l = blockIdx.x, b = blockIdx.y, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const size_t slot = (size_t)b * 5 + l;
-    boxes += (size_t)b * 5 * pre * 4;
-    valid += (size_t)b * 5 * pre;
-    const float off = (float)__popc(level_mask & ((1 << l) - 1)) * (__uint_as_float(maxc[b]) + 1.0f);
-    float* bx = S.box + slot * 4 * TR_MAX;
-    if (tid == 0) wsum[16] = 0;
-    __syncthreads();
-    for (int base = 0; base < pre; base += 1024) {
-        const int i = base + tid, e = l * pre + i;
-        const bool f = i < pre && valid[e];
-        const uint64_t bal = __ballot(f);
-        if (lane == 0) wsum[wave] = __popcll(bal);
-        __syncthreads();
-        int o = wsum[16];
-        for (int w = 0; w < wave; ++w) o += wsum[w];
-        const int pos = o + __popcll(bal & ((1ull << lane) - 1ull));
-        if (f && pos < TR_MAX) {
-            const float x0 = boxes[e * 4 + 0] + off, y0 = boxes[e * 4 + 1] + off;
-            const float x1 = boxes[e * 4 + 2] + off, y1 = boxes[e * 4 + 3] + off;
-            bx[pos] = x0; bx[TR_MAX + pos] = y0; bx[2 * TR_MAX + pos] = x1; bx[3 * TR_MAX + pos] = y1;
-            S.area[slot * TR_MAX + pos] = (x1 - x0) * (y1 - y0);
-            S.entry[slot * TR_MAX + pos] = e;
-        }
-        __syncthreads();
-        if (tid == 0) { int t = wsum[16]; for (int w = 0; w < 16; ++w) t += wsum[w]; wsum[16] = t; }
-        __syncthreads();
-    }
-    if (tid == 0) S.n[slot] = wsum[16] < TR_MAX ? wsum[16] : TR_MAX;
-}
-
-// grid (TR_WORDS column chunks, TR_WORDS row chunks, 5 B), 64 threads: thread t owns row 64 * ic + t.
-__global__ __launch_bounds__(64) void train_nms_matrix(TrainNms S, float thr) {
-    __shared__ float cb[5][64];
-    const int jc = blockIdx.x, ic = blockIdx.y;
-    const size_t slot = blockIdx.z;
-    const int n = S.n[slot];
-    if (jc < ic || 64 * ic >= n || 64 * jc >= n) return;
-    const int t = threadIdx.x;
-    const float* bx = S.box + slot * 4 * TR_MAX;
-    const float* ar = S.area + slot * TR_MAX;
-    const int j = 64 * jc + t;
-    if (j < n) {
-        cb[0][t] = bx[j]; cb[1][t] = bx[TR_MAX + j]; cb[2][t] = bx[2 * TR_MAX + j]; cb[3][t] = bx[3 * TR_MAX + j];
-        cb[4][t] = ar[j];
-    }
-    __syncthreads();
-    const int i = 64 * ic + t;
-    if (i >= n) return;
-    uint64_t bits = 0;
-    const float ix0 = bx[i], iy0 = bx[TR_MAX + i], ix1 = bx[2 * TR_MAX + i], iy1 = bx[3 * TR_MAX + i];
-    const float ia = ar[i];
-    const int jend = (n - 64 * jc) < 64 ? (n - 64 * jc) : 64;
-    for (int jj = 0; jj < jend; ++jj) {
-        if (64 * jc + jj <= i) continue;
-        const float xx0 = fmaxf(ix0, cb[0][jj]), yy0 = fmaxf(iy0, cb[1][jj]);
-        const float xx1 = fminf(ix1, cb[2][jj]), yy1 = fminf(iy1, cb[3][jj]);
-        const float ww = fmaxf(0.f, xx1 - xx0), hh = fmaxf(0.f, yy1 - yy0);
-        const float inter = ww * hh;
-        const float ovr = inter / (ia + cb[4][jj] - inter);
-        if (ovr > thr) bits |= (1ull << jj);
-    }
-    S.mask[(slot * TR_MAX + i) * TR_WORDS + jc] = bits;
-}
-
-// Greedy scan, grid (5, B), the bit matrix read from HBM (only words on and right of the diagonal of rows < n: those the matrix
-// kernel wrote).  Kept entries in processing order -> keep [slot][TR_MAX], at most `post` of them.
-__global__ __launch_bounds__(1024) void train_nms_scan(TrainNms S, int post) {
-    __shared__ uint64_t removed[TR_WORDS];
-    __shared__ uint64_t keepbits_s;
-    __shared__ int kept_s;
-    const size_t slot = (size_t)blockIdx.y * 5 + blockIdx.x;
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const int n = S.n[slot];
-    const int nw = (n + 63) >> 6;
-    const uint64_t* gm = S.mask + slot * TR_MAX * TR_WORDS;
-    const int* entry = S.entry + slot * TR_MAX;
-    int* keep = S.keep + slot * TR_MAX;
-    if (tid < TR_WORDS) removed[tid] = 0ull;
-    if (tid == 0) kept_s = 0;
-    __syncthreads();
-    int kept = 0;                                   // wave 0's running count
-    for (int ch = 0; ch < nw; ++ch) {
-        const int rows_here = (n - 64 * ch) < 64 ? (n - 64 * ch) : 64;
-        if (wave == 0) {
-            const int row = 64 * ch + lane;
-            const uint64_t diag = row < n ? gm[(size_t)row * TR_WORDS + ch] : 0ull;
-            uint64_t rem = removed[ch];
-            uint64_t keepbits = 0;
-            uint64_t alive = ~rem & (rows_here == 64 ? ~0ull : ((1ull << rows_here) - 1ull));
-            while (alive) {
-                const int r = __builtin_ctzll(alive);
-                keepbits |= (1ull << r);
-                rem |= readlane64(diag, r) | (1ull << r);
-                alive &= ~rem;
-            }
-            const int pos = kept + __popcll(keepbits & ((1ull << lane) - 1ull));
-            if (((keepbits >> lane) & 1ull) && pos < post) keep[pos] = entry[row];
-            kept += __popcll(keepbits);
-            if (lane == 0) { keepbits_s = keepbits; kept_s = kept; }
-        }
-        __syncthreads();
-        if (kept_s >= post) break;                  // block-uniform
-        const uint64_t kb = keepbits_s;
-        for (int w = ch + 1 + wave; w < nw; w += 16) {
-            uint64_t v = 0;
-            if (lane < rows_here && ((kb >> lane) & 1ull)) v = gm[(size_t)(64 * ch + lane) * TR_WORDS + w];
-            v = wave_or64(v);
-            if (lane == 0) removed[w] |= v;
-        }
-        __syncthreads();
-    }
-    if (tid == 0) S.keep_cnt[slot] = kept_s < post ? kept_s : post;
-}
-
-// rank_merge over five lists of up to TR_MAX keys: grid (image, level), every block loads the five lists of its image and ranks
-// the elements of its own (position + binary-search counts in the other four).  K <= TR_MAX.
-__global__ __launch_bounds__(1024) void train_rank_merge(const float* __restrict__ boxes, const float* __restrict__ scores,
-                                                        int n_total, TrainNms S, int K, float* __restrict__ out_boxes,
-                                                        float* __restrict__ out_scores, int* __restrict__ out_entry,
-                                                        int* __restrict__ out_count) {
-    extern __shared__ __attribute__((aligned(16))) char smem[];
-    uint64_t* keys = reinterpret_cast<uint64_t*>(smem);      // [5][TR_MAX]
-    __shared__ int cnt[5];
-    const int b = blockIdx.x, c = blockIdx.y, tid = threadIdx.x;
-    boxes += (size_t)b * n_total * 4;
-    scores += (size_t)b * n_total;
-    if (tid < 5) cnt[tid] = S.keep_cnt[b * 5 + tid];
-    __syncthreads();
-    int total = 0;
-    for (int o = 0; o < 5; ++o) {
-        const int* src = S.keep + ((size_t)b * 5 + o) * TR_MAX;
-        for (int i = tid; i < cnt[o]; i += 1024) { const int e = src[i]; keys[o * TR_MAX + i] = comp_key(scores[e], (uint32_t)e); }
-        total += cnt[o];
-    }
-    __syncthreads();
-    const int nout = total < K ? total : K;
-    for (int i = tid; i < cnt[c]; i += 1024) {
-        const uint64_t key = keys[c * TR_MAX + i];
-        int rank = i;
-        for (int o = 0; o < 5; ++o) {
-            if (o == c) continue;
-            int lo = 0, hi = cnt[o];
-            const uint64_t* ko = keys + o * TR_MAX;
-            while (lo < hi) { const int mid = (lo + hi) >> 1; if (ko[mid] < key) lo = mid + 1; else hi = mid; }
-            rank += lo;
-        }
-        if (rank < K) {
-            const uint32_t e = (uint32_t)key;
-            float* ob = out_boxes + ((size_t)b * K + rank) * 4;
-            ob[0] = boxes[e * 4 + 0]; ob[1] = boxes[e * 4 + 1]; ob[2] = boxes[e * 4 + 2]; ob[3] = boxes[e * 4 + 3];
-            out_scores[(size_t)b * K + rank] = scores[e];
-            out_entry[(size_t)b * K + rank] = (int)e;
-        }
-    }
-    if (c != 0) return;
-    for (int i = nout + tid; i < K; i += 1024) {
-        float* ob = out_boxes + ((size_t)b * K + i) * 4;
-        ob[0] = ob[1] = ob[2] = ob[3] = 0.f;
-        out_scores[(size_t)b * K + i] = 0.f;
-        out_entry[(size_t)b * K + i] = -1;
-    }
-    if (tid == 0) out_count[b] = nout;
 }
 
 // Pack per-image detections into one dense list (image id kept per entry) so the mask tail's
@@ -1175,6 +931,48 @@ __global__ void pack_detections(const float* __restrict__ det_boxes, const float
     }
 }
 
+// ---------------------------------------------------------------- host side
+// A scratch layout is written once, as a walk that takes its arrays in order.  With a base the walk hands out the pointers;
+// without one it only adds up the sizes: the byte count and the carve cannot disagree.
+struct ScratchWalk {
+    void* base;
+    size_t bytes = 0;
+    template <class T>
+    T* take(size_t count) {
+        T* p = base ? reinterpret_cast<T*>(static_cast<char*>(base) + bytes) : nullptr;
+        bytes += count * sizeof(T);
+        return p;
+    }
+};
+// `slots` NMS slots of `len` boxes.  The 64-bit words come first; everything after them is 4-byte data.
+static NmsSlots walk_slots(ScratchWalk& w, size_t slots, size_t len) {
+    NmsSlots S;
+    S.mask = w.take<uint64_t>(slots * len * (len / 64));
+    S.box = w.take<float>(slots * 4 * len);
+    S.area = w.take<float>(slots * len);
+    S.entry = w.take<int>(slots * len);
+    S.n = w.take<int>(slots);
+    return S;
+}
+// Training-time selection: five slots of TR_MAX per image, their kept lists for the merge, the images' max-coordinate cells.
+struct TrainScratch { NmsSlots S; int* keep; int* keep_cnt; uint32_t* maxc; };
+static TrainScratch walk_train(ScratchWalk& w, size_t B) {
+    TrainScratch T;
+    T.S = walk_slots(w, B * 5, TR_MAX);
+    T.keep = w.take<int>(B * 5 * TR_MAX);
+    T.keep_cnt = w.take<int>(B * 5);
+    T.maxc = w.take<uint32_t>(B);
+    return T;
+}
+
+// A kernel opts in to its largest dynamic LDS size (`Bytes`) once, before its first launch.
+template <auto Kernel, int Bytes>
+static void allow_dynamic_lds() {
+    static const hipError_t once =
+        hipFuncSetAttribute(reinterpret_cast<const void*>(Kernel), hipFuncAttributeMaxDynamicSharedMemorySize, Bytes);
+    (void)once;
+}
+
 extern "C" {
 int apse_k_rpn_topk_stage(const RpnLevels* L_dev, const TopkJob* jobs_dev, int njobs, uint64_t* lists, int nslots, int B,
                           uint32_t* zero_word, hipStream_t s) {
@@ -1190,46 +988,29 @@ int apse_k_rpn_decode(const RpnLevels* L_dev, int pre_topk, const uint64_t* list
     return hipGetLastError() == hipSuccess ? APSE_OK : APSE_E_HIP;
 }
 size_t apse_nms_scratch_bytes(int slots) {
-    return (size_t)slots * (NMS_MAX * 4 + 4 * NMS_MAX * 4 + NMS_MAX * 4 + (size_t)NMS_MAX * 16 * 8 + 16);
-}
-static NmsScratch carve(void* scratch, int slots) {
-    NmsScratch S;
-    char* p = reinterpret_cast<char*>(scratch);
-    S.mask = reinterpret_cast<uint64_t*>(p); p += (size_t)slots * NMS_MAX * 16 * 8;
-    S.box = reinterpret_cast<float*>(p); p += (size_t)slots * 4 * NMS_MAX * 4;
-    S.area = reinterpret_cast<float*>(p); p += (size_t)slots * NMS_MAX * 4;
-    S.entry = reinterpret_cast<int*>(p); p += (size_t)slots * NMS_MAX * 4;
-    S.n = reinterpret_cast<int*>(p);
-    return S;
+    ScratchWalk w{nullptr};
+    walk_slots(w, (size_t)slots, NMS_MAX);
+    return w.bytes;
 }
 int apse_k_nms_percat(const float* boxes, const float* scores, const int* valid, int n_total, int cat_div, int cat_mod,
                       const uint32_t* maxc, float thr, int* keep_idx, int* keep_cnt, int ncat, void* scratch, int cat_mask,
                       int B, int presorted, hipStream_t s) {
-    static bool done = false;
-    if (!done) {
-        hipFuncSetAttribute(reinterpret_cast<const void*>(&nms_scan), hipFuncAttributeMaxDynamicSharedMemorySize,
-                            NMS_MAX * 16 * 8);
-        done = true;
-    }
-    NmsScratch S = carve(scratch, ncat * B);
+    allow_dynamic_lds<&nms_scan, NMS_MAX * 16 * 8>();
+    ScratchWalk w{scratch};
+    const NmsSlots S = walk_slots(w, (size_t)ncat * B, NMS_MAX);
     hipLaunchKernelGGL(nms_prepare, dim3(ncat, B), dim3(1024), 0, s, boxes, scores, valid, n_total, cat_div, cat_mod, maxc, S,
                        ncat, cat_mask, presorted);
-    hipLaunchKernelGGL(nms_matrix, dim3(16, 16, ncat * B), dim3(64), 0, s, S, thr);
+    hipLaunchKernelGGL(nms_matrix<NMS_MAX>, dim3(NMS_MAX / 64, NMS_MAX / 64, ncat * B), dim3(64), 0, s, S, thr);
     hipLaunchKernelGGL(nms_scan, dim3(ncat, B), dim3(1024), NMS_MAX * 16 * 8, s, S, keep_idx, keep_cnt);
     return hipGetLastError() == hipSuccess ? APSE_OK : APSE_E_HIP;
 }
 int apse_k_rank_final(const float* boxes, const float* scores, int n_total, const int* keep_idx, const int* keep_cnt,
                       int ncat, int K, float* out_boxes, float* out_scores, int* out_entry, int* out_count,
                       uint32_t* zero_word, int B, hipStream_t s) {
-    static bool done = false;
-    if (!done) {
-        hipFuncSetAttribute(reinterpret_cast<const void*>(&rank_merge), hipFuncAttributeMaxDynamicSharedMemorySize,
-                            8 * NMS_MAX * 8);
-        done = true;
-    }
+    allow_dynamic_lds<&rank_merge<NMS_MAX>, 8 * NMS_MAX * 8>();
     if (ncat > 8) return APSE_E_INVALID;
-    hipLaunchKernelGGL(rank_merge, dim3(B, ncat), dim3(1024), (size_t)ncat * NMS_MAX * 8, s, boxes, scores, n_total, keep_idx, keep_cnt,
-                       ncat, K, out_boxes, out_scores, out_entry, out_count, zero_word);
+    hipLaunchKernelGGL(rank_merge<NMS_MAX>, dim3(B, ncat), dim3(1024), (size_t)ncat * NMS_MAX * 8, s, boxes, scores, n_total,
+                       keep_idx, keep_cnt, ncat, K, out_boxes, out_scores, out_entry, out_count, zero_word);
     return hipGetLastError() == hipSuccess ? APSE_OK : APSE_E_HIP;
 }
 int apse_k_box_candidates(const float* pred, int ld, int K, const float* props, const int* prop_cnt, int P, float img_h,
@@ -1251,80 +1032,49 @@ int apse_k_box_candidates_wide(const float* pred, int ld, int K, const float* pr
 int apse_k_rank_wide(const float* boxes, const float* scores, int n_total, const int* keep_idx, const int* keep_cnt, int ncat,
                      int K, float* out_boxes, float* out_scores, int* out_entry, int* out_count, int B, hipStream_t s) {
     if (ncat < 1 || ncat > 128 || K < 1 || (size_t)ncat * K > 8192) return APSE_E_INVALID;      // one block sorts <= 8192 keys
-    static bool done = false;
-    if (!done) {
-        hipFuncSetAttribute(reinterpret_cast<const void*>(&rank_sort_wide), hipFuncAttributeMaxDynamicSharedMemorySize, 8192 * 8);
-        done = true;
-    }
+    allow_dynamic_lds<&rank_sort_wide, 8192 * 8>();
     hipLaunchKernelGGL(rank_sort_wide, dim3(B), dim3(1024), 8192 * 8, s, boxes, scores, n_total, keep_idx, keep_cnt, ncat, K,
                        out_boxes, out_scores, out_entry, out_count);
     return hipGetLastError() == hipSuccess ? APSE_OK : APSE_E_HIP;
 }
 int apse_k_nms_lists(const float* boxes, const float* scores, int n_total, const int* clist, int* ccnt, int list_stride,
                      const uint32_t* maxc, float thr, int* keep_idx, int* keep_cnt, int ncat, void* scratch, int B, hipStream_t s) {
-    static bool done = false;
-    if (!done) {
-        hipFuncSetAttribute(reinterpret_cast<const void*>(&nms_scan), hipFuncAttributeMaxDynamicSharedMemorySize,
-                            NMS_MAX * 16 * 8);
-        done = true;
-    }
+    allow_dynamic_lds<&nms_scan, NMS_MAX * 16 * 8>();
     if (list_stride > NMS_MAX) return APSE_E_INVALID;
-    NmsScratch S = carve(scratch, ncat * B);
+    ScratchWalk w{scratch};
+    const NmsSlots S = walk_slots(w, (size_t)ncat * B, NMS_MAX);
     hipLaunchKernelGGL(nms_prepare_list, dim3(ncat, B), dim3(1024), 0, s, boxes, scores, n_total, clist, ccnt, list_stride, maxc, S,
                        ncat);
-    hipLaunchKernelGGL(nms_matrix, dim3(16, 16, ncat * B), dim3(64), 0, s, S, thr);
+    hipLaunchKernelGGL(nms_matrix<NMS_MAX>, dim3(NMS_MAX / 64, NMS_MAX / 64, ncat * B), dim3(64), 0, s, S, thr);
     hipLaunchKernelGGL(nms_scan, dim3(ncat, B), dim3(1024), NMS_MAX * 16 * 8, s, S, keep_idx, keep_cnt);
     return hipGetLastError() == hipSuccess ? APSE_OK : APSE_E_HIP;
 }
 size_t apse_c4_nms_scratch_bytes(int B) {
-    return (size_t)B * ((size_t)C4_NMS_MAX * C4_NMS_WORDS * 8 + (size_t)C4_NMS_MAX * 4 * 4 + (size_t)C4_NMS_MAX * 4 * 2 + 16);
-}
-static C4Nms c4_carve(void* scratch, int B) {
-    C4Nms S;
-    char* p = reinterpret_cast<char*>(scratch);
-    S.mask = reinterpret_cast<uint64_t*>(p); p += (size_t)B * C4_NMS_MAX * C4_NMS_WORDS * 8;
-    S.box = reinterpret_cast<float*>(p); p += (size_t)B * 4 * C4_NMS_MAX * 4;
-    S.area = reinterpret_cast<float*>(p); p += (size_t)B * C4_NMS_MAX * 4;
-    S.entry = reinterpret_cast<int*>(p); p += (size_t)B * C4_NMS_MAX * 4;
-    S.n = reinterpret_cast<int*>(p);
-    return S;
+    ScratchWalk w{nullptr};
+    walk_slots(w, (size_t)B, C4_NMS_MAX);
+    return w.bytes;
 }
 // C4 proposals: select + decode (dec_* [B][pre]), long NMS, keep[:post] -> props [B][post], counts.  pre <= 6000, post <= 1000.
 int apse_k_c4_rpn(const C4Rpn* R, int pre, int post, float img_h, float img_w, float scale_clamp, float thr, float* dec_boxes,
                   float* dec_scores, int* dec_valid, void* scratch, float* props, float* prop_scores, int* prop_entry,
                   int* prop_count, int B, hipStream_t s) {
     if (pre < 1 || pre > 6000 || R->k > pre || post < 1 || post > 1000) return APSE_E_INVALID;
-    static bool done = false;
-    const size_t lds = (size_t)C4_SORT_N * 8 + 16 * 256 * 4;
-    if (!done) {
-        hipFuncSetAttribute(reinterpret_cast<const void*>(&c4_rpn_select), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        done = true;
-    }
+    constexpr int lds = C4_SORT_N * 8 + 16 * 256 * 4;
+    allow_dynamic_lds<&c4_rpn_select, lds>();
     hipLaunchKernelGGL(c4_rpn_select, dim3(B), dim3(1024), lds, s, *R, img_h, img_w, scale_clamp, dec_boxes, dec_scores, dec_valid, pre);
-    C4Nms S = c4_carve(scratch, B);
-    hipLaunchKernelGGL(c4_nms_prepare, dim3(B), dim3(1024), 0, s, dec_boxes, dec_valid, pre, S);
-    hipLaunchKernelGGL(c4_nms_matrix, dim3(C4_NMS_WORDS, C4_NMS_WORDS, B), dim3(64), 0, s, S, thr);
-    hipLaunchKernelGGL(c4_nms_scan, dim3(B), dim3(1024), 0, s, S, dec_boxes, dec_scores, pre, post, props, prop_scores, prop_entry,
-                       prop_count);
+    ScratchWalk w{scratch};
+    const NmsSlots S = walk_slots(w, (size_t)B, C4_NMS_MAX);
+    hipLaunchKernelGGL(long_nms_prepare<C4_NMS_MAX>, dim3(1, B), dim3(1024), 0, s, dec_boxes, dec_valid, pre,
+                       static_cast<const uint32_t*>(nullptr), 0, S);
+    hipLaunchKernelGGL(nms_matrix<C4_NMS_MAX>, dim3(C4_NMS_MAX / 64, C4_NMS_MAX / 64, B), dim3(64), 0, s, S, thr);
+    hipLaunchKernelGGL(long_nms_scan_proposals, dim3(B), dim3(1024), 0, s, S, dec_boxes, dec_scores, pre, post, props, prop_scores,
+                       prop_entry, prop_count);
     return hipGetLastError() == hipSuccess ? APSE_OK : APSE_E_HIP;
 }
 size_t apse_rpn_train_scratch_bytes(int B) {
-    const size_t slots = (size_t)B * 5;
-    return slots * ((size_t)TR_MAX * TR_WORDS * 8 + (size_t)TR_MAX * 4 * 4 + (size_t)TR_MAX * 4 * 3 + 8) + (size_t)B * 4 + 16;
-}
-static TrainNms train_carve(void* scratch, int B, uint32_t** maxc) {
-    TrainNms S;
-    const size_t slots = (size_t)B * 5;
-    char* p = reinterpret_cast<char*>(scratch);
-    S.mask = reinterpret_cast<uint64_t*>(p); p += slots * TR_MAX * TR_WORDS * 8;
-    S.box = reinterpret_cast<float*>(p); p += slots * 4 * TR_MAX * 4;
-    S.area = reinterpret_cast<float*>(p); p += slots * TR_MAX * 4;
-    S.entry = reinterpret_cast<int*>(p); p += slots * TR_MAX * 4;
-    S.keep = reinterpret_cast<int*>(p); p += slots * TR_MAX * 4;
-    S.n = reinterpret_cast<int*>(p); p += slots * 4;
-    S.keep_cnt = reinterpret_cast<int*>(p); p += slots * 4;
-    *maxc = reinterpret_cast<uint32_t*>(p);
-    return S;
+    ScratchWalk w{nullptr};
+    walk_train(w, (size_t)B);
+    return w.bytes;
 }
 // Training-time FPN proposals: L (host; pre_topk and every level's k filled, rpn_select_plan) -> key lists (keys may be null),
 // dec_* [B][5 * pre], props [B][post], counts.  1 <= pre, post <= TR_MAX; scratch of apse_rpn_train_scratch_bytes(B).
@@ -1335,22 +1085,19 @@ int apse_k_rpn_train_select(const RpnLevels* L, int post, float img_h, float img
     if (pre < 1 || pre > TR_MAX || post < 1 || post > TR_MAX || B < 1) return APSE_E_INVALID;
     for (int l = 0; l < 5; ++l)
         if (L->lv[l].k > pre || L->lv[l].k > L->lv[l].n) return APSE_E_INVALID;
-    static bool done = false;
-    if (!done) {
-        hipFuncSetAttribute(reinterpret_cast<const void*>(&train_rank_merge), hipFuncAttributeMaxDynamicSharedMemorySize,
-                            5 * TR_MAX * 8);
-        done = true;
-    }
-    uint32_t* maxc;
-    TrainNms S = train_carve(scratch, B, &maxc);
-    if (hipMemsetAsync(maxc, 0, (size_t)B * 4, s) != hipSuccess) return APSE_E_HIP;
+    allow_dynamic_lds<&rank_merge<TR_MAX>, 5 * TR_MAX * 8>();
+    ScratchWalk w{scratch};
+    const TrainScratch T = walk_train(w, (size_t)B);
+    if (hipMemsetAsync(T.maxc, 0, (size_t)B * 4, s) != hipSuccess) return APSE_E_HIP;
     hipLaunchKernelGGL(train_rpn_select, dim3(5, B), dim3(1024), 0, s, *L, img_h, img_w, scale_clamp, keys, dec_boxes, dec_scores,
-                       dec_valid, maxc, level_mask);
-    hipLaunchKernelGGL(train_nms_prepare, dim3(5, B), dim3(1024), 0, s, dec_boxes, dec_valid, pre, maxc, level_mask, S);
-    hipLaunchKernelGGL(train_nms_matrix, dim3(TR_WORDS, TR_WORDS, 5 * B), dim3(64), 0, s, S, thr);
-    hipLaunchKernelGGL(train_nms_scan, dim3(5, B), dim3(1024), 0, s, S, post);
-    hipLaunchKernelGGL(train_rank_merge, dim3(B, 5), dim3(1024), (size_t)5 * TR_MAX * 8, s, dec_boxes, dec_scores, 5 * pre, S, post,
-                       props, prop_scores, prop_entry, prop_count);
+                       dec_valid, T.maxc, level_mask);
+    hipLaunchKernelGGL(long_nms_prepare<TR_MAX>, dim3(5, B), dim3(1024), 0, s, dec_boxes, dec_valid, pre,
+                       static_cast<const uint32_t*>(T.maxc), level_mask, T.S);
+    hipLaunchKernelGGL(nms_matrix<TR_MAX>, dim3(TR_MAX / 64, TR_MAX / 64, 5 * B), dim3(64), 0, s, T.S, thr);
+    hipLaunchKernelGGL(long_nms_scan_keep, dim3(5, B), dim3(1024), 0, s, T.S, post, T.keep, T.keep_cnt);
+    hipLaunchKernelGGL(rank_merge<TR_MAX>, dim3(B, 5), dim3(1024), (size_t)5 * TR_MAX * 8, s, dec_boxes, dec_scores, 5 * pre,
+                       static_cast<const int*>(T.keep), static_cast<const int*>(T.keep_cnt), 5, post, props, prop_scores,
+                       prop_entry, prop_count, static_cast<uint32_t*>(nullptr));
     return hipGetLastError() == hipSuccess ? APSE_OK : APSE_E_HIP;
 }
 int apse_k_pack_detections(const float* det_boxes, const float* det_scores, const int* det_entry, const int* det_cnt, int B,
