@@ -180,6 +180,9 @@ int apse_k_dense_to_bits(const uint8_t* dense, int out_h, int out_w, int words_p
                          unsigned long long* sums, hipStream_t s);
 // ---- mask_train.hip
 int apse_k_mask_roi_index(int* idx, int n, hipStream_t s);
+// ---- coco_eval.hip (the polygon rule lives there; apse_coco_mask_targets of mask_train.hip checks the limits and calls this)
+int apse_k_mask_targets(const double* xy, const int* part_vert_off, int n_parts, const int* obj_part_off, int n_obj, int n_verts,
+                        const float* rois, const int* matched, int n, uint8_t* targets, int* info, hipStream_t s);
 // ---- augment.hip
 int apse_k_augment(const uint8_t* src, int B, int H, int W, const AugmentBatch* P_host, uint8_t* out_u8, float* out_chw,
                    unsigned long long* sums, hipStream_t s);

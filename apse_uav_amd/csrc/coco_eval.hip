@@ -5,13 +5,15 @@
 //   poly_to_bits   rleFrPoly + merge: one thread per polygon edge writes the edge's y-boundary points (the host sized every
 //                  edge's share by the same column rule), then one wave per window word counts, per part, the points at or before
 //                  each pixel (odd: set) and ORs the parts
+//   mask_targets   PolygonMasks.crop_and_resize at 28 x 28 for mask-head training: one block per RoI transforms the matched
+//                  object's vertices, takes every part through the same edge rule with its points kept in LDS, writes bytes
 //   match          evaluateImg's greedy matching: one wave per (group, area range, IoU threshold), detections in order, the
 //                  ground truths spread over the lanes; the pick is an (ignore class, IoU, index) max-reduction
 //   accumulate     a stable LSD radix sort of every (category, maxDet) list of scores (one block per list), then one wave per
 //                  (threshold, category, area range, maxDet): counts, precision envelope and the recall-threshold lookups
 // Every value is f64 as pycocotools computes it (the build keeps -ffp-contract=off), there are no float atomics, and every
 // reduction is an exact max or an integer sum: results are bit-reproducible.
-#include "apse_common.h"
+#include "apse_kernels.h"
 #include "../../include/apse_hip.h"
 #include <limits.h>
 #include <math.h>
@@ -69,9 +71,59 @@ __device__ __forceinline__ int last_le(const int* off, int n, int v) {     // la
     return lo;
 }
 
-// Edge j (vertex j to the next vertex of its part): the y-boundary points rleFrPoly keeps from this edge's consecutive walk
-// points.  There is one per column x in [0, w-1] whose boundary u = 5x+2 | 5x+3 the walk crosses (xd == x exactly there, and
-// nowhere else); consecutive edges share their scaled vertex, so no kept point spans two edges.
+// An edge between two scaled vertices, as rleFrPoly walks it.  The y-boundary points it keeps from this edge's consecutive walk
+// points: one per column x in [0, w-1] whose boundary u = 5x+2 | 5x+3 the walk crosses (xd == x exactly there, and nowhere
+// else); consecutive edges share their scaled vertex, so no kept point spans two edges.
+struct PolyEdge {
+    int xs, ys, xe, ye, dx, dy;       // after orient(): in walk order
+    int xa, xb;                       // the columns that hold a point: xa .. xb (none when xb < xa)
+    double s;                         // the walk's slope (set by orient())
+};
+
+__device__ __forceinline__ PolyEdge poly_edge(int xs, int ys, int xe, int ye, int w) {
+    PolyEdge e;
+    e.xs = xs; e.ys = ys; e.xe = xe; e.ye = ye;
+    e.dx = abs(xe - xs); e.dy = abs(ys - ye);
+    const int lo = min(xs, xe), hi = max(xs, xe);
+    e.xa = lo > 2 ? (lo + 2) / 5 : 0;                // first x with 5x+2 >= lo
+    e.xb = hi >= 3 ? min(w - 1, (hi - 3) / 5) : -1;  // last x with 5x+3 <= hi
+    e.s = 0.0;
+    return e;
+}
+
+__device__ __forceinline__ int edge_count(const PolyEdge& e) { return e.xb >= e.xa ? e.xb - e.xa + 1 : 0; }
+
+// rleFrPoly's flip and slope; only for an edge with points (dx > 0 there, so no division by zero)
+__device__ __forceinline__ void orient(PolyEdge& e) {
+    const bool flip = (e.dx >= e.dy && e.xs > e.xe) || (e.dx < e.dy && e.ys > e.ye);
+    if (flip) { int t = e.xs; e.xs = e.xe; e.xe = t; t = e.ys; e.ys = e.ye; e.ye = t; }
+    e.s = e.dx >= e.dy ? (double)(e.ye - e.ys) / e.dx : (double)(e.xe - e.xs) / e.dy;
+}
+
+// The point of column x (xa <= x <= xb) of an oriented edge in an image of height h: x * h + y, y in [0, h]
+__device__ __forceinline__ int edge_point(const PolyEdge& e, int x, int h) {
+    int vmin;
+    if (e.dx >= e.dy) {                                  // u = t + xs: the pair t0 = 5x+2-xs, t0+1
+        const int t0 = 5 * x + 2 - e.xs;
+        const int v0 = (int)(e.ys + e.s * t0 + .5), v1 = (int)(e.ys + e.s * (t0 + 1) + .5);
+        vmin = min(v0, v1);
+    } else {                                             // u = (int)(xs + s t + .5): monotone in t, steps of at most 1
+        int a = 1, b = e.dy;                             // first t whose u is past the boundary
+        while (a < b) {
+            const int mid = (a + b) >> 1;
+            const int u = (int)(e.xs + e.s * mid + .5);
+            const bool past = e.s >= 0 ? u >= 5 * x + 3 : u <= 5 * x + 2;
+            if (past) b = mid; else a = mid + 1;
+        }
+        vmin = a - 1 + e.ys;                             // v = t + ys: the pair (a-1, a)
+    }
+    double yd = ((double)vmin + .5) / kScale - .5;
+    if (yd < 0) yd = 0; else if (yd > h) yd = h;
+    yd = ceil(yd);
+    return x * h + (int)yd;
+}
+
+// Edge j (vertex j to the next vertex of its part) writes its points into the share the host sized for it.
 __global__ void __launch_bounds__(256) poly_edges(const double* __restrict__ xy, const int* __restrict__ part_vert_off,
                                                   int n_parts, const int* __restrict__ obj_part_off, int n_obj,
                                                   const int* __restrict__ obj_hw, const int* __restrict__ edge_off, int n_verts,
@@ -82,40 +134,13 @@ __global__ void __launch_bounds__(256) poly_edges(const double* __restrict__ xy,
     const int obj = last_le(obj_part_off, n_obj + 1, part);
     const int h = obj_hw[2 * obj], w = obj_hw[2 * obj + 1];
     const int nxt = j + 1 < part_vert_off[part + 1] ? j + 1 : part_vert_off[part];
-    int xs = scaled(xy[2 * j]), ys = scaled(xy[2 * j + 1]);
-    int xe = scaled(xy[2 * nxt]), ye = scaled(xy[2 * nxt + 1]);
-    const int dx = abs(xe - xs), dy = abs(ys - ye);
-    const int lo = min(xs, xe), hi = max(xs, xe);
-    const int xa = lo > 2 ? (lo + 2) / 5 : 0;                // first x with 5x+2 >= lo
-    const int xb = hi >= 3 ? min(w - 1, (hi - 3) / 5) : -1;  // last x with 5x+3 <= hi
-    const int cnt = xb >= xa ? xb - xa + 1 : 0;
+    PolyEdge e = poly_edge(scaled(xy[2 * j]), scaled(xy[2 * j + 1]), scaled(xy[2 * nxt]), scaled(xy[2 * nxt + 1]), w);
+    const int cnt = edge_count(e);
     const int base = edge_off[j];
     if (cnt != edge_off[j + 1] - base) { info[0] = 1; return; }     // the host sized this edge differently: write nothing
     if (cnt == 0) return;
-    const bool flip = (dx >= dy && xs > xe) || (dx < dy && ys > ye);
-    if (flip) { int t = xs; xs = xe; xe = t; t = ys; ys = ye; ye = t; }
-    const double s = dx >= dy ? (double)(ye - ys) / dx : (double)(xe - xs) / dy;
-    for (int x = xa; x <= xb; ++x) {
-        int vmin;
-        if (dx >= dy) {                                      // u = t + xs: the pair t0 = 5x+2-xs, t0+1
-            const int t0 = 5 * x + 2 - xs;
-            const int v0 = (int)(ys + s * t0 + .5), v1 = (int)(ys + s * (t0 + 1) + .5);
-            vmin = min(v0, v1);
-        } else {                                             // u = (int)(xs + s t + .5): monotone in t, steps of at most 1
-            int a = 1, b = dy;                               // first t whose u is past the boundary
-            while (a < b) {
-                const int mid = (a + b) >> 1;
-                const int u = (int)(xs + s * mid + .5);
-                const bool past = s >= 0 ? u >= 5 * x + 3 : u <= 5 * x + 2;
-                if (past) b = mid; else a = mid + 1;
-            }
-            vmin = a - 1 + ys;                               // v = t + ys: the pair (a-1, a)
-        }
-        double yd = ((double)vmin + .5) / kScale - .5;
-        if (yd < 0) yd = 0; else if (yd > h) yd = h;
-        yd = ceil(yd);
-        toggles[base + (x - xa)] = x * h + (int)yd;
-    }
+    orient(e);
+    for (int x = e.xa; x <= e.xb; ++x) toggles[base + (x - e.xa)] = edge_point(e, x, h);
 }
 
 // One wave per (object, window word): pixel p = x*h + y is set in a part when an odd number of the part's points lie at or
@@ -148,6 +173,76 @@ __global__ void __launch_bounds__(256) poly_bits(const int* __restrict__ obj_par
         const uint64_t m = __ballot(inside && set);
         if (lane == 0) win.bits[(size_t)r * win.words_per_row + c] = m;
     }
+}
+
+// ---------------------------------------------------------------- mask-head training targets
+// detectron2 PolygonMasks.crop_and_resize at kTgt x kTgt, one block per RoI: the matched object's vertices are shifted by the
+// box origin and scaled by kTgt / max(extent, 0.1) in f64 (utils/COCO_utils.py crop_and_resize_polygons), then every part goes
+// through the edge rule above.  No scratch and no host-sized shares: a wave owns a part and keeps its points as one word per
+// column in LDS (bit y of column x = position x * kTgt + y; XOR, so a position hit twice cancels as two sorted points would).
+// A pixel is set when an odd number of points lie at or before it: the prefix parity down the columns.  Parts are ORed.
+constexpr int kTgt = 28;
+constexpr double kCoordMax = 2147483648.0 / 5.0 - 1.0;      // utils/coco.py _COORD_MAX
+
+__global__ void __launch_bounds__(256) mask_targets_kernel(const double* __restrict__ xy, const int* __restrict__ part_vert_off,
+                                                           int n_parts, const int* __restrict__ obj_part_off, int n_obj,
+                                                           int n_verts, const float* __restrict__ rois,
+                                                           const int* __restrict__ matched, unsigned char* __restrict__ targets,
+                                                           int* __restrict__ info) {
+    __shared__ unsigned s_tog[4][kTgt];
+    __shared__ unsigned s_acc[kTgt];
+    __shared__ int s_bad;
+    const int row = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    if (tid < kTgt) s_acc[tid] = 0u;
+    if (tid == 0) s_bad = 0;
+    const int obj = matched[row];
+    int p0 = 0, p1 = 0;
+    if (obj >= 0 && obj < n_obj) { p0 = max(obj_part_off[obj], 0); p1 = min(obj_part_off[obj + 1], n_parts); }
+    const double x0 = rois[4 * row], y0 = rois[4 * row + 1];
+    const double bw = (double)rois[4 * row + 2] - x0, bh = (double)rois[4 * row + 3] - y0;
+    const double rw = (double)kTgt / (0.1 > bw ? 0.1 : bw), rh = (double)kTgt / (0.1 > bh ? 0.1 : bh);   // Python's max(extent, 0.1)
+    __syncthreads();
+    for (int q0 = p0; q0 < p1; q0 += 4) {                    // the same trip count in every wave: the barriers are uniform
+        const int q = q0 + wave;
+        if (lane < kTgt) s_tog[wave][lane] = 0u;
+        __syncthreads();
+        if (q < p1) {
+            const int v0 = max(part_vert_off[q], 0), v1 = min(part_vert_off[q + 1], n_verts);
+            for (int j = v0 + lane; j < v1; j += 64) {
+                const int nxt = j + 1 < v1 ? j + 1 : v0;
+                const double ax = (xy[2 * j] - x0) * rw, ay = (xy[2 * j + 1] - y0) * rh;
+                const double bx = (xy[2 * nxt] - x0) * rw, by = (xy[2 * nxt + 1] - y0) * rh;
+                if (!(fabs(ax) <= kCoordMax) || !(fabs(ay) <= kCoordMax) || !(fabs(bx) <= kCoordMax) || !(fabs(by) <= kCoordMax)) {
+                    s_bad = 1;                               // the host path refuses these: the row's bytes are not meaningful
+                    continue;
+                }
+                PolyEdge e = poly_edge(scaled(ax), scaled(ay), scaled(bx), scaled(by), kTgt);
+                if (edge_count(e) == 0) continue;
+                orient(e);
+                for (int x = e.xa; x <= e.xb; ++x) {
+                    const int pos = edge_point(e, x, kTgt);  // x * kTgt + y, y in [0, kTgt]: y == kTgt is column x + 1, bit 0
+                    const int col = pos / kTgt;
+                    if (col < kTgt) atomicXor(&s_tog[wave][col], 1u << (pos - col * kTgt));
+                }
+            }
+        }
+        __syncthreads();
+        if (q < p1 && lane < kTgt) {
+            unsigned carry = 0u;
+            for (int c = 0; c < lane; ++c) carry ^= (unsigned)__popc(s_tog[wave][c]);
+            unsigned m = s_tog[wave][lane];
+            m ^= m << 1; m ^= m << 2; m ^= m << 4; m ^= m << 8; m ^= m << 16;      // bit y = parity of bits 0 .. y
+            if (carry & 1u) m = ~m;
+            atomicOr(&s_acc[lane], m & ((1u << kTgt) - 1u));
+        }
+        __syncthreads();
+    }
+    unsigned char* out = targets + (size_t)row * (kTgt * kTgt);
+    for (int i = tid; i < kTgt * kTgt; i += 256) {
+        const int y = i / kTgt, x = i - y * kTgt;
+        out[i] = (unsigned char)((s_acc[x] >> y) & 1u);
+    }
+    if (tid == 0 && s_bad) info[0] = 1;
 }
 
 // ---------------------------------------------------------------- matching
@@ -441,6 +536,12 @@ void launch_sort(const double* score, const int* seg_off, int n_seg, const int* 
 }  // namespace
 
 extern "C" {
+
+int apse_k_mask_targets(const double* xy, const int* part_vert_off, int n_parts, const int* obj_part_off, int n_obj, int n_verts,
+                        const float* rois, const int* matched, int n, uint8_t* targets, int* info, hipStream_t s) {
+    mask_targets_kernel<<<n, 256, 0, s>>>(xy, part_vert_off, n_parts, obj_part_off, n_obj, n_verts, rois, matched, targets, info);
+    return launched("apse_coco_mask_targets: launch failed");
+}
 
 int apse_coco_box_iou(const int* dt_off, const int* gt_off, const long long* iou_off, int n_groups, int max_dt, int max_gt,
                       const double* dt_box, const double* gt_box, const int* gt_crowd, double* iou, void* stream) {

@@ -651,4 +651,20 @@ int apse_mask_predictor_backward(const float* d, const float* a5, const int* cla
     return launched();
 }
 
+// The targets of sampled proposals: the limits here, the kernel beside the polygon rule it shares (coco_eval.hip).
+int apse_coco_mask_targets(const double* xy, const int* part_vert_off, int n_parts, const int* obj_part_off, int n_obj, int n_verts,
+                      const float* rois, const int* matched, int n, int mask_size, uint8_t* targets, int* info, void* stream) {
+    if (n < 0 || n > APSE_MASK_TRAIN_MAX_N) return invalid("apse_coco_mask_targets: needs 0 <= n <= APSE_MASK_TRAIN_MAX_N (1024) RoIs");
+    if (mask_size != kUp) return invalid("apse_coco_mask_targets: mask_size must be 28");
+    if (n_obj < 0 || n_obj > APSE_COCO_MAX_POLY_OBJECTS || n_parts < 0 || n_parts > APSE_COCO_MAX_POLY_PARTS || n_verts < 0 ||
+        n_verts > APSE_COCO_MAX_POLY_VERTS)
+        return invalid("apse_coco_mask_targets: n_obj, n_parts or n_verts outside [0, APSE_COCO_MAX_POLY_OBJECTS / _PARTS / _VERTS]");
+    if (n == 0) return APSE_OK;
+    if (!rois || !matched || !targets || !info || (n_obj > 0 && !obj_part_off) || (n_parts > 0 && !part_vert_off) ||
+        (n_verts > 0 && !xy))
+        return invalid("apse_coco_mask_targets: null pointer");
+    return apse_k_mask_targets(xy, part_vert_off, n_parts, obj_part_off, n_obj, n_verts, rois, matched, n, targets, info,
+                               (hipStream_t)stream);
+}
+
 }  // extern "C"

@@ -9,6 +9,8 @@ dcnn/scripts/train/finetune_segmentation.py leans on (dataset dictionaries, ``Po
 * ``detectron2_dataset_to_coco``: the dictionaries back to a COCO dataset (for ``utils.coco.COCO.from_dataset`` / ``COCOeval``).
 * ``mask_targets``: ``PolygonMasks.crop_and_resize`` (``rasterize_polygons_within_box``) at 28 x 28: the polygon transform on the
   host in float64, the rasterisation by ``apse_coco_poly_to_bits`` (equal to pycocotools ``frPyObjects`` + ``merge``).
+* ``DevicePolygons`` / ``mask_targets_device``: the same targets for boxes that are new every step (the joint loop's sampled
+  proposals), in one launch of ``apse_coco_mask_targets`` against an image's polygons uploaded once; ``select_mask_rows`` picks the rows.
 * ``MaskTrainLoader``: batches of ``IMS_PER_BATCH`` images -> RoI features of the ground-truth boxes from the frozen backbone
   (test-size resize with an optional seeded horizontal flip; or, with ``augment`` / ``min_sizes``, the reference mapper's
   multi-scale resize, flip and colour chain on the GPU: utils/augment.py), classes and 28 x 28 targets.  Ground truths appear once: detectron2 appends
@@ -29,11 +31,13 @@ XYWH_ABS = 1          # detectron2 BoxMode.XYWH_ABS
 
 
 def generate_coco_dataset_dictionaries(json_file, imgfolder, allowed_classes=None, category_mapping=None,
-                                       precomputed_proposals=True):
+                                       precomputed_proposals=True, keep_box_only=False):
     """-> list of {file_name, image_id, height, width, annotations: [{bbox (XYWH), bbox_mode, category_id, segmentation, iscrowd}],
     proposal_boxes (XYXY f32 [k, 4]), proposal_objectness_logits, proposal_bbox_mode}.  ``allowed_classes``: category NAMES to
     keep (None: all); ``category_mapping``: {json category id: training class index} (None: the sorted kept ids -> 0..K-1).
-    Images left without annotations are dropped, as the reference does."""
+    Images left without annotations are dropped, as the reference does.  An annotation without a segmentation is dropped too,
+    unless ``keep_box_only`` (the joint loop with the mask head, where box-only data feeds the RPN and box losses): it is then
+    kept with ``segmentation`` []."""
     with open(json_file) as fh:
         data = json.load(fh)
     names = {c["id"]: c["name"] for c in data["categories"]}
@@ -54,7 +58,9 @@ def generate_coco_dataset_dictionaries(json_file, imgfolder, allowed_classes=Non
                 raise ValueError("annotation %s: RLE segmentations are not supported for mask-head training (non-crowd COCO "
                                  "annotations are polygons)" % ann.get("id"))
             if not seg:
-                continue
+                if not keep_box_only:
+                    continue
+                seg = []
             anns.append({"bbox": [float(v) for v in ann["bbox"]], "bbox_mode": XYWH_ABS,
                          "category_id": int(category_mapping[ann["category_id"]]),
                          "segmentation": [list(map(float, p)) for p in seg],          # the list itself (not the reference's 1-tuple)
@@ -127,6 +133,72 @@ def mask_targets(polygons_per_roi, boxes, device, mask_size=MASK_SIZE):
     dense = cocomod.windows_to_dense(windows, mask_size, mask_size)
     del keep
     return torch.from_numpy(dense.astype(np.uint8)).to(device)
+
+
+class DevicePolygons:
+    """The polygons of one image on the device, as ``apse_coco_mask_targets`` reads them: xy f64 [n_verts][2], part_vert_off int32
+    [n_parts + 1], obj_part_off int32 [n_obj + 1] (the arrays of ``coco.poly_layout`` without the edge shares, rects and windows).
+    ``polygons_per_object``: per object a list of flat x, y lists in resized-image pixels; every part is cut to whole pairs, as
+    ``crop_and_resize_polygons`` cuts it.  ``parts`` (host int64 [n_obj]) counts each object's parts."""
+
+    def __init__(self, polygons_per_object, device):
+        parts = [np.asarray(p, np.float64).reshape(-1)[:2 * (len(p) // 2)] for ps in polygons_per_object for p in ps]
+        self.parts = np.array([len(ps) for ps in polygons_per_object], np.int64)
+        part_vert_off = np.zeros(len(parts) + 1, np.int64)
+        np.cumsum([len(p) // 2 for p in parts], out=part_vert_off[1:])
+        obj_part_off = np.zeros(len(self.parts) + 1, np.int64)
+        np.cumsum(self.parts, out=obj_part_off[1:])
+        xy = np.concatenate(parts) if parts else np.zeros(0, np.float64)
+        self.n_obj, self.n_parts, self.n_verts = len(self.parts), len(parts), int(part_vert_off[-1])
+        self.device = torch.device(device)
+        self.xy = torch.from_numpy(np.ascontiguousarray(xy, np.float64)).to(self.device)
+        self.part_vert_off = torch.from_numpy(part_vert_off.astype(np.int32)).to(self.device)
+        self.obj_part_off = torch.from_numpy(obj_part_off.astype(np.int32)).to(self.device)
+
+
+def mask_targets_device(polygons, rois, matched, mask_size=MASK_SIZE, out=None):
+    """``mask_targets`` for proposals that are new every step (``apse_coco_mask_targets``): ``polygons`` a DevicePolygons of the image,
+    ``rois`` f32 [n][4] and ``matched`` int32 [n] (each row's object) on the device -> uint8 [n][mask_size][mask_size] on the device,
+    byte for byte ``mask_targets([polygons of matched[r]], rois)``.  One launch; the only host step is the read of the info word
+    afterwards, which raises the host path's ValueError for coordinates outside the rasteriser's range.  ``out``: a uint8 buffer
+    of at least n rows to write into (rows past n stay untouched); the result is its first n rows."""
+    from .. import _lib
+    from ..networks.head_base import _check
+    dev = polygons.device
+    rois = torch.as_tensor(rois, dtype=torch.float32).reshape(-1, 4).to(dev).contiguous()
+    matched = torch.as_tensor(matched).reshape(-1).to(dev, torch.int32).contiguous()
+    n = int(rois.shape[0])
+    if int(matched.shape[0]) != n:
+        raise ValueError("mask_targets_device: %d boxes, %d matched indices" % (n, int(matched.shape[0])))
+    if out is None:
+        out = torch.empty((n, mask_size, mask_size), dtype=torch.uint8, device=dev)
+    elif out.dtype != torch.uint8 or not out.is_contiguous() or out.dim() != 3 or out.shape[0] < n or \
+            tuple(out.shape[1:]) != (mask_size, mask_size) or out.device != rois.device:
+        raise ValueError("mask_targets_device: out must be a contiguous uint8 [>= n][%d][%d] tensor on the device" % (mask_size, mask_size))
+    info = torch.zeros(1, dtype=torch.int32, device=dev)
+    _check(_lib.load().apse_coco_mask_targets(_lib.ptr(polygons.xy), _lib.ptr(polygons.part_vert_off), polygons.n_parts,
+                                         _lib.ptr(polygons.obj_part_off), polygons.n_obj, polygons.n_verts, _lib.ptr(rois),
+                                         _lib.ptr(matched), n, int(mask_size), _lib.ptr(out), _lib.ptr(info), _lib.stream_ptr()),
+           "apse_coco_mask_targets")
+    if n and int(info.cpu()[0]):
+        raise ValueError("polygon coordinates must be finite and below %.0f in magnitude" % cocomod._COORD_MAX)
+    return out[:n]
+
+
+def select_mask_rows(labels, matched, parts_per_gt, num_classes):
+    """detectron2's ``select_foreground_proposals`` on the sampled box rows of one image, then the rows whose ground truth has a
+    polygon: ``labels`` [n] (num_classes = background, -1 = ignored), ``matched`` [n] ground-truth index per row, ``parts_per_gt``
+    [G] polygon parts per ground truth, all on the host.  -> (kept row indices int64, in sampling order; the number of foreground
+    rows dropped for lack of polygons)."""
+    labels = np.asarray(labels).reshape(-1)
+    matched = np.asarray(matched).reshape(-1).astype(np.int64)
+    parts = np.asarray(parts_per_gt, np.int64).reshape(-1)
+    fg = np.nonzero((labels != -1) & (labels != num_classes))[0]
+    m = matched[fg]
+    inside = (m >= 0) & (m < len(parts))
+    has = np.zeros(len(fg), bool)
+    has[inside] = parts[m[inside]] > 0
+    return fg[has].astype(np.int64), int(len(fg) - has.sum())
 
 
 def flip_annotations(boxes, polygons_per_roi, width):
@@ -206,7 +278,7 @@ class MaskTrainLoader:
             raise ValueError("%s is %dx%d, the annotations say %dx%d" % (d["file_name"], H, W, d["height"], d["width"]))
         boxes = np.array([[a["bbox"][0], a["bbox"][1], a["bbox"][0] + a["bbox"][2], a["bbox"][1] + a["bbox"][3]]
                           for a in d["annotations"]], np.float64).reshape(-1, 4)
-        polys = [a["segmentation"] for a in d["annotations"]]
+        polys = [a.get("segmentation") or [] for a in d["annotations"]]          # a box-only annotation: no parts
         classes = torch.tensor([a["category_id"] for a in d["annotations"]], dtype=torch.int64)
         return frame, boxes, polys, classes
 

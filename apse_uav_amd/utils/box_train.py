@@ -23,12 +23,13 @@ def subsample_labels(labels, num_samples, positive_fraction, bg_label, generator
 
 
 def label_and_sample_proposals(proposals, gt_boxes, gt_classes, num_classes, batch_size_per_image=512, positive_fraction=0.25,
-                               generator=None, iou_thresh=0.5):
+                               generator=None, iou_thresh=0.5, return_index=False):
     """ROIHeads.label_and_sample_proposals for one image, on the device.  proposals f32 [P][4], gt_boxes f32 [G][4], gt_classes
     [G], all in resized-image pixels.  The ground-truth boxes are appended after the proposals (PROPOSAL_APPEND_GT),
     apse_box_match labels the candidates, subsample_labels draws the rows, foreground first.
     -> (boxes f32 [n][4], labels int32 [n] (num_classes = background), matched ground-truth boxes f32 [n][4] (zeros without a
-    ground truth), (num_fg, num_bg))."""
+    ground truth), (num_fg, num_bg)); with ``return_index`` also the matched ground-truth index of every row, int32 [n] (-1
+    without a ground truth), as the last entry."""
     dev = proposals.device
     if not proposals.is_cuda:
         raise bh._lib.ApseError("label_and_sample_proposals needs GPU tensors (no CPU fallback)")
@@ -39,7 +40,10 @@ def label_and_sample_proposals(proposals, gt_boxes, gt_classes, num_classes, bat
     pos, neg = subsample_labels(labels, batch_size_per_image, positive_fraction, num_classes, generator)
     sel = torch.cat([pos, neg])
     matched = gt[idx[sel].long()] if gt.shape[0] else torch.zeros((sel.numel(), 4), dtype=torch.float32, device=dev)
-    return cand[sel], labels[sel], matched, (int(pos.numel()), int(neg.numel()))
+    out = (cand[sel], labels[sel], matched, (int(pos.numel()), int(neg.numel())))
+    if return_index:
+        out += (idx[sel] if gt.shape[0] else torch.full((sel.numel(),), -1, dtype=torch.int32, device=dev),)
+    return out
 
 
 class SamplingLoader(MaskTrainLoader):

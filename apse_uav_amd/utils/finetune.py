@@ -117,8 +117,9 @@ def adapt_detector(detector, K):
     return out, True
 
 
-def bbox_scores(pred, dicts, coco_gt):
-    """bbox COCOeval stats (12 numbers) of the predictor's detections on ``dicts``; None when there is nothing to score."""
+def detection_scores(pred, dicts, coco_gt, iou_types=("bbox",)):
+    """COCOeval stats (12 numbers per entry of ``iou_types``: "bbox", "segm") of the predictor's detections on ``dicts``, from
+    one pass over the images -- the masks are those of the predictor's own boxes; None when there is nothing to score."""
     from PIL import Image
     from .coco_eval import CocoEvaluator
     ev = CocoEvaluator(coco_gt)
@@ -130,7 +131,13 @@ def bbox_scores(pred, dicts, coco_gt):
         total += len(inst)
     if total == 0:
         return None
-    return [float(v) for v in ev.evaluate("bbox").stats]
+    return [[float(v) for v in ev.evaluate(t).stats] for t in iou_types]
+
+
+def bbox_scores(pred, dicts, coco_gt):
+    """bbox COCOeval stats (12 numbers) of the predictor's detections on ``dicts``; None when there is nothing to score."""
+    res = detection_scores(pred, dicts, coco_gt)
+    return None if res is None else res[0]
 
 
 def proposal_scores(pred, dicts):
@@ -151,7 +158,8 @@ class Task:
     summary_num_classes = True          # the summary has "num_classes"
     summary_predictor = False           # the summary has "predictor"
     coco_ground_truth = True            # do_test gets the held-out images as a COCO object (else None)
-    precomputed_proposals = False       # generate_coco_dataset_dictionaries' last argument
+    precomputed_proposals = False       # generate_coco_dataset_dictionaries' precomputed_proposals
+    keep_box_only = False               # ... and its keep_box_only: annotations without a segmentation stay
     context_cache = 4                   # training_cfg's
     best_needs_score = False            # _bestAP / _bestAR: False = also written when nothing was scored or the file is missing
     resume_takes_detector = True        # --resume: the frozen part comes from the checkpoint, not from the start detector
@@ -215,7 +223,8 @@ def run(task, args, detector):
     from . import COCO_utils
     from .coco import COCO
 
-    dicts = COCO_utils.generate_coco_dataset_dictionaries(args.annotations, args.images, args.classes, None, task.precomputed_proposals)
+    dicts = COCO_utils.generate_coco_dataset_dictionaries(args.annotations, args.images, args.classes, None, task.precomputed_proposals,
+                                                          task.keep_box_only)
     K = task.num_classes(args, detector, dicts)
     cfg = training_cfg(K, task.context_cache)
     if is_c4(cfg):

@@ -1,12 +1,16 @@
 """The data side of joint RPN / box-head training (tools/finetune_uav.py): one backbone run per image feeds both heads, and the
 box head's proposals come from the RPN head as it is at that step (``TrackRCNN.set_rpn_head`` follows every optimiser step), at
-detectron2's training limits (``TrackRCNN.train_proposals``).
+detectron2's training limits (``TrackRCNN.train_proposals``).  With ``mask=True`` the sampled foreground proposals also become
+mask-head rows, their targets made on the device (``apse_coco_mask_targets``).
 """
+import numpy as np
 import torch
 
 from ..networks import box_head as bh
+from ..networks import mask_head as mh
 from ..networks import rpn_head as rh
 from .box_train import SamplingLoader, label_and_sample_proposals
+from .COCO_utils import DevicePolygons, mask_targets_device, select_mask_rows
 from .rpn_train import label_and_sample_anchors
 
 
@@ -45,6 +49,16 @@ def box_losses_chunked(head, feats, labels, prop_boxes, gt_boxes, rows_per_image
     return out
 
 
+def check_mask_rows(ims_per_batch, box_batch_size_per_image, box_positive_fraction, max_rows=mh.MAX_ROIS):
+    """The most mask rows a batch can have -- every image's foreground quota, floor(batch size x positive fraction) -- against the
+    rows ``MaskHead`` takes in one step; raises ValueError past them.  -> that bound."""
+    bound = int(ims_per_batch) * int(int(box_batch_size_per_image) * float(box_positive_fraction))
+    if bound > max_rows:
+        raise ValueError("%d images x %d foreground RoIs exceed the %d mask rows of one step (APSE_MASK_TRAIN_MAX_N)"
+                         % (int(ims_per_batch), int(int(box_batch_size_per_image) * float(box_positive_fraction)), max_rows))
+    return bound
+
+
 class JointTrainLoader(SamplingLoader):
     """Yields (rpn, box) per batch of ``ims_per_batch`` images, endlessly, in a seeded shuffled order:
 
@@ -52,6 +66,14 @@ class JointTrainLoader(SamplingLoader):
       of RpnTrainLoader;
     * box = (roi_features [m][7][7][256], labels int32 [m], proposal_boxes f32 [m][4], gt_boxes f32 [m][4]), the tuple of
       BoxTrainLoader; ``last_box_rows`` holds m per image (m may exceed one step's rows: ``box_losses_chunked``).
+
+    With ``mask=True`` it yields (rpn, box, mask): mask = (roi_features f32 [f][14][14][256], classes int64 [f] on the host, targets
+    uint8 [f][28][28]), the tuple of MaskTrainLoader, for the sampled box rows that are foreground (label < K, in sampling order:
+    detectron2's ``select_foreground_proposals``) and whose matched ground truth has at least one polygon part.  The features are
+    ``mask_roi_features`` of those PROPOSAL boxes and the targets ``apse_coco_mask_targets`` of the matched polygons cropped to them
+    (``mask_rcnn_loss``), against the image's polygons uploaded once.  An image or annotation without polygons gives RPN and box
+    rows only.  ``last_mask_rows`` holds f per image and ``last_mask_skipped`` the foreground rows dropped for lack of polygons.
+    The mask rows draw no random numbers: rpn and box are the same bits with ``mask`` on and off, and so is ``state_dict``.
 
     ``model``: a TrackRCNN (FPN, f32).  Per image: the image and annotation path of MaskTrainLoader, the frozen backbone once,
     then ``label_and_sample_anchors`` and ``rpn_patches`` for the RPN rows, then ``train_proposals`` on the context's current RPN
@@ -61,9 +83,13 @@ class JointTrainLoader(SamplingLoader):
 
     def __init__(self, dicts, model, ims_per_batch=2, seed=0, flip=False, augment=False, min_sizes=None, max_size=None,
                  sampling="choice", num_classes=None, rpn_batch_size_per_image=256, rpn_positive_fraction=0.5,
-                 rpn_iou_thresholds=(0.3, 0.7), box_batch_size_per_image=512, box_positive_fraction=0.25, box_iou_thresh=0.5):
+                 rpn_iou_thresholds=(0.3, 0.7), box_batch_size_per_image=512, box_positive_fraction=0.25, box_iou_thresh=0.5,
+                 mask=False):
         if getattr(model, "c4", False):
             raise NotImplementedError("joint detection-head training covers FPN models (p2 .. p6)")
+        self.mask = bool(mask)
+        if self.mask:
+            check_mask_rows(ims_per_batch, box_batch_size_per_image, box_positive_fraction)
         super().__init__(dicts, model, ims_per_batch, seed, flip, False, bh.MAX_ROIS, augment, min_sizes, max_size, sampling)
         self.num_classes = int(num_classes if num_classes is not None else model.cfg.MODEL.ROI_HEADS.NUM_CLASSES)
         self.rpn_batch_size_per_image, self.rpn_positive_fraction = int(rpn_batch_size_per_image), float(rpn_positive_fraction)
@@ -80,6 +106,8 @@ class JointTrainLoader(SamplingLoader):
         self.last_box_counts = []             # (num_fg, num_bg) per image of the last batch
         self.last_box_rows = []               # box rows per image of the last batch
         self.last_proposals = []              # the training proposals (boxes [count][4]) per image of the last batch
+        self.last_mask_rows = []              # mask=True: mask rows per image of the last batch
+        self.last_mask_skipped = []           # mask=True: foreground rows without polygons per image of the last batch
 
     def _sample(self, boxes, polys, classes, d):
         model = self.model
@@ -88,11 +116,28 @@ class JointTrainLoader(SamplingLoader):
                                                                    self.rpn_generator, self.rpn_iou_thresholds)
         patches, slots, anchor_boxes, _ = model.rpn_patches(sel)
         props = model.train_proposals(1)[0][0]
-        sb, blabels, bmatched, bcounts = label_and_sample_proposals(props, gt, cls, self.num_classes, self.box_batch_size_per_image,
-                                                                    self.box_positive_fraction, self.box_generator, self.box_iou_thresh)
+        sampled = label_and_sample_proposals(props, gt, cls, self.num_classes, self.box_batch_size_per_image, self.box_positive_fraction,
+                                             self.box_generator, self.box_iou_thresh, return_index=self.mask)
+        sb, blabels, bmatched, bcounts = sampled[:4]
         rpn = (patches, slots, rlabels, anchor_boxes, rmatched)
         box = (model.box_roi_features(sb), blabels, sb, bmatched)
-        return rpn, box, rcounts, bcounts, props
+        if not self.mask:
+            return rpn, box, rcounts, bcounts, props
+        return rpn, box, rcounts, bcounts, props, self._mask_rows(sb, blabels, sampled[4], polys, d)
+
+    def _mask_rows(self, boxes, labels, matched, polys, d):
+        """The mask item of one image from its sampled box rows: ((features, classes, targets), rows skipped).  ``matched`` indexes
+        the ground truths ``ground_truth`` kept (the non-crowd annotations), so the polygons are filtered the same way."""
+        model = self.model
+        gt_polys = [polys[i] for i, a in enumerate(d["annotations"]) if not a.get("iscrowd", 0)]
+        poly_dev = DevicePolygons(gt_polys, model.device)
+        labels_host = labels.cpu().numpy()
+        rows, skipped = select_mask_rows(labels_host, matched.cpu().numpy(), poly_dev.parts, self.num_classes)
+        rows_dev = torch.from_numpy(rows).to(model.device)
+        mboxes = boxes[rows_dev].contiguous()
+        targets = mask_targets_device(poly_dev, mboxes, matched[rows_dev])
+        classes = torch.from_numpy(labels_host[rows].astype(np.int64))
+        return (model.mask_roi_features(mboxes), classes, targets), skipped
 
     def __next__(self):
         items = self.next_items()
@@ -102,4 +147,8 @@ class JointTrainLoader(SamplingLoader):
         self.last_proposals = [i[4] for i in items]
         rpn = tuple(torch.cat([i[0][k] for i in items]) for k in range(5))
         box = tuple(torch.cat([i[1][k] for i in items]) for k in range(4))
-        return rpn, box
+        if not self.mask:
+            return rpn, box
+        self.last_mask_rows = [int(i[5][0][1].shape[0]) for i in items]
+        self.last_mask_skipped = [i[5][1] for i in items]
+        return rpn, box, tuple(torch.cat([i[5][0][k] for i in items]) for k in range(3))

@@ -704,6 +704,22 @@ int apse_mask_loss_backward(const float* logits_dev, int K, const int* classes_d
  * pre-activation), dw [K][256] and db [K] (classes without a RoI: exactly 0).  a5 = the deconvolution's output. */
 int apse_mask_predictor_backward(const float* d_dev, const float* a5_dev, const int* classes_dev, const float* w_pred_dev, int n, int K,
                                  float* g5_dev, float* dw_dev, float* db_dev, float* ws, size_t ws_bytes, void* stream);
+/* The mask targets of sampled proposals: detectron2's PolygonMasks.crop_and_resize(boxes, 28) of mask_rcnn_loss on the device,
+ * byte for byte what utils/COCO_utils.py mask_targets gives for the same boxes and polygons.  The polygons of ONE image, uploaded
+ * once: object i owns parts obj_part_off[i] .. obj_part_off[i + 1] (int [n_obj + 1]); part p owns vertices part_vert_off[p] ..
+ * part_vert_off[p + 1] (int [n_parts + 1]) of xy [n_verts][2] (f64, x then y, resized-image pixels), closed back to its first
+ * vertex.  Row r: the box rois_dev[r] (f32 x1,y1,x2,y2) goes to f64 exactly; the vertices of object matched_dev[r] become
+ * ((x - x1) * (28 / max(x2 - x1, 0.1)), (y - y1) * (28 / max(y2 - y1, 0.1))) in f64 without contraction; every part is then
+ * rasterised by the rule of apse_coco_poly_to_bits (pycocotools rleFrPoly at h = w = 28) and the parts are ORed.
+ * targets_dev u8 [n][28][28] (row y, column x): 1 inside, 0 elsewhere; every byte of the n rows is written and nothing past them.
+ * An object without parts, or matched_dev[r] outside 0 .. n_obj - 1, gives an all-zero row.  A row with a scaled coordinate that
+ * is not finite or above 2^31 / 5 - 1 in magnitude sets info_dev[0] = 1 (the caller zeroes it first) and its bytes are not
+ * meaningful.  One launch, one block per row; no scratch, no allocation, no float atomics; integer XOR / OR only, so two calls
+ * give the same bytes.  0 <= n <= APSE_MASK_TRAIN_MAX_N (n = 0 enqueues nothing), mask_size == 28 and the object / part / vertex
+ * counts within the APSE_COCO_MAX_POLY_* limits, else APSE_E_INVALID before any launch. */
+int apse_coco_mask_targets(const double* xy_dev, const int* part_vert_off_dev, int n_parts, const int* obj_part_off_dev, int n_obj,
+                      int n_verts, const float* rois_dev, const int* matched_dev, int n, int mask_size, uint8_t* targets_dev,
+                      int* info_dev, void* stream);
 
 /* ---- Box-head training (csrc/box_train.hip): the f32 steps of fine-tuning roi_heads.box_head.fc1 / fc2 and
  * roi_heads.box_predictor.cls_score / bbox_pred of a frozen FPN detector (dcnn/scripts/train/finetune_uav.py): proposal labelling,
