@@ -57,6 +57,7 @@ struct ConvParams {
     int x_st, res_st, y_st;   // storage type of x / res / y: 0 f32, 1 bf16, 2 f16 (pointers are then 16-bit element arrays)
     int no_stream;            // 1: keep this launch on the tiled kernel (a caller forcing a tile shape: tests, sweeps)
     const float* wu;          // != nullptr: Winograd F(2x2,3x3) filters [Cin/8][16][Cout][8] -> the layer runs as conv_winograd_f32
+    int wino_geom;            // block geometry of conv_winograd_f32: 0 = 16 x 4 tiles (32 x 8 output pixels), 1 = 8 x 8 tiles (16 x 16)
 };
 
 // cfg: 0=128x128 1=64x64 2=128x32 3=128x64.  ev0/ev1 (optional) are recorded right before / after the
@@ -82,7 +83,9 @@ int apse_conv_effective_cfg(const ConvParams& p, int cfg);
 // conv_winograd.hip: fused f32 Winograd F(2x2,3x3) for named 3x3 layers of the f32 plan (profiled under the slot of the tiled
 // config the layer would otherwise run, with its algorithmic FLOPs).  max_items: the most images a launch covers.
 bool apse_conv_winograd_ok(const ConvParams& p, int max_items);
-int apse_conv_winograd_blocks(const ConvParams& p);     // blocks per image
+int apse_conv_winograd_blocks(const ConvParams& p);     // blocks per image and split, in geometry p.wino_geom
+// p.splitk > 1: a Cin split into p.ws slabs, followed by conv_splitk_reduce4 (conv_igemm.hip)
+void apse_launch_splitk_reduce4(const ConvParams& p, hipStream_t s);
 int apse_launch_conv_winograd(const ConvParams& p, hipStream_t s, hipEvent_t ev0 = nullptr, hipEvent_t ev1 = nullptr);
 typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
 

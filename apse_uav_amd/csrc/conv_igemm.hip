@@ -725,6 +725,13 @@ __global__ __launch_bounds__(256) void conv_splitk_reduce(const ConvParams p) {
     }
 }
 
+// The four-column reduce for another kernel's slabs (conv_winograd.hip): p.ws holds [splitk][M][Cout], plain NHWC output.
+void apse_launch_splitk_reduce4(const ConvParams& p, hipStream_t s) {
+    int blocks = (int)(((size_t)p.M * p.Cout / 4 + 255) / 256);
+    if (blocks > 4096) blocks = 4096;
+    hipLaunchKernelGGL(conv_splitk_reduce4, dim3(blocks), dim3(256), 0, s, p);
+}
+
 template <int WM, int WN, int TM, int TN, int KS, int XT, int WK = 1, int PR = 0>
 static int launch_cfg_x(const ConvParams& p, hipStream_t s, hipEvent_t ev0, hipEvent_t ev1) {
     constexpr int BM = WM * TM * 32, BN = WN * TN * 32;

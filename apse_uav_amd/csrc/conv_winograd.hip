@@ -1,7 +1,8 @@
 // Fused f32 Winograd F(2x2, 3x3) convolution for gfx950 (CDNA4), exact-f32 MFMA (v_mfma_f32_32x32x2_f32).
 //
-// Takes the 3x3 / stride 1 / pad 1 layers of the f32 mode that the plan names (FPN outputs p2 / p3, RPN conv at p2 / p3,
-// detector.hip add_conv).  16 instead of 36 multiplies per 2x2 output block: 2.25x fewer matrix-pipe FLOPs.
+// Takes the 3x3 / stride 1 / pad 1 layers of the f32 mode that the plan names (FPN outputs p2 / p3, RPN conv at p2 / p3 and, in
+// plans of large frames, the trunk's conv2 layers and the p4 pair: plan.hip add_conv).  16 instead of 36 multiplies per 2x2
+// output block: 2.25x fewer matrix-pipe FLOPs.
 //
 //   U[xi][co][ci] = (G g G^T)[i][j]   filters, transformed once on the host (float64, rounded once), xi = 4 i + j
 //   V[xi][t][ci]  = (B^T d B)[i][j]   input tile t (4x4 pixels, stride 2), computed here on VALU per k-slice
@@ -10,7 +11,7 @@
 // Nothing transformed goes through HBM: V lives in LDS for one k-slice, M in accumulators until the epilogue.
 //
 // Block = 512 threads = 8 waves, one block per CU (128 KiB LDS).  Block tile = 64 Winograd tiles (WTR x WTC tile rows x
-// columns = 32 x 8 output pixels) x 64 output channels.  Wave w owns xi = 2w, 2w+1: 2 xi x 2 M-tiles x 2 N-tiles of 32x32
+// columns: 16 x 4 = 32 x 8 output pixels, or 8 x 8 = 16 x 16) x 64 output channels.  Wave w owns xi = 2w, 2w+1: 2 xi x 2 M-tiles x 2 N-tiles of 32x32
 // = 128 accumulators per lane.  Per k-slice of 8 channels (double-buffered, one barrier):
 //   - 512 threads = (tile t, transform row i, channel group cg of 4): two input rows x 4 pixels x 4 channels through a
 //     buffer descriptor (out-of-image taps get an offset past the range: zeros, i.e. the padding and partial tiles at odd
@@ -26,12 +27,12 @@
 // other, and the transforms keep their operation order: the bits are those of the unscheduled loop.
 // Epilogue: per 32-channel half of the N tile the accumulators go to LDS as [16][64 t][32 co]; each thread then owns one
 // tile x 4 channels, applies A^T . A, bias, ReLU and stores the 2x2 pixels as dwordx4 (pixels past H / W are dropped).
-// No split-K, no atomics: a tile's result depends on nothing but its inputs (not on batch, grid or history).
+// No atomics: a tile's result depends on nothing but its inputs (not on batch, grid or history).  The Cin split (SPLIT, below)
+// writes partial tiles into workspace slabs that conv_splitk_reduce4 sums in a fixed order.
 #include "apse_common.h"
 
 namespace {
-constexpr int WTR = 16, WTC = 4;          // Winograd tiles per block: rows x columns (64 tiles = 32 x 8 output pixels)
-constexpr int WT = WTR * WTC;
+constexpr int WT = 64;                    // Winograd tiles per block: WTR rows x WTC columns, a template parameter of the kernel
 constexpr int WN = 64;                    // output channels per block
 constexpr int KC = 8;                     // channels per k-slice
 constexpr int NTHR = 512;
@@ -45,7 +46,14 @@ static_assert(WN == WT, "V and U slices share one size");
 static_assert((size_t)16 * WT * 32 * sizeof(float) <= WINO_LDS, "epilogue chunk must fit the staging LDS");
 }
 
+// <WTR, WTC>: block geometry, <16, 4> = 32 x 8 output pixels (geometry 0), <8, 8> = 16 x 16 (geometry 1: fewer blocks on small
+// maps, 18 instead of 22 at 48 x 84).  SPLIT: the Cin split.  blockIdx.y = z multiplies only the k-slices [s_begin, s_end) of its
+// share (whole 8-channel slices divided as evenly as possible, larger shares first), applies A^T . A but neither bias nor ReLU and
+// writes its 2x2 pixels into slab z of the workspace (p.ws + z M Cout, dense NHWC, ld = Cout): the layout conv_splitk_reduce4
+// sums, z ascending, then bias, then ReLU.  The output transform is linear, so the partial Y tiles add up to the whole one.
+template <int WTR, int WTC, bool SPLIT>
 __global__ __launch_bounds__(NTHR) void conv_winograd_f32(const ConvParams p) {
+    static_assert(WTR * WTC == WT, "64 tiles per block");
     extern __shared__ __attribute__((aligned(16))) char smem[];
     float* Vs = reinterpret_cast<float*>(smem);          // [2][16][WT][KC]
     float* Us = Vs + 2 * SLICE_F;                         // [2][16][WN][KC]
@@ -67,7 +75,13 @@ __global__ __launch_bounds__(NTHR) void conv_winograd_f32(const ConvParams p) {
     const int b = rest / tiles_y;
     const int oy0 = by * 2 * WTR, ox0 = bx * 2 * WTC, n0 = nb * WN;
     const int C = 1 << p.cin_log2;
-    const int nsteps = C / KC;
+    int s_begin = 0, s_end = C / KC;
+    if constexpr (SPLIT) {
+        const int z = blockIdx.y, share = s_end / p.splitk, extra = s_end % p.splitk;
+        s_begin = z * share + (z < extra ? z : extra);
+        s_end = s_begin + share + (z < extra ? 1 : 0);
+    }
+    const int nsteps = s_end - s_begin;
 
     // ---- staging roles
     // input: thread = (transform row i, tile t, channel group cg); rows ra / rb of the 4x4 tile give row i of B^T d.  The row
@@ -98,9 +112,10 @@ __global__ __launch_bounds__(NTHR) void conv_winograd_f32(const ConvParams p) {
     }
     // U: four 16-byte pieces per thread, piece q = tid + 512 k: xi = q >> 7, row co = (q >> 1) & 63, half q & 1.  Read through
     // a descriptor of the whole U (16 * Cout * Cin floats, slice-major): a slice past the last one is out of its range
-    const __amdgpu_buffer_rsrc_t ursrc =
-        __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(p.wu), 0, (int)((((unsigned)(16 * p.Cout)) << p.cin_log2) * 4u), 0x00020000);
+    // (of a split: of the slices in front of s_end, so that the fetches past the share read nothing of the next split's)
     const unsigned ustep = (unsigned)(16 * p.Cout * KC * 4);     // bytes per k-slice of the global U
+    const __amdgpu_buffer_rsrc_t ursrc = __builtin_amdgcn_make_buffer_rsrc(
+        const_cast<float*>(p.wu), 0, SPLIT ? (int)((unsigned)s_end * ustep) : (int)((((unsigned)(16 * p.Cout)) << p.cin_log2) * 4u), 0x00020000);
     unsigned uoff[4], ulds[4];
 #pragma unroll
     for (int k = 0; k < 4; ++k) {
@@ -115,12 +130,12 @@ __global__ __launch_bounds__(NTHR) void conv_winograd_f32(const ConvParams p) {
     // of the slice before (see the loop)
     f32x4 xr[2][4], ur[4];
     auto fetch_u = [&](int s) {
-        const unsigned kb = (unsigned)s * ustep;
+        const unsigned kb = (unsigned)(s_begin + s) * ustep;
 #pragma unroll
         for (int k = 0; k < 4; ++k) ur[k] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(ursrc, (int)(uoff[k] + kb), 0, 0));
     };
     auto fetch_x = [&](int s) {
-        const unsigned kb = (unsigned)(s * KC * 4);
+        const unsigned kb = (unsigned)((s_begin + s) * KC * 4);
         const __amdgpu_buffer_rsrc_t rs = s < nsteps ? xrsrc : xnone;
 #pragma unroll
         for (int r = 0; r < 2; ++r)
@@ -233,6 +248,20 @@ __global__ __launch_bounds__(NTHR) void conv_winograd_f32(const ConvParams p) {
             s1[c] = m[4 + c] - m[8 + c] - m[12 + c];
         }
         const int co = n0 + 32 * j + 4 * eg;
+        if constexpr (SPLIT) {
+            // a partial sum: plain stores (the reduce kernel reads the slabs next), bias and ReLU are the reduce's
+            float* slab = p.ws + (size_t)blockIdx.y * p.M * p.Cout;
+#pragma unroll
+            for (int dy = 0; dy < 2; ++dy)
+#pragma unroll
+                for (int dx = 0; dx < 2; ++dx) {
+                    const f32x4 val = dy ? (dx ? s1[1] - s1[2] - s1[3] : s1[0] + s1[1] + s1[2]) : (dx ? s0[1] - s0[2] - s0[3] : s0[0] + s0[1] + s0[2]);
+                    if (oy + dy < p.OH && ox + dx < p.OW)
+                        *reinterpret_cast<f32x4*>(slab + ((size_t)(b * p.OH + oy + dy) * p.OW + ox + dx) * p.Cout + co) = val;
+                }
+            __syncthreads();
+            continue;
+        }
         const f32x4 bias4 = p.bias ? *reinterpret_cast<const f32x4*>(p.bias + co) : f32x4{0.f, 0.f, 0.f, 0.f};
         f32x4 y[2][2] = {{s0[0] + s0[1] + s0[2], s0[1] - s0[2] - s0[3]}, {s1[0] + s1[1] + s1[2], s1[1] - s1[2] - s1[3]}};
 #pragma unroll
@@ -252,29 +281,44 @@ __global__ __launch_bounds__(NTHR) void conv_winograd_f32(const ConvParams p) {
 }
 
 // the layers this kernel handles: f32 in / out, 3x3 / stride 1 / pad 1, whole 64-channel N tiles, 8-channel k-slices, plain
-// NHWC output with 16-byte aligned rows, no residual, activations below 2 GiB (32-bit descriptor offsets, see xoff)
+// NHWC output with 16-byte aligned rows, no residual, activations below 2 GiB (32-bit descriptor offsets, see xoff); a Cin
+// split of at most one share per k-slice, block geometry 0 (<16, 4>) or 1 (<8, 8>)
 bool apse_conv_winograd_ok(const ConvParams& p, int max_items) {
     return p.prec == 0 && p.x_st == 0 && p.y_st == 0 && p.KH == 3 && p.KW == 3 && p.stride == 1 && p.pad == 1 && p.out_mode == 0 &&
-           p.res_mode == 0 && p.splitk == 1 && p.Cout % WN == 0 && p.cin_log2 >= 3 && p.OH == p.H && p.OW == p.W &&
+           p.res_mode == 0 && p.Cout % WN == 0 && p.cin_log2 >= 3 && p.splitk >= 1 && p.splitk <= (1 << p.cin_log2) / KC &&
+           (p.wino_geom == 0 || p.wino_geom == 1) && p.OH == p.H && p.OW == p.W &&
            (p.y_ld & 3) == 0 && (p.y_coff & 3) == 0 && ((((size_t)max_items * p.H * p.W) << p.cin_log2) * 4 < 0x7fff0000ull);
 }
 
-// blocks of one image (64 Winograd tiles x 64 output channels each)
+// spatial blocks x N tiles of one image in geometry p.wino_geom (64 Winograd tiles x 64 output channels each); a split launch
+// runs p.splitk times as many
 int apse_conv_winograd_blocks(const ConvParams& p) {
-    return ((p.OH + 2 * WTR - 1) / (2 * WTR)) * ((p.OW + 2 * WTC - 1) / (2 * WTC)) * (p.Cout / WN);
+    const int wtr = p.wino_geom ? 8 : 16, wtc = p.wino_geom ? 8 : 4;
+    return ((p.OH + 2 * wtr - 1) / (2 * wtr)) * ((p.OW + 2 * wtc - 1) / (2 * wtc)) * (p.Cout / WN);
 }
 
-int apse_launch_conv_winograd(const ConvParams& p, hipStream_t s, hipEvent_t ev0, hipEvent_t ev1) {
-    if (!p.wu || !apse_conv_winograd_ok(p, p.B) || p.m_count) return APSE_E_INVALID;
+template <int WTR, int WTC, bool SPLIT>
+static void launch_wino(const ConvParams& p, int grid, hipStream_t s) {
     static bool attr_done = false;
     if (!attr_done) {
-        hipFuncSetAttribute(reinterpret_cast<const void*>(&conv_winograd_f32), hipFuncAttributeMaxDynamicSharedMemorySize, (int)WINO_LDS);
+        hipFuncSetAttribute(reinterpret_cast<const void*>(&conv_winograd_f32<WTR, WTC, SPLIT>), hipFuncAttributeMaxDynamicSharedMemorySize,
+                            (int)WINO_LDS);
         attr_done = true;
     }
-    const int tiles_y = (p.OH + 2 * WTR - 1) / (2 * WTR), tiles_x = (p.OW + 2 * WTC - 1) / (2 * WTC);
-    const int grid = p.B * tiles_y * tiles_x * (p.Cout / WN);
+    hipLaunchKernelGGL((conv_winograd_f32<WTR, WTC, SPLIT>), dim3(grid, SPLIT ? p.splitk : 1), dim3(NTHR), WINO_LDS, s, p);
+}
+
+// ev0 / ev1 bracket the Winograd kernel itself; the reduce pass of a split launch follows ev1 (as in apse_launch_conv)
+int apse_launch_conv_winograd(const ConvParams& p, hipStream_t s, hipEvent_t ev0, hipEvent_t ev1) {
+    if (!p.wu || !apse_conv_winograd_ok(p, p.B) || p.m_count) return APSE_E_INVALID;
+    const bool split = p.splitk > 1;
+    // the slabs are [splitk][M][Cout] with M = B OH OW, summed four columns at a time with 32-bit element indices
+    if (split && (!p.ws || p.tile_cnt || p.M != p.B * p.OH * p.OW || (size_t)p.M * p.Cout >= 0x7fffffffull)) return APSE_E_INVALID;
+    const int grid = p.B * apse_conv_winograd_blocks(p);
     if (ev0) hipEventRecord(ev0, s);
-    hipLaunchKernelGGL(conv_winograd_f32, dim3(grid), dim3(NTHR), WINO_LDS, s, p);
+    if (p.wino_geom == 0) { if (split) launch_wino<16, 4, true>(p, grid, s); else launch_wino<16, 4, false>(p, grid, s); }
+    else { if (split) launch_wino<8, 8, true>(p, grid, s); else launch_wino<8, 8, false>(p, grid, s); }
     if (ev1) hipEventRecord(ev1, s);
+    if (split) apse_launch_splitk_reduce4(p, s);
     return hipGetLastError() == hipSuccess ? APSE_OK : APSE_E_HIP;
 }

@@ -35,7 +35,7 @@ struct Step { StepKind kind; ConvStep c; const float* x; float* y; int H, W, C; 
 struct apse_ctx {
     apse_config cfg;
     std::string err;
-    bool f32_winograd = true;    // APSE_F32_WINOGRAD=0 (read once, at apse_create): the named f32 3x3 layers keep the direct kernel
+    bool f32_winograd = true;    // APSE_F32_WINOGRAD=0 (read once, at apse_create): the named f32 3x3 layers (plan.hip: winograd_layer, winograd_trunk_layer) keep the direct kernel
     std::map<std::string, HostW> hw;
     bool finalized = false;
     int PH = 0, PW = 0;

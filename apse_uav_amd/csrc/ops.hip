@@ -111,6 +111,23 @@ int apse_winograd_conv2d(const apse_conv_desc* d, const float* x, const float* w
     return apse_launch_conv_winograd(p, (hipStream_t)stream);
 }
 
+int apse_winograd_conv2d_split(const apse_conv_desc* d, const float* x, const float* wu, const float* bias, float* y, float* ws,
+                               size_t ws_bytes, int geometry, void* stream) {
+    if (!d || !x || !wu || !y || d->B < 1 || d->H < 1 || d->W < 1 || d->Cin < 8 || pow2_at_least(d->Cin) != d->Cin) return APSE_E_INVALID;
+    if (d->splitk < 1 || d->splitk > d->Cin / 8 || (geometry != 0 && geometry != 1)) return APSE_E_INVALID;
+    ConvParams p;
+    memset(&p, 0, sizeof p);
+    p.x = x; p.wu = wu; p.bias = bias; p.y = y; p.ws = ws;
+    p.B = d->B; p.H = d->H; p.W = d->W; p.cin_log2 = apse_ilog2(d->Cin);
+    p.KH = d->KH; p.KW = d->KW; p.stride = d->stride; p.pad = d->pad;
+    p.OH = d->H; p.OW = d->W; p.Cout = d->Cout; p.relu = d->relu;
+    p.M = p.B * p.OH * p.OW; p.m_per_item = p.OH * p.OW;
+    p.y_ld = d->Cout; p.splitk = d->splitk; p.wino_geom = geometry;
+    p.res_mode = d->res_mode; p.prec = d->prec; p.x_st = d->x_st; p.y_st = d->y_st;      // anything but 0 is refused by the launcher
+    if (p.splitk > 1 && (!ws || (size_t)p.splitk * p.M * p.Cout * sizeof(float) > ws_bytes)) return APSE_E_INVALID;
+    return apse_launch_conv_winograd(p, (hipStream_t)stream);
+}
+
 int apse_maxpool3x3s2(const float* x, float* y, int B, int H, int W, int C, void* stream) {
     return apse_k_maxpool3x3s2(x, y, B, H, W, C, 0, (hipStream_t)stream);
 }

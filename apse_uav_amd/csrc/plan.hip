@@ -7,6 +7,10 @@
 #include <string.h>
 
 #define APSE_WINO_MIN_BLOCKS 128  // f32 Winograd layers: fewest blocks per image (see add_conv)
+// the trunk's f32 Winograd layers (winograd_trunk_layer): fewest Winograd tiles per image of the plan's res4-stride map,
+// ceil(H / 2) ceil(W / 2).  A 16:9 frame at the 800 / 1333 resize has 24 x 42 = 1008; 600 / 1000 has 576, KITTI 546.
+#define APSE_WINO_TRUNK_MIN_TILES 1000
+#define APSE_WINO_GRID 256        // blocks a trunk Winograd launch may have per image: one per CU
 #define APSE_EXPECTED_DETS 8      // list length the packed-list GEMMs are shaped for (static: see add_conv)
 
 // ------------------------------------------------------------------------------------------------
@@ -74,6 +78,34 @@ static int storage_type(const apse_ctx* c) { return (c->cfg.compute_dtype >= 1 &
 // the RPN conv, whose results feed no further 3x3 chain (conv_winograd_f32)
 static bool winograd_layer(const std::string& n) {
     return n == "backbone.fpn_output2" || n == "backbone.fpn_output3" || n == "rpn_t2" || n == "rpn_t3";
+}
+// ... and, in plans of large frames only (APSE_WINO_TRUNK_MIN_TILES), 3x3 layers of the trunk and of the res4-stride level: the
+// bottlenecks' conv2 of res2, res3 and res5, the FPN output and the RPN conv at p4, with a Cin split and the block geometry that
+// fill the card.  res4's 23 conv2 layers stay on the direct kernel: with them the 64-frame given-boxes sequence at 4K missed its
+// exact CSV text in one centroid cell ("In the trunk")
+static bool winograd_trunk_layer(const std::string& n) {
+    static const std::string trunk = "backbone.bottom_up.res", c2 = ".conv2";
+    if (n == "backbone.fpn_output4" || n == "rpn_t4") return true;
+    return n.size() > trunk.size() + c2.size() && n.compare(0, trunk.size(), trunk) == 0 && n[trunk.size()] != '4' &&
+           n.compare(n.size() - c2.size(), c2.size(), c2) == 0;
+}
+// Geometry and Cin split of a trunk Winograd layer: the grid (blocks per image x split) nearest to APSE_WINO_GRID from below; a map
+// that has more blocks than that unsplit runs unsplit.  Equal grids: the unsplit launch keeps <16, 4>, a split one takes <8, 8>
+// (the squarer patch has the smaller halo).  A plan constant: shape only.
+static void winograd_trunk_shape(ConvParams& p) {
+    const int slices = (1 << p.cin_log2) / 8;
+    int best = -1;
+    for (int g = 0; g < 2; ++g) {
+        ConvParams q = p;
+        q.wino_geom = g;
+        const int nb = apse_conv_winograd_blocks(q);
+        int sk = nb >= APSE_WINO_GRID ? 1 : APSE_WINO_GRID / nb;
+        if (sk > slices) sk = slices;
+        const int grid = nb * sk, over = grid > APSE_WINO_GRID;
+        const int score = over ? -grid : grid;           // any grid within the bound beats one above it; above it, the smaller
+        const bool better = best == -1 || score > best || (score == best && sk > 1);
+        if (better) { best = score; p.wino_geom = g; p.splitk = sk; }
+    }
 }
 // U = G g G^T per (cout, cin) in float64, rounded to f32 once, stored [cin_p / 8][16][Cout][8] (xi = 4 i + j): the B-operand
 // staging of conv_winograd_f32 reads one contiguous 2 KiB run per xi and k-slice.  Channels past Cin are zero.
@@ -260,10 +292,29 @@ static int add_conv(apse_ctx* c, std::vector<Step>& plan, const ConvSpec& sp, co
     // the tiled config the layer would otherwise run and labels its profile slot.  Only maps of at least APSE_WINO_MIN_BLOCKS
     // blocks per image (p3 of a 4K frame: 252): the small-frame configurations keep the direct kernel and its exact results
     // (conv_winograd_f32)
-    if (c->f32_winograd && winograd_layer(sp.name) && sp.count_kind == 0 && apse_conv_winograd_ok(p, c->cfg.max_batch * sp.items) &&
-        apse_conv_winograd_blocks(p) >= APSE_WINO_MIN_BLOCKS) {
-        p.wu = dupload(c, winograd_filters(rows.data(), Cout, Cin, cin_p));
-        if (!p.wu) return fail(c, APSE_E_NOMEM, "weight upload failed at " + sp.name);
+    // The trunk set (winograd_trunk_layer; FPN plans only) is taken when the plan's res4-stride map has at least
+    // APSE_WINO_TRUNK_MIN_TILES tiles, with the geometry and the Cin split of winograd_trunk_shape; its slabs share the split-K
+    // workspace (these layers run on the caller's stream)
+    if (c->f32_winograd && sp.count_kind == 0) {
+        ConvParams q = p;
+        bool take = false;
+        if (winograd_layer(sp.name)) {
+            take = sk == 1 && apse_conv_winograd_ok(q, c->cfg.max_batch * sp.items) && apse_conv_winograd_blocks(q) >= APSE_WINO_MIN_BLOCKS;
+        } else if (!c->c4 && winograd_trunk_layer(sp.name) &&
+                   ((c->PH / 16 + 1) / 2) * ((c->PW / 16 + 1) / 2) >= APSE_WINO_TRUNK_MIN_TILES) {
+            q.splitk = 1;
+            if (apse_conv_winograd_ok(q, c->cfg.max_batch * sp.items)) {
+                winograd_trunk_shape(q);
+                take = apse_conv_winograd_ok(q, c->cfg.max_batch * sp.items);
+            }
+        }
+        if (take) {
+            p = q;
+            p.wu = dupload(c, winograd_filters(rows.data(), Cout, Cin, cin_p));
+            if (!p.wu) return fail(c, APSE_E_NOMEM, "weight upload failed at " + sp.name);
+            const size_t need = (size_t)p.splitk * Mfull * Cout;
+            if (p.splitk > 1 && need > c->ws_floats) c->ws_floats = need;
+        }
     }
     if (out) *out = o;
     plan.push_back(st);

@@ -45,8 +45,25 @@ def _output_transform(m):
     return np.stack([np.stack([y00, y01], -2), np.stack([y10, y11], -2)], -3)
 
 
-def emulate(x_hwc, w_oihw, bias, relu):
-    """3x3 / stride 1 / pad 1 convolution of one HWC f32 image by F(2x2, 3x3), every step in f32 -> HWC f32."""
+def split_ranges(cin, split):
+    """The channel ranges [c0, c1) of a Cin split: whole 8-channel slices divided as evenly as possible, larger shares first."""
+    slices = cin // 8
+    assert cin % 8 == 0 and 1 <= split <= slices
+    share, extra = divmod(slices, split)
+    out, s = [], 0
+    for z in range(split):
+        n = share + (1 if z < extra else 0)
+        out.append((8 * s, 8 * (s + n)))
+        s += n
+    return out
+
+
+def emulate(x_hwc, w_oihw, bias, relu, split=1):
+    """3x3 / stride 1 / pad 1 convolution of one HWC f32 image by F(2x2, 3x3), every step in f32 -> HWC f32.
+
+    split > 1: the Cin split of the kernel.  Every share of the channels (split_ranges) goes through its own accumulators and its
+    own output transform; the partial Y are then summed from zero in split order, and bias and ReLU follow, as the split-K reduce
+    kernel does."""
     x = np.asarray(x_hwc, dtype=np.float32)
     H, W, C = x.shape
     th, tw = (H + 1) // 2, (W + 1) // 2
@@ -60,11 +77,22 @@ def emulate(x_hwc, w_oihw, bias, relu):
     m = np.zeros((th, tw, 16, u.shape[1]), np.float32)
     uc = np.ascontiguousarray(u.transpose(2, 0, 1))               # [C][16][Cout]
     rows = max(1, (1 << 18) // (tw * 16 * u.shape[1]))            # tile rows per pass: about 1 MiB of m, so the channel loop stays in cache
-    for r0 in range(0, th, rows):                                 # (tiles are independent: the same arithmetic as one pass over the image)
-        vr, mr = v[r0:r0 + rows], m[r0:r0 + rows]
-        for c in range(C):                                        # channels ascending, one f32 rounding per product and per add
-            mr += vr[..., c:c + 1] * uc[c]
-    y = _output_transform(m) + np.asarray(bias, np.float32)      # [th][tw][2][2][Cout]
+    if split == 1:
+        for r0 in range(0, th, rows):                             # (tiles are independent: the same arithmetic as one pass over the image)
+            vr, mr = v[r0:r0 + rows], m[r0:r0 + rows]
+            for c in range(C):                                    # channels ascending, one f32 rounding per product and per add
+                mr += vr[..., c:c + 1] * uc[c]
+        y = _output_transform(m) + np.asarray(bias, np.float32)  # [th][tw][2][2][Cout]
+    else:
+        y = np.zeros((th, tw, 2, 2, u.shape[1]), np.float32)
+        for c0, c1 in split_ranges(C, split):
+            m[...] = 0
+            for r0 in range(0, th, rows):
+                vr, mr = v[r0:r0 + rows], m[r0:r0 + rows]
+                for c in range(c0, c1):
+                    mr += vr[..., c:c + 1] * uc[c]
+            y += _output_transform(m)                             # the reduce: partial Y summed from zero, z ascending
+        y = y + np.asarray(bias, np.float32)
     if relu:
         y = np.maximum(y, 0)
     y = y.transpose(0, 2, 1, 3, 4).reshape(2 * th, 2 * tw, -1)

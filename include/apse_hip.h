@@ -277,6 +277,13 @@ int apse_conv2d(const apse_conv_desc* d, const float* x_dev, const float* w_pack
 int apse_winograd_pack_filter(const float* w_oihw, int Cout, int Cin, float* packed);
 int apse_winograd_conv2d(const apse_conv_desc* d, const float* x_dev, const float* wu_dev, const float* bias_dev, float* y_dev,
                          void* stream);
+/* The same kernel with the Cin split and the block geometry the f32 plan of a large frame gives its trunk 3x3 layers.  d->splitk
+ * (>= 1, at most Cin / 8) shares of whole 8-channel slices go to slabs ws_dev[splitk][B H W][Cout] (needed for splitk > 1 only) and
+ * are summed in split order, then bias, then ReLU, by the split-K reduce kernel.  geometry: 0 = blocks of 16 x 4 Winograd tiles
+ * (apse_winograd_conv2d's), 1 = 8 x 8.  A workspace too small, a split above Cin / 8, an unknown geometry and whatever
+ * apse_winograd_conv2d refuses are APSE_E_INVALID, with y and ws untouched. */
+int apse_winograd_conv2d_split(const apse_conv_desc* d, const float* x_dev, const float* wu_dev, const float* bias_dev, float* y_dev,
+                               float* ws_dev, size_t ws_bytes, int geometry, void* stream);
 int apse_maxpool3x3s2(const float* x_dev, float* y_dev, int B, int H, int W, int C, void* stream);
 /* Same on a storage type (0 f32, 1 bf16, 2 f16): the form the 16-bit modes run after the stem. */
 int apse_maxpool3x3s2_typed(const void* x_dev, void* y_dev, int B, int H, int W, int C, int storage, void* stream);
