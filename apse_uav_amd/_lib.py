@@ -18,7 +18,7 @@ _TREE_LIB = os.path.join(_HERE, "libapse_hip.so")
 LIB_PATH = os.environ.get("APSE_HIP_LIB") or _TREE_LIB
 # entries that only tools/ and the operator tests use: a build from before they existed may still be loaded through
 # APSE_HIP_LIB (load())
-TOOL_ENTRIES = ("apse_winograd_pack_filter", "apse_winograd_conv2d", "apse_winograd_conv2d_split", "apse_lane_stats", "apse_rpn_select", "apse_box_inference",
+TOOL_ENTRIES = ("apse_conv2d_ex", "apse_winograd_pack_filter", "apse_winograd_conv2d", "apse_winograd_conv2d_split", "apse_lane_stats", "apse_rpn_select", "apse_box_inference",
                 "apse_c4_rpn_select", "apse_rpn_select_train", "apse_rpn_train_proposals_workspace_bytes", "apse_rpn_train_proposals",
                 "apse_set_rpn_head", "apse_preprocess_frames_yuv", "apse_yuv_to_bgr", "apse_yuv_matrix_host", "apse_resize_normalize_yuv")
 
@@ -118,6 +118,7 @@ SIGNATURES = {
     "apse_conv_packed_elems": ([C.POINTER(ConvDesc)], sz),
     "apse_conv_pack_weight": ([C.POINTER(ConvDesc), vp, i, vp, vp], i),
     "apse_conv2d": ([C.POINTER(ConvDesc), vp, vp, vp, vp, vp, vp, sz, vp], i),
+    "apse_conv2d_ex": ([C.POINTER(ConvDesc), vp, vp, vp, vp, vp, vp, sz, vp, i, i, i, vp], i),
     "apse_winograd_pack_filter": ([vp, i, i, vp], i),
     "apse_winograd_conv2d": ([C.POINTER(ConvDesc), vp, vp, vp, vp, vp], i),
     "apse_winograd_conv2d_split": ([C.POINTER(ConvDesc), vp, vp, vp, vp, vp, C.c_size_t, i, vp], i),

@@ -38,14 +38,21 @@ int apse_conv_pack_weight(const apse_conv_desc* d, const float* w, int cin_real,
     return APSE_OK;
 }
 
-int apse_conv2d(const apse_conv_desc* d, const float* x, const float* w, const float* bias, const float* res, float* y, float* ws,
-                size_t ws_bytes, void* stream) {
+// apse_conv2d and apse_conv2d_ex: one layer on the direct kernels.  The arguments behind ws_bytes are apse_conv2d_ex's (the forms
+// run_plan gives the ROI heads); apse_conv2d passes none of them and launches what it always did.
+static int conv2d_stateless(const apse_conv_desc* d, const void* x, const float* w, const float* bias, const void* res, void* y,
+                            float* ws, size_t ws_bytes, const int* count_dev, int hint_items, int y_ld, int deconv, void* stream) {
     if (!d || !x || !w || !y) return APSE_E_INVALID;
     const int cin_p = pow2_at_least(d->Cin);
     if (cin_p != d->Cin) return APSE_E_INVALID;
+    if (hint_items < 0 || y_ld < 0 || (y_ld > 0 && (y_ld < d->Cout || deconv))) return APSE_E_INVALID;
+    if (deconv && (d->KH != 1 || d->KW != 1 || d->stride != 1 || d->pad != 0 || (d->Cout & 15) || d->res_mode != 0)) return APSE_E_INVALID;
+    if (count_dev && (d->fuse_reduce || d->cfg == APSE_CFG_STREAM || d->cfg == APSE_CFG_GLDS)) return APSE_E_INVALID;
+    if (d->res_mode != 0 && (d->Cout & 3) != 0) return APSE_E_INVALID;      // residual rows are read as float4
     ConvParams p;
     memset(&p, 0, sizeof p);
-    p.x = x; p.w = w; p.bias = bias; p.res = res; p.y = y; p.ws = ws;
+    p.x = reinterpret_cast<const float*>(x); p.w = w; p.bias = bias; p.res = reinterpret_cast<const float*>(res);
+    p.y = reinterpret_cast<float*>(y); p.ws = ws;
     p.B = d->B; p.H = d->H; p.W = d->W; p.cin_log2 = apse_ilog2(cin_p);
     p.KH = d->KH; p.KW = d->KW; p.stride = d->stride; p.pad = d->pad;
     p.KWCp = apse_roundup(d->KW * cin_p, 32);
@@ -54,9 +61,14 @@ int apse_conv2d(const apse_conv_desc* d, const float* x, const float* w, const f
     p.Cout = d->Cout; p.relu = d->relu; p.res_mode = d->res_mode;
     p.M = p.B * p.OH * p.OW; p.m_per_item = p.OH * p.OW;
     p.y_ld = d->Cout; p.steps_total = p.KH * (p.KWCp / 32);
+    if (y_ld > 0) p.y_ld = y_ld;
+    if (deconv) { p.out_mode = 1; p.cdec = d->Cout / 4; p.y_ld = d->Cout / 4; }
+    if (count_dev) p.m_count = count_dev;
+    if (hint_items > 0) p.m_hint = (long long)hint_items * p.m_per_item < p.M ? hint_items * p.m_per_item : p.M;
     p.prec = (d->prec == 1 || d->prec == 2) ? d->prec : 0;
     p.x_st = d->x_st; p.res_st = d->res_st; p.y_st = d->y_st;
     if (p.x_st < 0 || p.x_st > 2 || p.res_st < 0 || p.res_st > 2 || p.y_st < 0 || p.y_st > 2) return APSE_E_INVALID;
+    if ((y_ld > 0 || deconv) && p.y_st && (p.y_ld & 7)) return APSE_E_INVALID;      // 16-bit rows are whole 16-byte groups
     if (p.prec && p.x_st && p.x_st != p.prec) return APSE_E_INVALID;       // 16-bit x must already be the operand type
     if (p.x_st && cin_p < 8) return APSE_E_INVALID;
     int sk = 1;
@@ -88,6 +100,16 @@ int apse_conv2d(const apse_conv_desc* d, const float* x, const float* w, const f
     if (rc) return rc;
     p.w16 = d16;
     return apse_launch_conv(p, cfg, (hipStream_t)stream);
+}
+
+int apse_conv2d(const apse_conv_desc* d, const float* x, const float* w, const float* bias, const float* res, float* y, float* ws,
+                size_t ws_bytes, void* stream) {
+    return conv2d_stateless(d, x, w, bias, res, y, ws, ws_bytes, nullptr, 0, 0, 0, stream);
+}
+
+int apse_conv2d_ex(const apse_conv_desc* d, const void* x, const float* w, const float* bias, const void* res, void* y, float* ws,
+                   size_t ws_bytes, const int* count_dev, int hint_items, int y_ld, int deconv, void* stream) {
+    return conv2d_stateless(d, x, w, bias, res, y, ws, ws_bytes, count_dev, hint_items, y_ld, deconv, stream);
 }
 
 int apse_winograd_pack_filter(const float* w, int Cout, int Cin, float* packed) {

@@ -270,6 +270,21 @@ size_t apse_conv_packed_elems(const apse_conv_desc* d);
 int apse_conv_pack_weight(const apse_conv_desc* d, const float* w_oihw, int cin_real, const float* scale, float* packed);
 int apse_conv2d(const apse_conv_desc* d, const float* x_dev, const float* w_packed_dev, const float* bias_dev,
                 const float* res_dev, float* y_dev, float* ws_dev, size_t ws_bytes, void* stream);
+/* apse_conv2d in the forms the plan gives the ROI heads (a test / tool helper; the descriptor is apse_conv2d's, and with
+ * count_dev = NULL, hint_items = y_ld = deconv = 0 so is the launch).  x / res / y are read in the descriptor's storage types.
+ * count_dev: device int, the number of live items; rows from min(*count_dev, d->B) * OH * OW on are neither computed nor written
+ * (d->B is the capacity in items; the split-K slabs are sized for it).  hint_items > 0: the expected count, which sizes the grid
+ * of a counted launch only (rows min(hint_items * OH * OW, M)); no result depends on it.  y_ld > 0: the stride of an output row
+ * in elements, >= Cout; columns from roundup(Cout, 4) on are never written, columns Cout .. roundup(Cout, 4) - 1 of a live row
+ * are either left alone or written with the epilogue of an all-zero filter row (the padded bias, ReLU applied).  deconv != 0: a
+ * 1x1 / stride 1 / pad 0 layer without residual and with Cout a multiple of 16 whose output is scattered as the 2x2 stride-2
+ * transposed convolution to [B][2H][2W][Cout / 4] (filter rows (dy * 2 + dx) * Cout / 4 + co, bias of Cout / 4 entries padded
+ * like any other).  APSE_E_INVALID, with nothing launched: y_ld < Cout, y_ld with deconv, a 16-bit y with y_ld (or Cout / 4 of a
+ * deconvolution) not a multiple of 8, fuse_reduce or an explicit cfg 9 / 11 with a count, a residual with Cout % 4 != 0, and
+ * whatever apse_conv2d refuses.  cfg = -1 with a count never takes the stream or LDS-DMA kernels (they are not count-limited). */
+int apse_conv2d_ex(const apse_conv_desc* d, const void* x_dev, const float* w_packed_dev, const float* bias_dev, const void* res_dev,
+                   void* y_dev, float* ws_dev, size_t ws_bytes, const int* count_dev, int hint_items, int y_ld, int deconv,
+                   void* stream);
 /* One layer through the fused f32 Winograd F(2x2,3x3) kernel the f32 plan uses for its p2 / p3 3x3 layers (a test / tool helper,
  * like apse_conv2d, which keeps the direct kernels).  apse_winograd_pack_filter: OIHW host filter [Cout][Cin][3][3], Cin a power of
  * two >= 8 -> U = G g G^T, 16 * Cout * Cin floats on the host, the bytes a context uploads.  apse_winograd_conv2d: f32 NHWC in /

@@ -137,6 +137,80 @@ def hip_conv2d(x_nchw, w_oihw, bias=None, stride=1, pad=0, relu=False, residual=
     return y.float().cpu().permute(0, 3, 1, 2).contiguous()
 
 
+def storage16_tolerance(ref, prec):
+    """Per-element bound on |kernel - reference rounded to the 16-bit type| for a 16-bit STORED output (test_conv2d_16bit_storage):
+    the kernel's f32 result differs from the reference's by summation order only; after the 16-bit store the two agree except
+    where that tiny difference straddles a rounding boundary (then by one 16-bit ulp).
+    + 4e-6: f32 summation-order noise of a unit-variance sum that cancels to |ref| < 1e-3 [round 4: 7 of 7.1 M outputs of the
+    K = 512 case sit at 2.3e-6 from the reference with |ref| = 6e-4; the LDS-DMA kernel and the tiled kernel agree on them bit
+    for bit]"""
+    ulp = 2.0 ** (-7 if prec == 1 else -10)        # one unit in the last place, relative to the binade's lower edge
+    return ulp * ref.abs().clamp_min(1e-3) * 1.01 + 4e-6
+
+
+# ---------------------------------------------------------------------------------------------- apse_conv2d_ex
+# fill of y (in its storage type) and of the workspace in front of a launch: NaNs no kernel produces, compared as integers
+CONV_FILL = {0: (torch.int32, 0x7fc5a5a5), 1: (torch.int16, 0x7fc5), 2: (torch.int16, 0x7e5a)}
+_TDT = {0: torch.float32, 1: torch.bfloat16, 2: torch.float16}
+
+
+class ConvExLayer:
+    """The device operands of one layer for apse_conv2d_ex, uploaded once: x (CPU NCHW f32, the capacity in items), the packed
+    filter, the bias padded to a multiple of 128 entries (entries from Cout on = ``bias_pad``) and the residual.  ``packed`` /
+    ``bias_p`` (device tensors) with ``geom`` = (Cout, KH, KW) replace ``w_oihw`` / ``bias`` for a filter packed elsewhere."""
+
+    def __init__(self, x_nchw, w_oihw=None, bias=None, stride=1, pad=0, relu=False, residual=None, res_mode=0, prec=0, x_st=0,
+                 res_st=0, y_st=0, packed=None, bias_p=None, geom=None, bias_pad=0.0):
+        dev = torch.device("cuda:0")
+        self.Bcap, Cin, self.H, self.W = x_nchw.shape
+        if packed is None:
+            self.Cout, _, self.KH, self.KW = w_oihw.shape
+            pk, self.cin_p = pack_filter(w_oihw)
+            self.wd = torch.from_numpy(pk).to(dev)
+            bp = torch.full((((self.Cout + 127) // 128) * 128,), float(bias_pad))
+            bp[:self.Cout] = 0.0 if bias is None else bias
+            self.bd = bp.to(dev)
+        else:
+            (self.Cout, self.KH, self.KW), self.cin_p, self.wd, self.bd = geom, Cin, packed, bias_p
+        self.stride, self.pad, self.relu, self.res_mode = stride, pad, relu, res_mode
+        self.prec, self.x_st, self.res_st, self.y_st = prec, x_st, res_st, y_st
+        self.OH = (self.H + 2 * pad - self.KH) // stride + 1
+        self.OW = (self.W + 2 * pad - self.KW) // stride + 1
+        self.xd = to_nhwc(x_nchw, self.cin_p).to(dev).to(_TDT[x_st]).contiguous()
+        self.rd = None if residual is None else to_nhwc(residual).to(dev).to(_TDT[res_st]).contiguous()
+
+    def run(self, B, cfg=-1, splitk=0, count=None, hint=0, y_ld=0, deconv=0, fuse=0, extra_rows=256, ws_slabs=None):
+        """One launch over the first ``B`` items (the capacity of a counted launch).  Returns (rc, y, ws): y as integers of its
+        storage type, [output rows + extra_rows][row stride], ws as int32 -- both filled with CONV_FILL in front of the launch."""
+        lib = _lib.load()
+        dev = self.xd.device
+        d = _lib.ConvDesc()
+        d.B, d.H, d.W, d.Cin = B, self.H, self.W, self.cin_p
+        d.Cout, d.KH, d.KW, d.stride, d.pad = self.Cout, self.KH, self.KW, self.stride, self.pad
+        d.relu, d.res_mode, d.cfg, d.splitk, d.prec, d.fuse_reduce = int(self.relu), self.res_mode, cfg, splitk, self.prec, fuse
+        d.x_st, d.res_st, d.y_st = self.x_st, self.res_st, self.y_st
+        M = B * self.OH * self.OW
+        ld = max(self.Cout // 4, 1) if deconv else max(y_ld, self.Cout)
+        ydt, ypat = CONV_FILL[self.y_st]
+        y = torch.full(((4 * M if deconv else M) + extra_rows, ld), ypat, dtype=ydt, device=dev)
+        slabs = ws_slabs if ws_slabs is not None else max(splitk, 1)
+        ws = torch.full((slabs * M * self.Cout + 16,), CONV_FILL[0][1], dtype=torch.int32, device=dev)
+        cnt = None if count is None else torch.tensor([count], dtype=torch.int32).to(dev)
+        rc = lib.apse_conv2d_ex(C.byref(d), _lib.ptr(self.xd), _lib.ptr(self.wd), _lib.ptr(self.bd), _lib.ptr(self.rd), _lib.ptr(y),
+                                _lib.ptr(ws), ws.numel() * 4, _lib.ptr(cnt), hint, y_ld, deconv, _lib.stream_ptr())
+        torch.cuda.synchronize()
+        return rc, y, ws
+
+    def values(self, y):
+        """y of ``run`` as float64 on the CPU (same shape)."""
+        return y.view(_TDT[self.y_st]).double().cpu()
+
+
+def conv_untouched(t, st=0):
+    """True when every element of ``t`` (y or ws of ConvExLayer.run) still holds the fill pattern."""
+    return bool((t == CONV_FILL[st][1]).all())
+
+
 def err_stats(a, b):
     a = a.double()
     b = b.double()
