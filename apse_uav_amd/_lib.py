@@ -18,7 +18,7 @@ _TREE_LIB = os.path.join(_HERE, "libapse_hip.so")
 LIB_PATH = os.environ.get("APSE_HIP_LIB") or _TREE_LIB
 # entries that only tools/ and the operator tests use: a build from before they existed may still be loaded through
 # APSE_HIP_LIB (load())
-TOOL_ENTRIES = ("apse_conv2d_ex", "apse_winograd_pack_filter", "apse_winograd_conv2d", "apse_winograd_conv2d_split", "apse_lane_stats", "apse_rpn_select", "apse_box_inference",
+TOOL_ENTRIES = ("apse_conv2d_ex", "apse_winograd_pack_filter", "apse_winograd_conv2d", "apse_winograd_conv2d_split", "apse_conv_pointwise_launches", "apse_lane_stats", "apse_rpn_select", "apse_box_inference",
                 "apse_c4_rpn_select", "apse_rpn_select_train", "apse_rpn_train_proposals_workspace_bytes", "apse_rpn_train_proposals",
                 "apse_set_rpn_head", "apse_preprocess_frames_yuv", "apse_yuv_to_bgr", "apse_yuv_matrix_host", "apse_resize_normalize_yuv")
 
@@ -122,6 +122,7 @@ SIGNATURES = {
     "apse_winograd_pack_filter": ([vp, i, i, vp], i),
     "apse_winograd_conv2d": ([C.POINTER(ConvDesc), vp, vp, vp, vp, vp], i),
     "apse_winograd_conv2d_split": ([C.POINTER(ConvDesc), vp, vp, vp, vp, vp, C.c_size_t, i, vp], i),
+    "apse_conv_pointwise_launches": ([], C.c_uint),
     "apse_maxpool3x3s2": ([vp, vp, i, i, i, i, vp], i),
     "apse_maxpool3x3s2_typed": ([vp, vp, i, i, i, i, i, vp], i),
     "apse_roi_align": ([C.POINTER(vp), C.POINTER(i), C.POINTER(i), vp, i, i, i, vp, vp], i),

@@ -21,6 +21,7 @@
 // 128x128); one barrier per k-step -- for every f32 tile but 128x128 in front of the step's LAST MFMA group, which then runs
 // over the next step's first fragment reads.  See DESIGN.md section 3 for the measured effect of each choice.
 #include "apse_common.h"
+#include <atomic>
 #include <type_traits>
 
 // XT = 0: x is f32 and is read through a buffer descriptor: a tap outside the image (or a k sub-step past the end)
@@ -41,9 +42,25 @@ typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
 __device__ __forceinline__ f32x16 apse_mfma16(bf16x8 a, bf16x8 b, f32x16 c) { return __builtin_amdgcn_mfma_f32_32x32x16_bf16(a, b, c, 0, 0, 0); }
 __device__ __forceinline__ f32x16 apse_mfma16(f16x8 a, f16x8 b, f32x16 c) { return __builtin_amdgcn_mfma_f32_32x32x16_f16(a, b, c, 0, 0, 0); }
 
-template <int WM, int WN, int TM, int TN, int KS, int XT, int WK, int PR = 0>
+// FORM: the address code of the descriptor path's k loop (apse_launch_conv picks it; APSE_IGEMM_ADDR=0 keeps the general one).
+// General (no FORM argument): per piece and sub-step the tap's coordinates, two range tests, the masked offset and a 64-bit
+// filter address.
+// POINTWISE (FORM = apse_pointwise): for 1x1 / pad 0 layers, at any stride, whose filter row is exactly the pixel's Cin run.
+// Every tap is the output pixel's own input pixel.  From sub-step to sub-step only the k displacement of 128 bytes changes.
+// - Each A piece keeps ONE loop-invariant per-lane byte offset.  A row past M gets the out-of-range offset, once per tile.
+// - Each B piece keeps one per-lane offset into a buffer descriptor of the packed filter.
+// - The displacement rides in the buffer instructions' scalar offset; the walk is one scalar counter.
+// - A dead sub-step (odd steps_total at KS = 2, or a fetch past the last step) reads A through an empty range: zeros, no branch.
+// The loads are the same, of the same bytes, at the same places of the schedule: the bits are those of the general code.
+// FORM is a trailing pack, not a ninth value: an empty pack prints nothing, so the general kernels keep their names
+// conv_igemm_f32<WM, .., PR>.  Traces and the committed counter files look them up by those names.
+struct apse_pointwise {};
+template <int WM, int WN, int TM, int TN, int KS, int XT, int WK, int PR = 0, typename... FORM>
 __global__ __launch_bounds__(64 * WM * WN * WK) void conv_igemm_f32(const ConvParams p) {
+    static_assert(sizeof...(FORM) == 0 || (sizeof...(FORM) == 1 && (std::is_same<FORM, apse_pointwise>::value && ...)), "FORM is nothing or apse_pointwise");
+    constexpr bool PW = sizeof...(FORM) != 0;
     static_assert(PR == 0 || XT == 0, "16-bit operands use the descriptor path only");
+    static_assert(!PW || XT == 0, "the pointwise address form exists for the plain descriptor path only");
     // XT = 2 / 3: descriptor path with bf16 / f16 activations WIDENED to f32 operands (the exact-f32 decision heads of the
     // 16-bit modes: RPN logits / deltas, box predictor, mask logits): 8-byte fetches of 4 elements, widened on the way to LDS
     constexpr bool DESC = XT != 1;
@@ -95,8 +112,14 @@ __global__ __launch_bounds__(64 * WM * WN * WK) void conv_igemm_f32(const ConvPa
     const size_t w_row = (size_t)p.KH * p.KWCp;
     const bool direct = (p.splitk == 1);
     __amdgpu_buffer_rsrc_t xrsrc;
+    const unsigned xbytes = (((unsigned)(p.B * p.H * p.W) << p.cin_log2)) << (XT >= 2 ? 1 : ESH);
     if constexpr (DESC)
-        xrsrc = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(p.x), 0, (int)((((unsigned)(p.B * p.H * p.W) << p.cin_log2)) << (XT >= 2 ? 1 : ESH)), 0x00020000);
+        xrsrc = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(p.x), 0, (int)xbytes, 0x00020000);
+    // PW: the packed filter [Cout_p = Cout rounded up to 128][w_row] (the launcher keeps it below 4 GiB)
+    __amdgpu_buffer_rsrc_t wrsrc;
+    if constexpr (PW)
+        wrsrc = __builtin_amdgcn_make_buffer_rsrc(PR ? const_cast<void*>(reinterpret_cast<const void*>(p.w16)) : const_cast<void*>(reinterpret_cast<const void*>(p.w)), 0,
+                                                  (int)(((unsigned)((p.Cout + 127) & ~127) * (unsigned)w_row) << ESH), 0x00020000);
 
     bool warm_pending = p.next_w && z == 0;     // the block's first tile also warms a slice of the next layer's filters
     // Persistent over tiles: the grid is min(tiles, cap); count-limited launches (packed detection
@@ -147,7 +170,35 @@ __global__ __launch_bounds__(64 * WM * WN * WK) void conv_igemm_f32(const ConvPa
         // The k-step issues its pieces one per MFMA group, pinned there with sched_barriers, so the address
         // arithmetic and the fetches ride in the gaps of the matrix pipe instead of in front of it.
         int cur_r = 0, cur_ry = 0, cur_q = 0, cur_rowoff = 0, cur_woff = 0, cur_dpx = 0;
+        // PW: per-piece byte offsets, fixed for the tile; the scalars of the sub-step being fetched
+        unsigned pw_a[AP], pw_w[BP];
+        int pw_s = s_begin * KS, pw_soff = 0;
+        unsigned pw_xbytes = 0;
+        if constexpr (PW) {
+#pragma unroll
+            for (int i = 0; i < AP; ++i) {
+                const bool in = ((unsigned)a_iy0[i] < (unsigned)p.H) & ((unsigned)a_ix0[i] < (unsigned)p.W);      // the one tap of the row
+                pw_a[i] = in ? ((unsigned)(a_base[i] + slot * EPSLOT) << ESH) : 0xfffffff0u;
+            }
+#pragma unroll
+            for (int i = 0; i < BP; ++i) pw_w[i] = ((unsigned)(n0 + srow + SR * i) * (unsigned)w_row + (unsigned)(slot * EPSLOT)) << ESH;
+        }
         auto fetch_piece = [&](int set, int u, int j) {
+            if constexpr (PW) {
+                if (j == 0) {                  // scalars of sub-step u: its k displacement, and an empty activation range when it is dead
+                    const bool live = pw_s < steps_total;
+                    pw_soff = live ? pw_s * 128 : 0;
+                    pw_xbytes = live ? xbytes : 0u;
+                    ++pw_s;
+                }
+                if (j < AP) {
+                    const __amdgpu_buffer_rsrc_t xs = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(p.x), 0, (int)pw_xbytes, 0x00020000);
+                    ra[set][u][j] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(xs, (int)pw_a[j], pw_soff, 0));
+                } else {
+                    rb[set][u][j - AP] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(wrsrc, (int)pw_w[j - AP], pw_soff, 0));
+                }
+                return;
+            }
             if (j == 0) {                      // scalars of sub-step u
                 const bool live = ld_r < p.KH;
                 cur_r = live ? ld_r : p.KH - 1;
@@ -732,7 +783,11 @@ void apse_launch_splitk_reduce4(const ConvParams& p, hipStream_t s) {
     hipLaunchKernelGGL(conv_splitk_reduce4, dim3(blocks), dim3(256), 0, s, p);
 }
 
-template <int WM, int WN, int TM, int TN, int KS, int XT, int WK = 1, int PR = 0>
+// launches of the pointwise kernel by this process (apse_conv_pointwise_launches: lets a test see which address form ran)
+static std::atomic<unsigned> g_pointwise_launches{0};
+extern "C" unsigned apse_conv_pointwise_launches(void) { return g_pointwise_launches.load(std::memory_order_relaxed); }
+
+template <int WM, int WN, int TM, int TN, int KS, int XT, int WK = 1, int PR = 0, bool PW = false>
 static int launch_cfg_x(const ConvParams& p, hipStream_t s, hipEvent_t ev0, hipEvent_t ev1) {
     constexpr int BM = WM * TM * 32, BN = WN * TN * 32;
     const int tiles = ((p.M + BM - 1) / BM) * ((p.Cout + BN - 1) / BN);
@@ -740,8 +795,12 @@ static int launch_cfg_x(const ConvParams& p, hipStream_t s, hipEvent_t ev0, hipE
     const size_t lds = lds_stage > lds_c ? lds_stage : lds_c;
     static bool attr_done = false;
     if (!attr_done) {
-        hipFuncSetAttribute(reinterpret_cast<const void*>(&conv_igemm_f32<WM, WN, TM, TN, KS, XT, WK, PR>),
-                            hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+        if constexpr (PW)
+            hipFuncSetAttribute(reinterpret_cast<const void*>(&conv_igemm_f32<WM, WN, TM, TN, KS, XT, WK, PR, apse_pointwise>),
+                                hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+        else
+            hipFuncSetAttribute(reinterpret_cast<const void*>(&conv_igemm_f32<WM, WN, TM, TN, KS, XT, WK, PR>),
+                                hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
         attr_done = true;
     }
     // count-limited launches are persistent over the live tiles: size the grid for about twice the expected
@@ -757,7 +816,12 @@ static int launch_cfg_x(const ConvParams& p, hipStream_t s, hipEvent_t ev0, hipE
         if (grid_x > want) grid_x = want;
     }
     if (ev0) hipEventRecord(ev0, s);
-    hipLaunchKernelGGL((conv_igemm_f32<WM, WN, TM, TN, KS, XT, WK, PR>), dim3(grid_x, p.splitk), dim3(64 * WM * WN * WK), lds, s, p);
+    if constexpr (PW) {
+        hipLaunchKernelGGL((conv_igemm_f32<WM, WN, TM, TN, KS, XT, WK, PR, apse_pointwise>), dim3(grid_x, p.splitk), dim3(64 * WM * WN * WK), lds, s, p);
+        g_pointwise_launches.fetch_add(1, std::memory_order_relaxed);
+    } else {
+        hipLaunchKernelGGL((conv_igemm_f32<WM, WN, TM, TN, KS, XT, WK, PR>), dim3(grid_x, p.splitk), dim3(64 * WM * WN * WK), lds, s, p);
+    }
     if (ev1) hipEventRecord(ev1, s);
     if (p.splitk > 1 && !p.tile_cnt) {
         const size_t total = (size_t)p.M * p.Cout;
@@ -773,14 +837,40 @@ static int launch_cfg_x(const ConvParams& p, hipStream_t s, hipEvent_t ev0, hipE
 // the descriptor path needs f32 activations of < 4 GiB (byte offsets are 32-bit)
 static bool descriptor_ok(const ConvParams& p) { return p.x_st == 0 && (((size_t)p.B * p.H * p.W) << p.cin_log2) * 4 < 0xfffffff0ull; }
 
-template <int WM, int WN, int TM, int TN, int KS>
+// APSE_IGEMM_ADDR=0 (read once, at the first launch): every layer keeps the general per-step address code (A/B runs and the
+// byte-identity tests of the pointwise form with one build)
+static bool igemm_addr_on() {
+    static const bool on = [] { const char* e = getenv("APSE_IGEMM_ADDR"); return !(e && e[0] == '0'); }();
+    return on;
+}
+// the pointwise address form (conv_igemm_f32<.., apse_pointwise>): 1x1 / pad 0 at any stride, the filter row exactly one pixel's Cin run
+// (so no k sub-step reaches into a neighbouring pixel), the packed filter within 32-bit byte offsets
+static bool pointwise_ok(const ConvParams& p) {
+    return igemm_addr_on() && p.KH == 1 && p.KW == 1 && p.pad == 0 && p.KWCp == (1 << p.cin_log2) &&
+           (size_t)((p.Cout + 127) & ~127) * (size_t)p.KWCp * 4 < 0xfffffff0ull;
+}
+
+// PWF: the shape has a pointwise instantiation (the tile configs the plans use: 0, 1, 3 and 6)
+template <int WM, int WN, int TM, int TN, int KS, bool PWF = false>
 static int launch_cfg(const ConvParams& p, hipStream_t s, hipEvent_t ev0, hipEvent_t ev1) {
-    return descriptor_ok(p) ? launch_cfg_x<WM, WN, TM, TN, KS, 0>(p, s, ev0, ev1) : launch_cfg_x<WM, WN, TM, TN, KS, 1>(p, s, ev0, ev1);
+    if (!descriptor_ok(p)) return launch_cfg_x<WM, WN, TM, TN, KS, 1>(p, s, ev0, ev1);
+    if constexpr (PWF)
+        if (pointwise_ok(p)) return launch_cfg_x<WM, WN, TM, TN, KS, 0, 1, 0, true>(p, s, ev0, ev1);
+    return launch_cfg_x<WM, WN, TM, TN, KS, 0>(p, s, ev0, ev1);
 }
 // 8-wave shapes exist for the descriptor path only; anything else falls back to the 4-wave shape of the same tile
-template <int WM, int WN, int TM, int TN, int KS, int KSF>
+template <int WM, int WN, int TM, int TN, int KS, int KSF, bool PWF = false>
 static int launch_cfg_k2(const ConvParams& p, hipStream_t s, hipEvent_t ev0, hipEvent_t ev1) {
-    return descriptor_ok(p) ? launch_cfg_x<WM, WN, TM, TN, KS, 0, 2>(p, s, ev0, ev1) : launch_cfg_x<WM, WN, TM, TN, KSF, 1>(p, s, ev0, ev1);
+    if (!descriptor_ok(p)) return launch_cfg_x<WM, WN, TM, TN, KSF, 1>(p, s, ev0, ev1);
+    if constexpr (PWF)
+        if (pointwise_ok(p)) return launch_cfg_x<WM, WN, TM, TN, KS, 0, 2, 0, true>(p, s, ev0, ev1);
+    return launch_cfg_x<WM, WN, TM, TN, KS, 0, 2>(p, s, ev0, ev1);
+}
+// the 16-bit kernels (PR = 1 / 2) with the launch's address form
+template <int WM, int WN, int TM, int TN, int KS, int WK, int PR>
+static int launch_cfg16(const ConvParams& p, hipStream_t s, hipEvent_t ev0, hipEvent_t ev1) {
+    if (pointwise_ok(p)) return launch_cfg_x<WM, WN, TM, TN, KS, 0, WK, PR, true>(p, s, ev0, ev1);
+    return launch_cfg_x<WM, WN, TM, TN, KS, 0, WK, PR>(p, s, ev0, ev1);
 }
 
 // 16-bit operands already stored in the operand type, filter rows a whole number of 64-element steps: the scheduled kernel's
@@ -830,16 +920,16 @@ int apse_launch_conv(const ConvParams& p, int cfg, hipStream_t s, hipEvent_t ev0
         if (c16 >= 0) {
             int rc = APSE_E_INVALID;
             if (p.prec == 1) {
-                if (c16 == 0) rc = launch_cfg_x<2, 2, 2, 2, 1, 0, 1, 1>(p, s, ev0, ev1);
-                else if (c16 == 1) rc = launch_cfg_x<2, 2, 1, 1, 2, 0, 1, 1>(p, s, ev0, ev1);
-                else if (c16 == 3) rc = launch_cfg_x<4, 1, 1, 2, 1, 0, 1, 1>(p, s, ev0, ev1);
-                else if (c16 == 6) rc = launch_cfg_x<2, 2, 1, 1, 2, 0, 2, 1>(p, s, ev0, ev1);
+                if (c16 == 0) rc = launch_cfg16<2, 2, 2, 2, 1, 1, 1>(p, s, ev0, ev1);
+                else if (c16 == 1) rc = launch_cfg16<2, 2, 1, 1, 2, 1, 1>(p, s, ev0, ev1);
+                else if (c16 == 3) rc = launch_cfg16<4, 1, 1, 2, 1, 1, 1>(p, s, ev0, ev1);
+                else if (c16 == 6) rc = launch_cfg16<2, 2, 1, 1, 2, 2, 1>(p, s, ev0, ev1);
                 else if (c16 == 8) rc = launch_cfg_x<4, 2, 2, 2, 1, 0, 1, 1>(p, s, ev0, ev1);      // 256x128, 8 waves
             } else {
-                if (c16 == 0) rc = launch_cfg_x<2, 2, 2, 2, 1, 0, 1, 2>(p, s, ev0, ev1);
-                else if (c16 == 1) rc = launch_cfg_x<2, 2, 1, 1, 2, 0, 1, 2>(p, s, ev0, ev1);
-                else if (c16 == 3) rc = launch_cfg_x<4, 1, 1, 2, 1, 0, 1, 2>(p, s, ev0, ev1);
-                else if (c16 == 6) rc = launch_cfg_x<2, 2, 1, 1, 2, 0, 2, 2>(p, s, ev0, ev1);
+                if (c16 == 0) rc = launch_cfg16<2, 2, 2, 2, 1, 1, 2>(p, s, ev0, ev1);
+                else if (c16 == 1) rc = launch_cfg16<2, 2, 1, 1, 2, 1, 2>(p, s, ev0, ev1);
+                else if (c16 == 3) rc = launch_cfg16<4, 1, 1, 2, 1, 1, 2>(p, s, ev0, ev1);
+                else if (c16 == 6) rc = launch_cfg16<2, 2, 1, 1, 2, 2, 2>(p, s, ev0, ev1);
                 else if (c16 == 8) rc = launch_cfg_x<4, 2, 2, 2, 1, 0, 1, 2>(p, s, ev0, ev1);
             }
             return rc;              // launch_cfg_x adds the split-K reduce pass itself
@@ -848,18 +938,18 @@ int apse_launch_conv(const ConvParams& p, int cfg, hipStream_t s, hipEvent_t ev0
         return APSE_E_INVALID;
     }
     switch (cfg) {
-        case 0: return launch_cfg<2, 2, 2, 2, 1>(p, s, ev0, ev1);
-        case 1: return launch_cfg<2, 2, 1, 1, 2>(p, s, ev0, ev1);
+        case 0: return launch_cfg<2, 2, 2, 2, 1, true>(p, s, ev0, ev1);
+        case 1: return launch_cfg<2, 2, 1, 1, 2, true>(p, s, ev0, ev1);
         case 2: {                                                        // the Cout <= 32 heads: also fed by 16-bit activations
             const bool small = (((size_t)p.B * p.H * p.W) << p.cin_log2) * 4 < 0xfffffff0ull;
             if (small && p.x_st == 1 && p.cin_log2 >= 2) return launch_cfg_x<4, 1, 1, 1, 2, 2>(p, s, ev0, ev1);
             if (small && p.x_st == 2 && p.cin_log2 >= 2) return launch_cfg_x<4, 1, 1, 1, 2, 3>(p, s, ev0, ev1);
             return launch_cfg<4, 1, 1, 1, 2>(p, s, ev0, ev1);
         }
-        case 3: return launch_cfg<4, 1, 1, 2, 1>(p, s, ev0, ev1);
+        case 3: return launch_cfg<4, 1, 1, 2, 1, true>(p, s, ev0, ev1);
         case 4: return launch_cfg<2, 2, 1, 1, 1>(p, s, ev0, ev1);     // 64x64, 32-deep steps: 32 KB of LDS, up to 4-5 blocks per CU
         case 5: return launch_cfg<4, 1, 1, 1, 1>(p, s, ev0, ev1);     // 128x32, 32-deep steps
-        case 6: return launch_cfg_k2<2, 2, 1, 1, 2, 2>(p, s, ev0, ev1);  // 64x64, 8 waves: two k groups, 64-deep steps
+        case 6: return launch_cfg_k2<2, 2, 1, 1, 2, 2, true>(p, s, ev0, ev1);  // 64x64, 8 waves: two k groups, 64-deep steps
         case 7: return launch_cfg_k2<2, 2, 1, 1, 4, 2>(p, s, ev0, ev1);  // 64x64, 8 waves, 128-deep steps
         case 8: return launch_cfg<2, 2, 2, 2, 1>(p, s, ev0, ev1);        // (256x128 exists for 16-bit operands only)
         default: return APSE_E_INVALID;

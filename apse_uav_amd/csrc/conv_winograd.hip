@@ -24,12 +24,16 @@
 // 1, 2 and 3 of slice s (sched_barrier), each followed by the fetch of slice s + 2 into the registers it freed.  The second
 // xi's fragments are read behind the first xi's MFMAs, and the slice's last MFMA group runs after the barrier, behind the
 // next slice's first fragment reads.  Every accumulator still takes its products channel-ascending, one k-step after the
-// other, and the transforms keep their operation order: the bits are those of the unscheduled loop.
+// other, and the transforms keep their operation order: the bits are those of the unscheduled loop.  The loop carries no
+// address arithmetic: the slice displacement of the twelve fetches is their scalar offset, and the loop runs two slices per
+// round so that the LDS buffer parity is a constant of each copy (instruction offsets); the only vector ALU work of a slice
+// is the transform (32 instructions; profiles/r11b_resource_usage.txt).
 // Epilogue: per 32-channel half of the N tile the accumulators go to LDS as [16][64 t][32 co]; each thread then owns one
 // tile x 4 channels, applies A^T . A, bias, ReLU and stores the 2x2 pixels as dwordx4 (pixels past H / W are dropped).
 // No atomics: a tile's result depends on nothing but its inputs (not on batch, grid or history).  The Cin split (SPLIT, below)
 // writes partial tiles into workspace slabs that conv_splitk_reduce4 sums in a fixed order.
 #include "apse_common.h"
+#include <type_traits>
 
 namespace {
 constexpr int WT = 64;                    // Winograd tiles per block: WTR rows x WTC columns, a template parameter of the kernel
@@ -128,20 +132,25 @@ __global__ __launch_bounds__(NTHR) void conv_winograd_f32(const ConvParams p) {
 
     // one register set: a slice is fetched one slice ahead of the MFMAs that use it and handed to LDS inside the MFMA stream
     // of the slice before (see the loop)
+    // The slice's displacement kb is wave-uniform and rides in the loads' scalar offset: the twelve per-lane offsets stay what
+    // they were in front of the loop.  A tap outside the image keeps its base of 2 GiB, past any range with or without kb; a
+    // slice past the last one (of a split: past the share) reads through the empty range.
+    const __amdgpu_buffer_rsrc_t unone = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(p.wu), 0, 0, 0x00020000);
     f32x4 xr[2][4], ur[4];
     auto fetch_u = [&](int s) {
-        const unsigned kb = (unsigned)(s_begin + s) * ustep;
+        const int kb = (int)((unsigned)(s_begin + s) * ustep);
+        const __amdgpu_buffer_rsrc_t rs = s < nsteps ? ursrc : unone;
 #pragma unroll
-        for (int k = 0; k < 4; ++k) ur[k] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(ursrc, (int)(uoff[k] + kb), 0, 0));
+        for (int k = 0; k < 4; ++k) ur[k] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(rs, (int)uoff[k], kb, 0));
     };
     auto fetch_x = [&](int s) {
-        const unsigned kb = (unsigned)((s_begin + s) * KC * 4);
+        const int kb = (s_begin + s) * KC * 4;
         const __amdgpu_buffer_rsrc_t rs = s < nsteps ? xrsrc : xnone;
 #pragma unroll
         for (int r = 0; r < 2; ++r)
 #pragma unroll
             for (int c = 0; c < 4; ++c)
-                xr[r][c] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(rs, (int)(xoff[r][c] + kb), 0, 0));
+                xr[r][c] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(rs, (int)xoff[r][c], kb, 0));
     };
     auto write_u = [&](int buf) {
 #pragma unroll
@@ -203,8 +212,10 @@ __global__ __launch_bounds__(NTHR) void conv_winograd_f32(const ConvParams p) {
                 acc[a][i][j] = __builtin_amdgcn_mfma_f32_32x32x2f32(af[a][i][k], bf[a][j][k], acc[a][i][j], 0, 0, 0);
     };
     read_frags(0, 0);
-    for (int s = 0; s < nsteps; ++s) {
-        const int buf = s & 1;
+    // one slice; BUF = s & 1 is a compile-time constant (the loop below runs two slices per round), so every LDS address of
+    // the slice is a per-lane base fixed in front of the loop plus an instruction offset
+    auto slice = [&](auto BUF, int s) {
+        constexpr int buf = decltype(BUF)::value;
         read_frags(buf, 1);                              // lands behind the first xi's MFMAs
 #pragma unroll
         for (int g = 0; g < 7; ++g) {                    // MFMA groups 0..6 of the slice: (xi, k-step) = (g >> 2, g & 3)
@@ -220,6 +231,10 @@ __global__ __launch_bounds__(NTHR) void conv_winograd_f32(const ConvParams p) {
         read_frags(buf ^ 1, 0);                          // the next slice's first fragments, behind this slice's last group
         __builtin_amdgcn_sched_barrier(0);
         mfma_group(1, 3);
+    };
+    for (int s = 0; s < nsteps; s += 2) {
+        slice(std::integral_constant<int, 0>{}, s);
+        if (s + 1 < nsteps) slice(std::integral_constant<int, 1>{}, s + 1);
     }
 
     // ---- epilogue, one 32-channel half of the N tile at a time

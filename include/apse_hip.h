@@ -285,6 +285,9 @@ int apse_conv2d(const apse_conv_desc* d, const float* x_dev, const float* w_pack
 int apse_conv2d_ex(const apse_conv_desc* d, const void* x_dev, const float* w_packed_dev, const float* bias_dev, const void* res_dev,
                    void* y_dev, float* ws_dev, size_t ws_bytes, const int* count_dev, int hint_items, int y_ld, int deconv,
                    void* stream);
+/* How many launches of this process took the pointwise address form of the tiled kernel (1x1 / pad 0 layers unless the
+ * environment has APSE_IGEMM_ADDR=0; csrc/conv_igemm.hip).  A test / tool helper: it shows which kernel a layer ran. */
+unsigned apse_conv_pointwise_launches(void);
 /* One layer through the fused f32 Winograd F(2x2,3x3) kernel the f32 plan uses for its p2 / p3 3x3 layers (a test / tool helper,
  * like apse_conv2d, which keeps the direct kernels).  apse_winograd_pack_filter: OIHW host filter [Cout][Cin][3][3], Cin a power of
  * two >= 8 -> U = G g G^T, 16 * Cout * Cin floats on the host, the bytes a context uploads.  apse_winograd_conv2d: f32 NHWC in /

@@ -131,7 +131,9 @@ for r in fr:
             lab = 'glds' + (kn.split('<')[1].split('>')[0] if '<' in kn else '')
         else:
             lab = kn.split('<')[1].split('>')[0] if '<' in kn else kn.split('conv_igemm')[1][:28]
-        items.append([lab[-22:], d, r['Grid_Size_X'], r['Grid_Size_Y']])
+            if lab.endswith(', apse_pointwise'):      # the pointwise address form of the same tile shape
+                lab = 'pw ' + lab[:-len(', apse_pointwise')]
+        items.append([lab[-28:], d, r['Grid_Size_X'], r['Grid_Size_Y']])
     elif ('conv_splitk_reduce' in kn.split('(')[0] or 'assoc_fc_finish' in kn.split('(')[0]) and items:
         items[-1][1] += d
 assert len(items) == len(layers), (len(items), len(layers))
