@@ -190,6 +190,8 @@ SIGNATURES = {
     "apse_mask_loss_backward": ([vp, i, vp, vp, i, vp, vp, vp], i),
     "apse_mask_predictor_backward": ([vp, vp, vp, vp, i, i, vp, vp, vp, vp, sz, vp], i),
     "apse_coco_mask_targets": ([vp, vp, i, vp, i, i, vp, vp, i, i, vp, vp, vp], i),
+    "apse_mots_remap_windows": ([vp, i, i, i, vp, vp, i, i, vp, vp, vp], i),
+    "apse_bitmask_targets": ([vp, i, i, i, vp, vp, i, i, vp, vp], i),
     "apse_box_roi_features": ([vp, i, vp, i, vp, vp], i),
     "apse_proposals": ([vp, i, vp, vp, vp], i),
     "apse_box_train_workspace_bytes": ([i, i], sz),

@@ -183,6 +183,12 @@ int apse_k_mask_roi_index(int* idx, int n, hipStream_t s);
 // ---- coco_eval.hip (the polygon rule lives there; apse_coco_mask_targets of mask_train.hip checks the limits and calls this)
 int apse_k_mask_targets(const double* xy, const int* part_vert_off, int n_parts, const int* obj_part_off, int n_obj, int n_verts,
                         const float* rois, const int* matched, int n, uint8_t* targets, int* info, hipStream_t s);
+// ---- bitmask_targets.hip
+struct apse_mots_window;
+int apse_k_remap_windows(const apse_mots_window* src, int n, const int* xmap, const int* ymap, int h, int w,
+                         const apse_mots_window* dst, hipStream_t s);
+int apse_k_bitmask_targets(const apse_mots_window* windows, int n_obj, int h, int w, const float* rois, const int* matched, int n,
+                           int mask_size, uint8_t* out, hipStream_t s);
 // ---- augment.hip
 int apse_k_augment(const uint8_t* src, int B, int H, int W, const AugmentBatch* P_host, uint8_t* out_u8, float* out_chw,
                    unsigned long long* sums, hipStream_t s);

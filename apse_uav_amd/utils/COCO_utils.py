@@ -5,7 +5,11 @@ dcnn/scripts/train/finetune_segmentation.py leans on (dataset dictionaries, ``Po
   (non-crowd annotations of the allowed class names, category ids mapped), ground-truth boxes as precomputed proposals.
   The reference's line ``annotation_dict['segmentation'] = ann['segmentation'],`` wraps the polygon list in a 1-tuple by accident;
   here the list itself is stored.  RLE (dict) segmentations are refused: the reference drops crowds, and non-crowd COCO
-  annotations are polygons.
+  annotations are polygons -- unless ``mask_format="bitmask"``, which keeps them.
+* ``DeviceBitmasks`` / ``nearest_maps`` / ``bitmask_targets_device`` / ``bitmask_targets``: detectron2's INPUT.MASK_FORMAT =
+  "bitmask" -- RLE, dense and ``WindowMask`` ground truth as bit windows on the device, resized / flipped with Pillow's
+  nearest-neighbour map (``apse_mots_remap_windows``), targets by ``BitMasks.crop_and_resize`` (``apse_bitmask_targets``).  The
+  loaders take ``mask_format="bitmask"``; DESIGN.md "Bitmask ground truth".
 * ``detectron2_dataset_to_coco``: the dictionaries back to a COCO dataset (for ``utils.coco.COCO.from_dataset`` / ``COCOeval``).
 * ``mask_targets``: ``PolygonMasks.crop_and_resize`` (``rasterize_polygons_within_box``) at 28 x 28: the polygon transform on the
   host in float64, the rasterisation by ``apse_coco_poly_to_bits`` (equal to pycocotools ``frPyObjects`` + ``merge``).
@@ -28,16 +32,20 @@ from . import resample
 
 MASK_SIZE = 28
 XYWH_ABS = 1          # detectron2 BoxMode.XYWH_ABS
+MASK_FORMATS = ("polygon", "bitmask")
 
 
 def generate_coco_dataset_dictionaries(json_file, imgfolder, allowed_classes=None, category_mapping=None,
-                                       precomputed_proposals=True, keep_box_only=False):
+                                       precomputed_proposals=True, keep_box_only=False, mask_format="polygon"):
     """-> list of {file_name, image_id, height, width, annotations: [{bbox (XYWH), bbox_mode, category_id, segmentation, iscrowd}],
     proposal_boxes (XYXY f32 [k, 4]), proposal_objectness_logits, proposal_bbox_mode}.  ``allowed_classes``: category NAMES to
     keep (None: all); ``category_mapping``: {json category id: training class index} (None: the sorted kept ids -> 0..K-1).
     Images left without annotations are dropped, as the reference does.  An annotation without a segmentation is dropped too,
     unless ``keep_box_only`` (the joint loop with the mask head, where box-only data feeds the RPN and box losses): it is then
-    kept with ``segmentation`` []."""
+    kept with ``segmentation`` [].  ``mask_format`` "polygon" refuses an RLE (dict) segmentation; "bitmask" (detectron2's
+    INPUT.MASK_FORMAT) keeps it as it is, beside polygon lists, for ``DeviceBitmasks``."""
+    if mask_format not in MASK_FORMATS:
+        raise ValueError("mask_format must be one of %s, got %r" % (MASK_FORMATS, mask_format))
     with open(json_file) as fh:
         data = json.load(fh)
     names = {c["id"]: c["name"] for c in data["categories"]}
@@ -54,7 +62,10 @@ def generate_coco_dataset_dictionaries(json_file, imgfolder, allowed_classes=Non
             if ann.get("iscrowd", 0) or ann["category_id"] not in keep_ids or ann["category_id"] not in category_mapping:
                 continue
             seg = ann.get("segmentation")
-            if isinstance(seg, dict):
+            if isinstance(seg, dict) and mask_format == "bitmask":
+                if "counts" not in seg or "size" not in seg:
+                    raise ValueError("annotation %s: an RLE segmentation needs 'counts' and 'size'" % ann.get("id"))
+            elif isinstance(seg, dict):
                 raise ValueError("annotation %s: RLE segmentations are not supported for mask-head training (non-crowd COCO "
                                  "annotations are polygons)" % ann.get("id"))
             if not seg:
@@ -63,7 +74,8 @@ def generate_coco_dataset_dictionaries(json_file, imgfolder, allowed_classes=Non
                 seg = []
             anns.append({"bbox": [float(v) for v in ann["bbox"]], "bbox_mode": XYWH_ABS,
                          "category_id": int(category_mapping[ann["category_id"]]),
-                         "segmentation": [list(map(float, p)) for p in seg],          # the list itself (not the reference's 1-tuple)
+                         # the list itself (not the reference's 1-tuple); an RLE dict as it is
+                         "segmentation": seg if isinstance(seg, dict) else [list(map(float, p)) for p in seg],
                          "iscrowd": 0})
         if not anns:
             continue
@@ -201,6 +213,241 @@ def select_mask_rows(labels, matched, parts_per_gt, num_classes):
     return fg[has].astype(np.int64), int(len(fg) - has.sum())
 
 
+# ---------------------------------------------------------------- bitmask ground truth (detectron2 INPUT.MASK_FORMAT = "bitmask")
+def nearest_maps(src, dst, flip_before=False, flip_after=False, vertical=False):
+    """The source index of every destination index of ``Image.resize(..., Image.NEAREST)`` from ``src`` to ``dst`` pixels along
+    one axis (``vertical``: rows), int32 [dst] -- what detectron2's ``ResizeTransform.apply_segmentation`` does to a mask.  Taken
+    from Pillow itself, by resizing an index ramp of mode "I": Pillow steps the source coordinate incrementally, so
+    floor((x + 0.5) * src / dst) is not always its answer.  ``flip_before`` mirrors the source first (the host-flip path of
+    ``MaskTrainLoader.prepare_image``), ``flip_after`` mirrors the result (``prepare_augmented``: resize, then flip)."""
+    from PIL import Image
+    src, dst = int(src), int(dst)
+    if src < 1 or dst < 1:
+        raise ValueError("nearest_maps: sizes must be positive, got %d -> %d" % (src, dst))
+    ramp = np.arange(src, dtype=np.int32)
+    if vertical:
+        m = np.asarray(Image.fromarray(ramp.reshape(src, 1)).resize((1, dst), Image.NEAREST))[:, 0]
+    else:
+        m = np.asarray(Image.fromarray(ramp.reshape(1, src)).resize((dst, 1), Image.NEAREST))[0]
+    m = m.astype(np.int32)
+    if flip_before:
+        m = src - 1 - m
+    if flip_after:
+        m = m[::-1]
+    return np.ascontiguousarray(m)
+
+
+def _map_range(m, lo, hi):
+    """The half-open range of indices i with lo <= m[i] < hi for a monotone map; (0, 0) when there is none."""
+    idx = np.nonzero((m >= lo) & (m < hi))[0]
+    return (int(idx[0]), int(idx[-1]) + 1) if len(idx) else (0, 0)
+
+
+def _is_polygon_list(seg):
+    return isinstance(seg, (list, tuple)) and len(seg) > 0
+
+
+class DeviceBitmasks:
+    """The masks of one image's objects as bit windows on the device (include/apse_hip.h ``apse_mots_window``), uploaded once:
+    what ``apse_bitmask_targets`` reads.  A segmentation is an RLE dict (compressed string / bytes or a plain count list; its
+    ``size`` must equal ``frame_hw``), a ``WindowMask`` of that frame, a dense bool / u8 [H][W] array or tensor, or a polygon
+    list (rasterised at ``frame_hw`` by ``apse_coco_poly_to_bits``).  ``[]`` or ``None`` is "no mask": an empty window, and
+    ``has_mask`` (host bool [n_obj]) is False there -- the analogue of ``DevicePolygons.parts == 0``.  ``host`` is the host copy
+    of the window structs and ``windows`` the device one."""
+
+    def __init__(self, segmentations, frame_hw, device):
+        from ..structures import device_windows as dw
+        from ..structures.window_mask import WindowMask
+        from . import mots_eval as me
+        H, W = (int(v) for v in frame_hw)
+        dev = torch.device(device)
+        n = len(segmentations)
+        if n > me.MAX_OBJECTS:
+            raise ValueError("%d objects in one image, more than %d" % (n, me.MAX_OBJECTS))
+        host = dw.fill_windows(np.zeros((n, 4), np.int64), np.zeros(n, np.int64), np.zeros(n, np.uint64)) if n else \
+            dw.fill_windows((), (), ())
+        has = np.zeros(n, bool)
+        polys, rles, words, keep = [], [], [], []
+        for k, seg in enumerate(segmentations):
+            if seg is None or (isinstance(seg, (list, tuple)) and len(seg) == 0):
+                continue
+            has[k] = True
+            if isinstance(seg, dict):
+                if "counts" not in seg or "size" not in seg:
+                    raise ValueError("segmentation %d: an RLE dict needs 'counts' and 'size'" % k)
+                counts, rh, rw = cocomod.rle_counts(seg)
+                if (rh, rw) != (H, W):
+                    raise ValueError("segmentation %d: an RLE of size %dx%d in a frame of %dx%d" % (k, rh, rw, H, W))
+                rles.append((k, counts))
+            elif isinstance(seg, (list, tuple)):
+                parts = []
+                for p in seg:
+                    a = np.asarray(p, np.float64).reshape(-1)
+                    parts.append(a[:2 * (len(a) // 2)].reshape(-1, 2))
+                polys.append((k, parts))
+            elif isinstance(seg, WindowMask):
+                if tuple(int(v) for v in seg.frame_size) != (H, W):
+                    raise ValueError("segmentation %d: a WindowMask of frame %s in a frame of %dx%d" % (k, tuple(seg.frame_size), H, W))
+                words.append((k, seg))
+            elif isinstance(seg, np.ndarray) or torch.is_tensor(seg):
+                if tuple(seg.shape) != (H, W):
+                    raise ValueError("segmentation %d: a dense mask of shape %s in a frame of %dx%d" % (k, tuple(seg.shape), H, W))
+                if isinstance(seg, np.ndarray):
+                    seg = torch.from_numpy(np.ascontiguousarray(seg != 0))
+                words.append((k, seg if seg.dtype == torch.bool else seg != 0))
+            else:
+                raise ValueError("segmentation %d: unsupported type %s" % (k, type(seg).__name__))
+        if polys:
+            win, kp = cocomod.polygons_to_windows([(parts, H, W) for _, parts in polys], dev)
+            host[[k for k, _ in polys]] = dw.read_back(win)
+            keep.append(kp)
+        if rles:
+            win, kp = me.rle_masks([c for _, c in rles], H, W, dev)
+            host[[k for k, _ in rles]] = dw.read_back(win)
+            keep.append(kp)
+        if words:
+            rects, wprs, ptrs, *kp = dw.masks_words([m for _, m in words], (H, W), dev)
+            host[[k for k, _ in words]] = dw.fill_windows(rects, wprs, ptrs)
+            keep.append(kp)
+        self._set(host, (H, W), dev, has, keep)
+
+    def _set(self, host, frame_hw, dev, has_mask, keep):
+        from ..structures import device_windows as dw
+        self.host, self.frame_hw, self.device, self.has_mask, self.keep = host, frame_hw, dev, has_mask, keep
+        self.n_obj = len(host)
+        self.windows = dw.upload(host, dev)
+
+    @classmethod
+    def _from(cls, host, frame_hw, dev, has_mask, keep):
+        self = cls.__new__(cls)
+        self._set(host, frame_hw, dev, has_mask, keep)
+        return self
+
+    @classmethod
+    def merged(cls, n, groups, frame_hw, device):
+        """``n`` objects from DeviceBitmasks of one frame: ``groups`` = [(object indices, DeviceBitmasks of those objects)];
+        an object in no group has no mask."""
+        from ..structures import device_windows as dw
+        host = dw.fill_windows(np.zeros((n, 4), np.int64), np.zeros(n, np.int64), np.zeros(n, np.uint64)) if n else \
+            dw.fill_windows((), (), ())
+        has = np.zeros(n, bool)
+        keep = []
+        for idx, bm in groups:
+            if tuple(bm.frame_hw) != tuple(int(v) for v in frame_hw):
+                raise ValueError("merged: bitmasks of frame %s in a frame of %s" % (tuple(bm.frame_hw), tuple(frame_hw)))
+            if len(idx):
+                host[list(idx)] = bm.host
+                has[list(idx)] = bm.has_mask
+            keep.append(bm)
+        return cls._from(host, tuple(int(v) for v in frame_hw), torch.device(device), has, keep)
+
+    def transformed(self, image_hw, xmap, ymap):
+        """These masks after a nearest-neighbour resize and / or flip (``nearest_maps``): a DeviceBitmasks in the image of
+        ``image_hw`` whose pixel (x, y) is this one's (``xmap[x]``, ``ymap[y]``), through ``apse_mots_remap_windows``.  The
+        destination rects come from the source rects and the (monotone) maps here on the host."""
+        from .. import _lib
+        from ..structures import device_windows as dw
+        h, w = (int(v) for v in image_hw)
+        xmap = np.ascontiguousarray(xmap, np.int32).reshape(-1)
+        ymap = np.ascontiguousarray(ymap, np.int32).reshape(-1)
+        H, W = self.frame_hw
+        if len(xmap) != w or len(ymap) != h:
+            raise ValueError("transformed: maps of %d columns and %d rows for an image of %dx%d" % (len(xmap), len(ymap), h, w))
+        if len(xmap) and (xmap.min() < 0 or xmap.max() >= W) or len(ymap) and (ymap.min() < 0 or ymap.max() >= H):
+            raise ValueError("transformed: a map entry outside the %dx%d frame" % (H, W))
+        for m in (xmap, ymap):
+            d = np.diff(m)
+            if len(d) and not ((d >= 0).all() or (d <= 0).all()):
+                raise ValueError("transformed: the maps must be monotone")
+        rects = np.zeros((self.n_obj, 4), np.int64)
+        for k in range(self.n_obj):
+            x0, y0, x1, y1 = (int(v) for v in self.host["rect"][k])
+            if x1 <= x0 or y1 <= y0 or not int(self.host["bits"][k]):
+                continue
+            (dx0, dx1), (dy0, dy1) = _map_range(xmap, x0, x1), _map_range(ymap, y0, y1)
+            if dx1 > dx0 and dy1 > dy0:
+                rects[k] = dx0, dy0, dx1, dy1
+        arr, pool = dw.pooled_windows(rects, self.device)
+        dst = dw.upload(arr, self.device)
+        xm, ym = torch.from_numpy(xmap).to(self.device), torch.from_numpy(ymap).to(self.device)
+        _lib.check(_lib.load().apse_mots_remap_windows(_lib.ptr(self.windows), self.n_obj, H, W, _lib.ptr(xm), _lib.ptr(ym), h, w,
+                                                       _lib.ptr(dst), _lib.ptr(arr), _lib.stream_ptr()), None,
+                   "apse_mots_remap_windows")
+        return DeviceBitmasks._from(arr, (h, w), self.device, self.has_mask.copy(), [pool, xm, ym, self])
+
+
+def bitmask_targets_device(bitmasks, rois, matched, mask_size=MASK_SIZE, out=None):
+    """``BitMasks.crop_and_resize`` for proposals that are new every step (``apse_bitmask_targets``), with the contract of
+    ``mask_targets_device``: ``bitmasks`` a DeviceBitmasks in image coordinates, ``rois`` f32 [n][4] and ``matched`` int32 [n] on
+    the device -> uint8 [n][mask_size][mask_size] on the device.  One launch, no host step.  ``out``: a uint8 buffer of at
+    least n rows to write into (rows past n stay untouched); the result is its first n rows."""
+    from .. import _lib
+    dev = bitmasks.device
+    rois = torch.as_tensor(rois, dtype=torch.float32).reshape(-1, 4).to(dev).contiguous()
+    matched = torch.as_tensor(matched).reshape(-1).to(dev, torch.int32).contiguous()
+    n = int(rois.shape[0])
+    if int(matched.shape[0]) != n:
+        raise ValueError("bitmask_targets_device: %d boxes, %d matched indices" % (n, int(matched.shape[0])))
+    if out is None:
+        out = torch.empty((n, mask_size, mask_size), dtype=torch.uint8, device=dev)
+    elif out.dtype != torch.uint8 or not out.is_contiguous() or out.dim() != 3 or out.shape[0] < n or \
+            tuple(out.shape[1:]) != (mask_size, mask_size) or out.device != rois.device:
+        raise ValueError("bitmask_targets_device: out must be a contiguous uint8 [>= n][%d][%d] tensor on the device" % (mask_size, mask_size))
+    h, w = bitmasks.frame_hw
+    _lib.check(_lib.load().apse_bitmask_targets(_lib.ptr(bitmasks.windows), bitmasks.n_obj, h, w, _lib.ptr(rois), _lib.ptr(matched), n,
+                                                int(mask_size), _lib.ptr(out), _lib.stream_ptr()), None, "apse_bitmask_targets")
+    return out[:n]
+
+
+def bitmask_targets(segmentations, boxes, frame_hw, device, mask_size=MASK_SIZE):
+    """``BitMasks.crop_and_resize(boxes, mask_size)`` of ground-truth boxes: segmentation r under box r (the analogue of
+    ``mask_targets``); uint8 [n][mask_size][mask_size] on the device."""
+    n = len(segmentations)
+    if n == 0:
+        return torch.zeros((0, mask_size, mask_size), dtype=torch.uint8, device=device)
+    bm = DeviceBitmasks(segmentations, frame_hw, device)
+    return bitmask_targets_device(bm, np.asarray(boxes, np.float64).reshape(-1, 4).astype(np.float32), np.arange(n, dtype=np.int32),
+                                  mask_size)
+
+
+class BitmaskSource:
+    """One image's segmentations on their way through a loader in bitmask mode, in place of the polygon lists: ``segs`` as the
+    dataset stores them (frame coordinates), ``polys`` the polygon objects transformed to the image as the polygon path
+    transforms them ([] for the others), and the maps of the image's resize / flip.  ``device_bitmasks`` builds the image's
+    DeviceBitmasks: polygons are rasterised at the image size (detectron2 transforms polygons first, ``polygons_to_bitmask``
+    after), RLE / dense / WindowMask objects are uploaded in the frame and remapped."""
+
+    def __init__(self, segs, polys, frame_hw, image_hw, xmap, ymap):
+        self.segs, self.polys, self.frame_hw, self.image_hw, self.xmap, self.ymap = list(segs), list(polys), frame_hw, image_hw, xmap, ymap
+
+    def __len__(self):
+        return len(self.segs)
+
+    def select(self, idx):
+        return BitmaskSource([self.segs[i] for i in idx], [self.polys[i] for i in idx], self.frame_hw, self.image_hw, self.xmap, self.ymap)
+
+    def device_bitmasks(self, device):
+        poly_idx = [k for k, s in enumerate(self.segs) if _is_polygon_list(s)]
+        raw_idx = [k for k, s in enumerate(self.segs) if not _is_polygon_list(s) and s is not None and not isinstance(s, (list, tuple))]
+        groups = []
+        if poly_idx:
+            groups.append((poly_idx, DeviceBitmasks([self.polys[k] for k in poly_idx], self.image_hw, device)))
+        if raw_idx:
+            raw = DeviceBitmasks([self.segs[k] for k in raw_idx], self.frame_hw, device)
+            groups.append((raw_idx, raw.transformed(self.image_hw, self.xmap, self.ymap)))
+        return DeviceBitmasks.merged(len(self.segs), groups, self.image_hw, device)
+
+
+def split_polygon_segmentations(segs, mask_format="bitmask"):
+    """Bitmask mode: the polygon objects of ``segs`` as polygon lists, [] for every other object (they take no polygon
+    transform).  Polygon mode: ``segs`` itself, and an RLE dict among them is refused."""
+    if mask_format != "bitmask":
+        if any(isinstance(s, dict) for s in segs):
+            raise ValueError("RLE segmentations need mask_format=\"bitmask\"")
+        return segs
+    return [s if _is_polygon_list(s) else [] for s in segs]
+
+
 def flip_annotations(boxes, polygons_per_roi, width):
     """Horizontal flip of XYXY boxes and polygons (detectron2 HFlipTransform: x -> width - x)."""
     b = np.asarray(boxes, np.float64).reshape(-1, 4).copy()
@@ -236,9 +483,12 @@ class MaskTrainLoader:
     ``len(min_sizes)`` (8 for "range") -- the model then keeps that many contexts alive instead of rebuilding one per image."""
 
     def __init__(self, dicts, model, ims_per_batch=2, seed=0, flip=False, cache_features=False, max_rois=1024, augment=False,
-                 min_sizes=None, max_size=None, sampling="choice"):
+                 min_sizes=None, max_size=None, sampling="choice", mask_format="polygon"):
         if getattr(model, "c4", False):
             raise NotImplementedError("mask-head training covers FPN models; C4 (Res5ROIHeads) shares res5 with the box branch")
+        if mask_format not in MASK_FORMATS:
+            raise ValueError("mask_format must be one of %s, got %r" % (MASK_FORMATS, mask_format))
+        self.mask_format = mask_format
         self.dicts = list(dicts)
         self.model = model
         self.ims_per_batch = int(ims_per_batch)
@@ -287,6 +537,8 @@ class MaskTrainLoader:
         model = self.model
         frame, boxes, polys, classes = self.read_annotated(d)
         H, W = frame.shape[:2]
+        segs = polys
+        polys = split_polygon_segmentations(segs, self.mask_format)
         if flipped:
             frame = frame[:, ::-1].copy()
             boxes, polys = flip_annotations(boxes, polys, W)
@@ -295,6 +547,9 @@ class MaskTrainLoader:
         boxes = boxes * np.array([sx, sy, sx, sy])
         polys = [[np.array(p, np.float64) * np.tile([sx, sy], len(p) // 2) for p in ps] for ps in polys]
         model.backbone_frames(torch.from_numpy(frame[None]).to(model.device))
+        if self.mask_format == "bitmask":                         # the source is flipped first, then resized
+            polys = BitmaskSource(segs, polys, (H, W), (ih, iw), nearest_maps(W, iw, flip_before=flipped),
+                                  nearest_maps(H, ih, vertical=True))
         return boxes, polys, classes
 
     def prepare_augmented(self, d, size, params):
@@ -305,7 +560,12 @@ class MaskTrainLoader:
         frame, boxes, polys, classes = self.read_annotated(d)
         H, W = frame.shape[:2]
         ih, iw = resample.resize_shortest_edge(H, W, size, self.max_size)
+        segs = polys
+        polys = split_polygon_segmentations(segs, self.mask_format)
         boxes, polys = aug.transform_annotations(boxes, polys, (H, W), (ih, iw), params.flip)
+        if self.mask_format == "bitmask":                         # resized first, then flipped
+            polys = BitmaskSource(segs, polys, (H, W), (ih, iw), nearest_maps(W, iw, flip_after=bool(params.flip)),
+                                  nearest_maps(H, ih, vertical=True))
         resized = aug.resize_frames(torch.from_numpy(frame[None]).to(model.device), ih, iw)
         _, chw, _ = aug.augment_images(resized, [params], want_u8=False)
         model.backbone_images(chw, (H, W))
@@ -315,6 +575,9 @@ class MaskTrainLoader:
         """The item of one image whose backbone has just run, from its transformed annotations: here (features, classes, targets)
         of the ground-truth boxes.  The loaders that subclass this one override it."""
         feats = self.model.mask_roi_features(boxes.astype(np.float32))
+        if self.mask_format == "bitmask":
+            bm = polys.device_bitmasks(self.model.device)
+            return feats, classes, bitmask_targets_device(bm, boxes.astype(np.float32), np.arange(len(boxes), dtype=np.int32))
         return feats, classes, mask_targets(polys, boxes, self.model.device)
 
     def image_item(self, d, flipped=False):

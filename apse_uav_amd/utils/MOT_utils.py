@@ -121,6 +121,68 @@ def read_frame_bgr(path):
     return np.ascontiguousarray(rgb[:, :, ::-1])
 
 
+def _idmap_rows(path):
+    """One instances/<seq>/%06d.png id map (u16, value = class * 1000 + instance) -> [(id, RLE dict)] in ascending id order."""
+    with Image.open(path) as im:
+        idmap = np.asarray(im)
+    if idmap.ndim != 2:
+        raise ValueError("%s is not a single-channel id map" % path)
+    return [(int(v), rle.encode((idmap == v).astype(np.uint8))) for v in np.unique(idmap) if v != 0]
+
+
+def generate_mots_dataset_dictionaries(dataset_path, seqmap_path, class_names=("car", "pedestrian")):
+    """KITTI MOTS / MOTSChallenge ground truth as detectron2-style dataset dictionaries in bitmask form (utils/COCO_utils.py
+    ``generate_coco_dataset_dictionaries(mask_format="bitmask")``): one dictionary per frame that has objects, from
+    <dataset>/instances_txt/<seq>.txt (``parse_mots_instances``) or, without it, the id maps <dataset>/instances/<seq>/%06d.png.
+    MOTS class ids 1, 2 (id // 1000) become 0, 1 -- ``class_names`` in that order; ignore regions (class 10) and any other class
+    are dropped.  ``bbox`` is ``rle_to_bbox`` of the mask (XYWH), ``segmentation`` the RLE dict, ``image_id`` counts the kept
+    frames over all sequences.  A frame whose image (<dataset>/training/image_02/<seq>/%06d.png) is missing is refused."""
+    names, _ = parse_mots_seqmap(seqmap_path)
+    K = len(class_names)
+    out = []
+    for seq in names:
+        txt = os.path.join(dataset_path, "instances_txt", seq + ".txt")
+        per_frame = {}
+        if os.path.exists(txt):
+            rows, masks = parse_mots_instances(txt)
+            for row, mask in zip(rows.tolist(), masks):
+                per_frame.setdefault(int(row[0]), []).append((int(row[1]), mask))
+        else:
+            folder = os.path.join(dataset_path, "instances", seq)
+            if not os.path.isdir(folder):
+                raise FileNotFoundError("sequence %s: neither %s nor %s exists" % (seq, txt, folder))
+            for fn in sorted(os.listdir(folder)):
+                if fn.endswith(".png"):
+                    per_frame[int(os.path.splitext(fn)[0])] = _idmap_rows(os.path.join(folder, fn))
+        for frame in sorted(per_frame):
+            anns = []
+            size = None
+            for ob_id, mask in per_frame[frame]:
+                cls = ob_id // 1000
+                if ob_id == IGNORE_ID or cls < 1 or cls > K:
+                    continue
+                h, w = (int(v) for v in mask["size"])
+                if size is not None and size != (h, w):
+                    raise ValueError("sequence %s frame %d: masks of sizes %s and %s" % (seq, frame, size, (h, w)))
+                size = (h, w)
+                bbox = mask_to_bbox(mask)
+                if bbox[2] <= 0 or bbox[3] <= 0:
+                    continue                                 # an all-zero mask: no object
+                anns.append({"bbox": bbox, "bbox_mode": 1, "category_id": cls - 1, "segmentation": mask, "iscrowd": 0,
+                             "track_id": ob_id})
+            if not anns:
+                continue
+            image = os.path.join(dataset_path, "training", "image_02", seq, "%06d.png" % frame)
+            if not os.path.exists(image):
+                raise FileNotFoundError("sequence %s frame %d: the image %s is missing" % (seq, frame, image))
+            b = np.array([a["bbox"] for a in anns], np.float32).reshape(-1, 4)
+            out.append({"file_name": image, "image_id": len(out), "height": size[0], "width": size[1], "annotations": anns,
+                        "sequence": seq, "frame": frame,
+                        "proposal_boxes": np.stack([b[:, 0], b[:, 1], b[:, 0] + b[:, 2], b[:, 1] + b[:, 3]], 1),
+                        "proposal_objectness_logits": np.ones(len(anns), np.float32), "proposal_bbox_mode": 0})
+    return out
+
+
 class MOTloader:
     """Training data of the association head from one MOT sequence (MOT_utils.py:25-130)."""
 

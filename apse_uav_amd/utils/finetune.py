@@ -18,6 +18,7 @@ AP_COLUMNS = "\t\tAP\tAP_05\tAP0.75\tAP_s\tAP_m\tAP_l\tAR_1\tAR_10\tAR_100\tAR_s
 RECALL_LIMITS = (100, 1000)
 MASK_PREDICTOR = "roi_heads.mask_head.predictor."
 CLS_SCORE = "roi_heads.box_predictor.cls_score.weight"
+SYNTHETIC_MOTS = "<generated>"          # --mots without a DATASET (with --synthetic N)
 
 
 def add_common_arguments(ap, name_default, start="heads"):
@@ -51,6 +52,35 @@ def add_common_arguments(ap, name_default, start="heads"):
     ap.add_argument("--resume", action="store_true")
     ap.add_argument("--test-on-train", action="store_true", help="score the training images instead of the held-out ones")
     ap.add_argument("--synthetic", type=int, default=0, metavar="N")
+    ap.add_argument("--mask-format", choices=("polygon", "bitmask"), default="polygon",
+                    help="ground truth of the mask head: polygon lists only, or (detectron2's INPUT.MASK_FORMAT = bitmask) RLE "
+                         "segmentations as well, with BitMasks.crop_and_resize targets; with --synthetic N the generated "
+                         "polygons are converted to RLE annotations")
+    ap.add_argument("--mots", nargs="?", const=SYNTHETIC_MOTS, default="", metavar="DATASET",
+                    help="train on a KITTI MOTS / MOTSChallenge layout (instances_txt/ or instances/, training/image_02/) with "
+                         "--seqmap FILE instead of --images / --annotations; implies --mask-format bitmask; with --synthetic N "
+                         "and no DATASET a generated one")
+    ap.add_argument("--seqmap", default="", help="the sequence map of --mots")
+
+
+def mask_format(args):
+    """The mask ground-truth format of a parsed command line: --mots implies bitmask."""
+    return "bitmask" if getattr(args, "mots", "") else getattr(args, "mask_format", "polygon")
+
+
+def annotations_to_rle(annotations, out_path):
+    """A COCO annotation file with every polygon segmentation replaced by its compressed RLE (the rasterisation of
+    utils/coco.py on the device) -> ``out_path``."""
+    import json
+    from .coco import COCO
+    coco = COCO.from_dataset(json.load(open(annotations)), verbose=False)
+    for ann in coco.dataset["annotations"]:
+        if isinstance(ann.get("segmentation"), list) and ann["segmentation"]:
+            r = coco.annToRLE(ann)
+            ann["segmentation"] = {"size": [int(v) for v in r["size"]], "counts": r["counts"].decode("ascii")}
+    with open(out_path, "w") as fh:
+        json.dump(coco.dataset, fh)
+    return out_path
 
 
 def holdout_split(n, k_folds, seed):
@@ -68,13 +98,27 @@ def load_start(args, ap):
     from ..synthetic import synthetic_dataset
     from ..weights import load_detector_file, synthetic_detector_state
     os.makedirs(args.out, exist_ok=True)
+    mots = getattr(args, "mots", "")
+    if args.synthetic and mots:
+        if mots != SYNTHETIC_MOTS:
+            ap.error("--synthetic N --mots takes no DATASET: it generates one")
+        from ..synthetic import write_synthetic_mots
+        args.mots = os.path.join(args.out, "synthetic_mots")
+        args.seqmap = write_synthetic_mots(args.mots, seqs=("0000", "0001"), frames=args.synthetic // 2 + 2)
+        return synthetic_detector_state(0, (1, 1, 1, 1), num_classes=4)
     if args.synthetic:
         args.images = os.path.join(args.out, "synthetic")
         args.annotations = synthetic_dataset(args.images, args.synthetic)
+        if mask_format(args) == "bitmask":
+            args.annotations = annotations_to_rle(args.annotations, os.path.join(args.images, "annotations_rle.json"))
         return synthetic_detector_state(0, (1, 1, 1, 1), num_classes=4)
+    if mots:
+        if mots == SYNTHETIC_MOTS or not args.seqmap or not args.weights:
+            ap.error("--mots DATASET needs --seqmap FILE and --weights (or --synthetic N --mots)")
+        return load_detector_file(args.weights)
     if args.images and args.annotations and args.weights:
         return load_detector_file(args.weights)
-    ap.error("--images, --annotations and --weights are required (or --synthetic N)")
+    ap.error("--images, --annotations and --weights are required (or --mots DATASET --seqmap FILE, or --synthetic N)")
 
 
 def training_cfg(K, context_cache):
@@ -223,8 +267,12 @@ def run(task, args, detector):
     from . import COCO_utils
     from .coco import COCO
 
-    dicts = COCO_utils.generate_coco_dataset_dictionaries(args.annotations, args.images, args.classes, None, task.precomputed_proposals,
-                                                          task.keep_box_only)
+    if getattr(args, "mots", ""):
+        from .MOT_utils import generate_mots_dataset_dictionaries
+        dicts = generate_mots_dataset_dictionaries(args.mots, args.seqmap, tuple(args.classes) if args.classes else ("car", "pedestrian"))
+    else:
+        dicts = COCO_utils.generate_coco_dataset_dictionaries(args.annotations, args.images, args.classes, None,
+                                                              task.precomputed_proposals, task.keep_box_only, mask_format(args))
     K = task.num_classes(args, detector, dicts)
     cfg = training_cfg(K, task.context_cache)
     if is_c4(cfg):
@@ -268,6 +316,7 @@ def run(task, args, detector):
     pred = task.predictor(cfg, task.merged_state(detector))
     sizes = dict(min_sizes=tuple(int(v) for v in args.min_sizes.split(",")) if args.min_sizes else None, max_size=args.max_size or None)
     loader = task.make_loader(args, train_dicts, pred.model, K, sizes)
+    loader.mask_format = mask_format(args)       # the box and RPN loaders read RLE annotations too (they make no mask targets)
     if chk is not None and ("loader" in chk or not task.loader_state_optional):
         loader.load_state_dict(chk["loader"])
 

@@ -10,7 +10,7 @@ from ..networks import box_head as bh
 from ..networks import mask_head as mh
 from ..networks import rpn_head as rh
 from .box_train import SamplingLoader, label_and_sample_proposals
-from .COCO_utils import DevicePolygons, mask_targets_device, select_mask_rows
+from .COCO_utils import DevicePolygons, bitmask_targets_device, mask_targets_device, select_mask_rows
 from .rpn_train import label_and_sample_anchors
 
 
@@ -74,6 +74,9 @@ class JointTrainLoader(SamplingLoader):
     (``mask_rcnn_loss``), against the image's polygons uploaded once.  An image or annotation without polygons gives RPN and box
     rows only.  ``last_mask_rows`` holds f per image and ``last_mask_skipped`` the foreground rows dropped for lack of polygons.
     The mask rows draw no random numbers: rpn and box are the same bits with ``mask`` on and off, and so is ``state_dict``.
+    ``mask_format="bitmask"``: the annotations may hold RLE segmentations; the image's ``DeviceBitmasks`` is built once, remapped
+    with the image's nearest-neighbour maps, and the targets are ``apse_bitmask_targets`` (``BitMasks.crop_and_resize``) of the
+    matched ground truth under the proposals; "has a polygon part" reads "has a segmentation".
 
     ``model``: a TrackRCNN (FPN, f32).  Per image: the image and annotation path of MaskTrainLoader, the frozen backbone once,
     then ``label_and_sample_anchors`` and ``rpn_patches`` for the RPN rows, then ``train_proposals`` on the context's current RPN
@@ -84,13 +87,14 @@ class JointTrainLoader(SamplingLoader):
     def __init__(self, dicts, model, ims_per_batch=2, seed=0, flip=False, augment=False, min_sizes=None, max_size=None,
                  sampling="choice", num_classes=None, rpn_batch_size_per_image=256, rpn_positive_fraction=0.5,
                  rpn_iou_thresholds=(0.3, 0.7), box_batch_size_per_image=512, box_positive_fraction=0.25, box_iou_thresh=0.5,
-                 mask=False):
+                 mask=False, mask_format="polygon"):
         if getattr(model, "c4", False):
             raise NotImplementedError("joint detection-head training covers FPN models (p2 .. p6)")
         self.mask = bool(mask)
         if self.mask:
             check_mask_rows(ims_per_batch, box_batch_size_per_image, box_positive_fraction)
-        super().__init__(dicts, model, ims_per_batch, seed, flip, False, bh.MAX_ROIS, augment, min_sizes, max_size, sampling)
+        super().__init__(dicts, model, ims_per_batch, seed, flip, False, bh.MAX_ROIS, augment, min_sizes, max_size, sampling,
+                         mask_format)
         self.num_classes = int(num_classes if num_classes is not None else model.cfg.MODEL.ROI_HEADS.NUM_CLASSES)
         self.rpn_batch_size_per_image, self.rpn_positive_fraction = int(rpn_batch_size_per_image), float(rpn_positive_fraction)
         self.rpn_iou_thresholds = (float(rpn_iou_thresholds[0]), float(rpn_iou_thresholds[1]))
@@ -129,13 +133,18 @@ class JointTrainLoader(SamplingLoader):
         """The mask item of one image from its sampled box rows: ((features, classes, targets), rows skipped).  ``matched`` indexes
         the ground truths ``ground_truth`` kept (the non-crowd annotations), so the polygons are filtered the same way."""
         model = self.model
-        gt_polys = [polys[i] for i, a in enumerate(d["annotations"]) if not a.get("iscrowd", 0)]
-        poly_dev = DevicePolygons(gt_polys, model.device)
+        keep = [i for i, a in enumerate(d["annotations"]) if not a.get("iscrowd", 0)]
         labels_host = labels.cpu().numpy()
-        rows, skipped = select_mask_rows(labels_host, matched.cpu().numpy(), poly_dev.parts, self.num_classes)
+        if self.mask_format == "bitmask":                    # polys: the image's BitmaskSource; has_mask in place of parts > 0
+            gt_dev = polys.select(keep).device_bitmasks(model.device)
+            has, targets_of = gt_dev.has_mask, bitmask_targets_device
+        else:
+            gt_dev = DevicePolygons([polys[i] for i in keep], model.device)
+            has, targets_of = gt_dev.parts, mask_targets_device
+        rows, skipped = select_mask_rows(labels_host, matched.cpu().numpy(), has, self.num_classes)
         rows_dev = torch.from_numpy(rows).to(model.device)
         mboxes = boxes[rows_dev].contiguous()
-        targets = mask_targets_device(poly_dev, mboxes, matched[rows_dev])
+        targets = targets_of(gt_dev, mboxes, matched[rows_dev])
         classes = torch.from_numpy(labels_host[rows].astype(np.int64))
         return (model.mask_roi_features(mboxes), classes, targets), skipped
 

@@ -745,6 +745,36 @@ int apse_mask_predictor_backward(const float* d_dev, const float* a5_dev, const 
 int apse_coco_mask_targets(const double* xy_dev, const int* part_vert_off_dev, int n_parts, const int* obj_part_off_dev, int n_obj,
                       int n_verts, const float* rois_dev, const int* matched_dev, int n, int mask_size, uint8_t* targets_dev,
                       int* info_dev, void* stream);
+/* ---- Bitmask targets (csrc/bitmask_targets.hip): the same targets from bitmask ground truth (RLE, dense masks, result windows),
+ * detectron2's INPUT.MASK_FORMAT = "bitmask".  DESIGN.md "Bitmask ground truth".  Windows are the layout of "MOTS evaluation".
+ * Stateless, one launch each on `stream`, no scratch, no allocation, no atomics: two calls give the same bytes.
+ *
+ * Nearest-neighbour resize and / or flip of bit windows.  src [n] (device) are windows in a frame of H x W; xmap [w] and ymap [h]
+ * (device int) give the source column of image column x and the source row of image row y.  dst [n] (device, with the same
+ * values in dst_host) are windows in the image of h x w whose rect and words_per_row the caller has set and whose bits
+ * (device) this writes: destination pixel (x, y) of dst[k]'s rect is set iff source pixel (xmap[x], ymap[y]) of src[k] is set.
+ * Every word of each destination window is written; bits outside the rect are 0.  A map entry that points outside the source
+ * window reads 0.  The caller derives each destination rect from the source rect and the maps (monotone maps cover one range
+ * of columns and of rows); an empty destination rect, or NULL bits, writes nothing.  APSE_E_INVALID, with no launch: a frame
+ * or image outside the frame limits, n outside 0 .. APSE_MOTS_MAX_OBJECTS, a NULL pointer, a non-empty dst_host rect that leaves
+ * the image or whose words_per_row is too small.  n == 0 is a no-op. */
+int apse_mots_remap_windows(const apse_mots_window* src, int n, int H, int W, const int* xmap, const int* ymap, int h, int w,
+                            const apse_mots_window* dst, const apse_mots_window* dst_host, void* stream);
+/* BitMasks.crop_and_resize(boxes, mask_size): row r of out u8 [n][mask_size][mask_size] is detectron2's ROIAlign((mask_size,
+ * mask_size), 1.0, 0, aligned=True) of the 0 / 1 mask of windows[matched[r]] (device [n_obj], image coordinates, image h x w)
+ * under rois[r] (device f32 x1,y1,x2,y2), 1 where the average is >= 0.5f.  ROIAlign_cpu.cpp in f32, every operation rounded on
+ * its own: start = x1 - 0.5f, roi = end - start (not clamped to 1), bin = roi / mask_size, grid = (int)ceilf(bin), count =
+ * max(gh * gw, 1); sample (iy, ix) of cell (ph, pw) at start + p * bin + (i + 0.5f) * bin / grid; outside (-1, size) a sample
+ * adds 0, at or below 0 it is 0; low = (int)v, at low >= size - 1 both cells are size - 1 and the fraction 0; weights hy*hx,
+ * hy*lx, ly*hx, ly*lx; w1*v1 + w2*v2 + w3*v3 + w4*v4 per sample, added into one accumulator with iy outer and ix inner, then
+ * divided by count.  A zero row: matched[r] outside 0 .. n_obj - 1, an empty window or NULL bits, a box with a non-positive or
+ * NaN extent (grid <= 0), and a box of more than 8192 * mask_size pixels along an axis (a limit of this entry).  Every byte
+ * of the n rows is written and nothing past them.  APSE_E_INVALID, with no launch: an image outside the frame limits, n_obj
+ * outside 0 .. APSE_MOTS_MAX_OBJECTS, n outside 0 .. APSE_MASK_TRAIN_MAX_N, mask_size outside 1 .. APSE_BITMASK_MAX_SIZE, a NULL
+ * pointer.  n == 0 is a no-op. */
+#define APSE_BITMASK_MAX_SIZE 64
+int apse_bitmask_targets(const apse_mots_window* windows, int n_obj, int h, int w, const float* rois, const int* matched, int n,
+                         int mask_size, uint8_t* out, void* stream);
 
 /* ---- Box-head training (csrc/box_train.hip): the f32 steps of fine-tuning roi_heads.box_head.fc1 / fc2 and
  * roi_heads.box_predictor.cls_score / bbox_pred of a frozen FPN detector (dcnn/scripts/train/finetune_uav.py): proposal labelling,

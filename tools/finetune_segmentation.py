@@ -10,6 +10,9 @@ proposals-given box head, so the boxes go straight to the mask branch (``detecte
   python tools/finetune_segmentation.py --images DIR --annotations FILE.json --weights detector.pth --classes car truck bus person --out DIR
   python tools/finetune_segmentation.py --synthetic 12 --iters 40 --out DIR          # dry run on generated data, seeded weights
   python tools/finetune_segmentation.py ... --resume                                 # continue from DIR/<name>_last.pth
+  python tools/finetune_segmentation.py ... --mask-format bitmask                    # RLE segmentations too (BitMasks targets)
+  python tools/finetune_segmentation.py --mots DATASET --seqmap FILE --weights detector.pth --out DIR     # KITTI MOTS ground truth
+  python tools/finetune_segmentation.py --synthetic 12 --mots --iters 20 --out DIR   # dry run on a generated MOTS dataset
 
 Checkpoint keys (the reference's): model, optimizer, scheduler, iteration, kfold_split, k_folds, best_precision, best_recall,
 training_results -- plus ``loader`` (the sampling state) so that a resumed run repeats the uninterrupted one bit for bit.
@@ -85,7 +88,7 @@ class MaskTask(ft.Task):
     def make_loader(self, args, dicts, model, K, sizes):
         from apse_uav_amd.utils.COCO_utils import MaskTrainLoader
         return MaskTrainLoader(dicts, model, args.ims_per_batch, args.seed, args.flip, args.cache_features, augment=args.augment,
-                               **sizes)
+                               mask_format=ft.mask_format(args), **sizes)
 
     def losses(self, batch, loader, args):
         return self.heads[0](*batch)

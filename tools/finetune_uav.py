@@ -17,6 +17,8 @@ the recall of the proposals at 100 and 1000) and a checkpoint with the merged fu
   python tools/finetune_uav.py --synthetic 6 --iters 12 --checkpoint-period 4 --out DIR     # dry run on generated data
   python tools/finetune_uav.py ... --resume                                                 # continue from DIR/<name>_last.pth
   python tools/finetune_uav.py ... --mask                                                   # the mask head too, in the same loop
+  python tools/finetune_uav.py ... --mask --mask-format bitmask                             # ... on RLE segmentations (BitMasks targets)
+  python tools/finetune_uav.py --mots DATASET --seqmap FILE --weights detector.pth --mask --out DIR     # KITTI MOTS ground truth
 
 ``--mask`` adds ``roi_heads.mask_head.*`` (12 tensors) as a third head under the same SGD and schedule, as detectron2's
 ``StandardROIHeads._forward_mask`` trains it: on the sampled FOREGROUND PROPOSALS of every image (at most 128 per image), each
@@ -119,7 +121,7 @@ class JointTask(ft.Task):
     def make_loader(self, args, dicts, model, K, sizes):
         from apse_uav_amd.utils.joint_train import JointTrainLoader
         return JointTrainLoader(dicts, model, args.ims_per_batch, args.seed, args.flip, augment=args.augment, num_classes=K,
-                                mask=self.mask, **sizes)
+                                mask=self.mask, mask_format=ft.mask_format(args), **sizes)
 
     def losses(self, batch, loader, args):
         from apse_uav_amd.utils.joint_train import box_losses_chunked
