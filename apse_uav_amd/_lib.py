@@ -20,7 +20,7 @@ LIB_PATH = os.environ.get("APSE_HIP_LIB") or _TREE_LIB
 # APSE_HIP_LIB (load())
 TOOL_ENTRIES = ("apse_conv2d_ex", "apse_winograd_pack_filter", "apse_winograd_conv2d", "apse_winograd_conv2d_split", "apse_conv_pointwise_launches", "apse_lane_stats", "apse_rpn_select", "apse_box_inference",
                 "apse_c4_rpn_select", "apse_rpn_select_train", "apse_rpn_train_proposals_workspace_bytes", "apse_rpn_train_proposals",
-                "apse_set_rpn_head", "apse_preprocess_frames_yuv", "apse_yuv_to_bgr", "apse_yuv_matrix_host", "apse_resize_normalize_yuv")
+                "apse_set_rpn_head", "apse_roi_features_windows", "apse_set_crop_features", "apse_preprocess_frames_yuv", "apse_yuv_to_bgr", "apse_yuv_matrix_host", "apse_resize_normalize_yuv")
 
 APSE_OK = 0
 
@@ -129,6 +129,8 @@ SIGNATURES = {
     "apse_roi_align_typed": ([C.POINTER(vp), C.POINTER(i), C.POINTER(i), vp, i, i, i, i, vp, vp], i),
     "apse_roi_pool": ([vp, i, i, vp, vp, i, i, f, vp, vp], i),
     "apse_roi_features": ([vp, i, vp, vp, i, i, vp, vp], i),
+    "apse_roi_features_windows": ([vp, i, vp, vp, i, i, vp, vp], i),
+    "apse_set_crop_features": ([vp, i], i),
     "apse_nms_rank": ([vp, vp, vp, i, i, i, i, f, i, vp, vp, vp, vp, vp], i),
     "apse_rpn_select": ([C.POINTER(vp), C.POINTER(i), C.POINTER(i), i, i, i, i, i, i, f, i, vp, vp, vp, vp, vp, vp, vp, vp, vp], i),
     "apse_box_inference": ([vp, i, i, vp, vp, i, i, i, i, f, f, i, i] + [vp] * 16, i),

@@ -141,8 +141,10 @@ def get_cfg():
         # (apse_config.tail_lane; the environment variable APSE_TAIL_LANE=0 switches it off for every context)
         # YUV_MATRIX: the conversion of INPUT.FORMAT "NV12" / "I420" frames (structures/yuv_frame.py): cv601 (OpenCV's
         # COLOR_YUV2BGR_NV12 constants), bt601, bt709, bt601-full, bt709-full
+        # CROP_FEATURES: the association head's RoI features are cut from p2 * the instance mask with roi_align (the reference's
+        # crop_features=True branch, rcnn_tracker.py:166-180) instead of roi_pool at the box (apse_set_crop_features; FPN only)
         "APSE": {"DTYPE": "f32", "MAX_BATCH": 1, "FUSED_PREPROC": True, "STORAGE16": True, "CONTEXT_CACHE": 1, "TAIL_LANE": True,
-                 "YUV_MATRIX": "cv601"},
+                 "YUV_MATRIX": "cv601", "CROP_FEATURES": False},
     })
 
 

@@ -160,6 +160,13 @@ int apse_k_mean_cells(const float* x, int n, int cells, int C, float* y, hipStre
 int apse_k_mask_resize(const uint8_t* masks, int n, int H, int W, int OH, int OW, float* out, hipStream_t s);
 int apse_k_roi_align_masked(const void* feat, int st, int H, int W, int img0, const float* rois, const float* mask, int n, int R,
                             int SR, float scale, float* out, hipStream_t s);
+// roi_align(aligned=False, sampling_ratio=SR) of feat * m_r, m_r the bilinear resize (frame_h x frame_w -> H x W) of row r's bit
+// mask: windows[r], or (windows == nullptr) plane r of `planes` inside rects[r], empty when valid[r] == 0.  Bit for bit
+// apse_k_mask_resize + apse_k_roi_align_masked.  R <= 32, SR in {1, 2, 4}; nchw: out [row][256][R][R], else [row][R][R][256].
+struct apse_mots_window;
+int apse_k_roi_align_windows(const void* feat, int st, int H, int W, const float* rois, const int* roi_img, int img0, const int* total,
+                             int n_max, const apse_mots_window* windows, const uint64_t* planes, const int* rects, const int* valid,
+                             int plane_wpr, int frame_h, int frame_w, int R, int SR, float scale, float* out, int nchw, hipStream_t s);
 int apse_k_l2_normalize(const float* x, float* y, int D, const int* total, int n_max, hipStream_t s);
 bool apse_assoc_fc_ok(int K, int N);
 int apse_k_assoc_fc(const float* x, const float* w, const float* bias, float* ws, const int* total, int n_max, int K, int N, float* raw,

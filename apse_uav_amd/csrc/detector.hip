@@ -482,6 +482,7 @@ static int pack_from_dets(apse_ctx* c, int batch, hipStream_t s) {
     const apse_config& g = c->cfg;
     uint8_t* r = c->res;
     c->sums_dirty = false;                 // pack_detections clears the integer sums of the mask tail
+    c->masks_fresh = false;                // a new detection list: the bit planes still hold the previous list's masks
     return apse_k_pack_detections(c->det_boxes, c->det_scores, c->det_entry, c->det_cnt, batch, g.dets_per_image, g.num_classes,
                                   (float*)(r + c->lay.box_resized), (float*)(r + c->lay.score), (int*)(r + c->lay.cls),
                                   (int*)(r + c->lay.img), (int*)(r + c->lay.roi), (int*)(r + c->lay.total),
@@ -635,6 +636,7 @@ int apse_mask_tail(apse_ctx* c, int batch, void* stream) {
     unsigned long long* keys = (unsigned long long*)(r + c->lay.closest);      // raw (distance, index) keys; decoded on the host
     rc = apse_k_mask_paste(&p, NM, keys, g.dets_per_image, s);
     if (rc) return fail(c, rc, "mask paste launch failed");
+    c->masks_fresh = true;                 // set bits_cur now holds this detection list's masks (apse_embed with crop features)
     rc = apse_k_closest_points(bits, p.rect, p.valid, c->sums, (int*)(r + c->lay.img), (int*)(r + c->lay.offset), total, NM,
                                g.dets_per_image, g.frame_h, g.frame_w, c->wpr, (int*)(r + c->lay.centroid), (int*)(r + c->lay.mass),
                                keys, c->hint_total, s);
@@ -655,12 +657,21 @@ int apse_embed(apse_ctx* c, int batch, void* stream) {
         const Tens& f = c->t["res4"];
         rc = apse_k_roi_pool_c4(f.p, f.H, f.W, f.C, (float*)(r + c->lay.box), (int*)(r + c->lay.img), total, NM, g.assoc_roi,
                                 g.assoc_scale, (float*)c->t["assoc_pooled"].p, s);
+    } else if (c->crop_features) {
+        // rcnn_tracker.py:166-180: p2 * the detection's own mask (bilinear to p2's padded size), then roi_align(sampling_ratio 4).
+        // The masks are the bit planes and rects the mask tail of THIS forward wrote (set bits_cur, same stream: ordered).
+        if (!c->masks_fresh)
+            return fail(c, APSE_E_STATE, "apse_embed with crop features needs the masks of these detections: call apse_mask_tail first");
+        const Tens& p2 = c->t["p2"];
+        rc = apse_k_roi_align_windows(p2.p, p2.st, p2.H, p2.W, (float*)(r + c->lay.box), (int*)(r + c->lay.img), 0, total, NM, nullptr,
+                                      c->bits2[c->bits_cur], (int*)(r + c->lay.rect), (int*)(r + c->lay.valid), c->wpr, g.frame_h,
+                                      g.frame_w, g.assoc_roi, 4, g.assoc_scale, (float*)c->t["assoc_pooled"].p, 0, s);
     } else {
         const Tens& p2 = c->t["p2"];
         rc = apse_k_roi_pool(p2.p, p2.st, p2.H, p2.W, (float*)(r + c->lay.box), (int*)(r + c->lay.img), total, NM, g.assoc_roi,
                              g.assoc_scale, (float*)c->t["assoc_pooled"].p, 0, 0, s);
     }
-    if (rc) return fail(c, rc, "roi_pool launch failed");
+    if (rc) return fail(c, rc, c->crop_features && !c->c4 ? "masked roi_align launch failed" : "roi_pool launch failed");
     if (c->ws_assoc) {
         // K-sliced FC + ordered reduction + normalise (roi.hip): the filters of the plan's convolution step, its own two kernels
         const ConvParams& fp = c->embedfc[0].c.p;
@@ -891,6 +902,31 @@ int apse_roi_features(apse_ctx* c, int image, const float* rois, const uint8_t* 
     if (rc) return fail(c, rc, "mask resize launch failed");
     rc = apse_k_roi_align_masked(p2.p, p2.st, p2.H, p2.W, image, rois, c->rf_mask, n, roi_size, 4, scale, out, s);
     return rc ? fail(c, rc, "masked roi_align launch failed") : APSE_OK;
+}
+
+int apse_set_crop_features(apse_ctx* c, int on) {
+    if (!c) return fail(nullptr, APSE_E_INVALID, "null context");
+    if (on && c->c4) return fail(c, APSE_E_INVALID, "crop features read p2 (256 channels): not available under C4 (arch 1)");
+    c->crop_features = on != 0;
+    return APSE_OK;
+}
+
+int apse_roi_features_windows(apse_ctx* c, int image, const float* rois, const apse_mots_window* windows, int n, int roi_size,
+                              float* out, void* stream) {
+    if (!c || !c->finalized) return fail(c, APSE_E_STATE, "not finalized");
+    const apse_config& g = c->cfg;
+    if (image < 0 || image >= g.max_batch || n < 0 || roi_size < 1 || roi_size > 32 || (n > 0 && (!rois || !out || !windows)))
+        return fail(c, APSE_E_INVALID, "bad roi_features_windows arguments");
+    if (c->c4) return fail(c, APSE_E_INVALID, "apse_roi_features_windows reads p2: not available under C4 (arch 1)");
+    if (n == 0) return APSE_OK;
+    hipStream_t s = (hipStream_t)stream;
+    const Tens& p2 = c->t["p2"];
+    const float scale = (float)p2.W / (float)g.frame_w;      // as apse_roi_features
+    int rc = lane_join(c, s);          // reads p2 only (written on the caller's stream): nothing for the lane to follow
+    if (rc) return rc;
+    rc = apse_k_roi_align_windows(p2.p, p2.st, p2.H, p2.W, rois, nullptr, image, nullptr, n, windows, nullptr, nullptr, nullptr, 0,
+                                  g.frame_h, g.frame_w, roi_size, 4, scale, out, 1, s);
+    return rc ? fail(c, rc, "masked roi_align (windows) launch failed") : APSE_OK;
 }
 
 // ROIAlign R x R of n caller-given boxes over p2..p5 of one image: apse_mask_roi_features (R = 14) and apse_box_roi_features (R = 7)

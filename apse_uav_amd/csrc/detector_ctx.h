@@ -66,6 +66,8 @@ struct apse_ctx {
     // mask tail
     uint64_t* bits2[2] = {nullptr, nullptr}; int bits_cur = 0, bits_read = 0;   // mask bit planes, alternating per forward (see apse_mask_tail)
     unsigned long long* sums = nullptr; int wpr = 0; bool sums_dirty = false;
+    bool crop_features = false;     // apse_set_crop_features: apse_embed cuts the RoI features from p2 * mask (roi_align_windows)
+    bool masks_fresh = false;       // apse_mask_tail has run on the current detection list (set bits_cur holds its masks)
     float* emb_raw = nullptr;
     float* ws_assoc = nullptr;      // [K / 128][max detections][embed_dim]: K slices of the association FC (apse_k_assoc_fc), or nullptr
     float* rf_mask = nullptr; size_t rf_mask_floats = 0;      // apse_roi_features: masks at p2 resolution (grown on demand)

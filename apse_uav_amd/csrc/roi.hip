@@ -2,10 +2,13 @@
 //  * roi_align_nhwc : detectron2 ROIPooler + ROIAlign(aligned=True, sampling_ratio=0) over p2..p5
 //                     (box head 7x7, mask head 14x14; reached from dcnn/networks/track_rcnn.py:51)
 //  * roi_pool_nhwc  : torchvision.ops.roi_pool on p2 (dcnn/engines/rcnn_tracker.py:182)
+//  * roi_align_masked / roi_align_windows : torchvision.ops.roi_align(aligned=False) of p2 * the instance mask, the mask dense at
+//                     map resolution or read from bit windows at frame resolution (rcnn_tracker.py:166-180, crop_features)
 //  * l2_normalize, sqdist_matrix : AssociationHead's F.normalize (dcnn/networks/association_head.py:25)
 //                     and RcnnTracker.calculate_distance_matrix (dcnn/engines/rcnn_tracker.py:192-221)
 // Output layout is [roi][ph][pw][C]; the consuming FC weights are permuted (c,h,w)->(h,w,c) at load.
 #include "apse_kernels.h"
+#include "mots_window.h"
 #include <float.h>
 
 // FpnMaps: apse_kernels.h
@@ -511,6 +514,120 @@ __global__ __launch_bounds__(256) void roi_align_masked(const void* __restrict__
     }
 }
 
+// ---- roi_align of feat * mask, the mask read from bit windows ------------------------------------------------------------------
+// The pair mask_resize_bilinear -> roi_align_masked in one kernel, without the dense mask and without the [n][H][W] f32 scratch:
+// row r's 0 / 1 mask lives at FRAME resolution (FH x FW) as an apse_mots_window (a bit counts only inside the rect; NULL bits or
+// an empty rect: the empty mask; the row stride may exceed what the rect needs), and the value m_r of a feature cell is
+// F.interpolate(bilinear, align_corners=False) evaluated from four bits with mask_resize_bilinear's own expression.  The
+// arithmetic is that of the two kernels operation for operation (the library is built with -ffp-contract=off), so the output
+// is bit for bit theirs.
+//   One wave per bin, the lane holding 4 of the 256 channels.  A bin's SR x SR samples touch 2 SR tap rows and 2 SR tap columns:
+// lane (2 iy + a) * 2 SR + (2 ix + b) evaluates the mask value of tap (a, b) of sample (iy, ix) once -- four bit reads per lane --
+// and the sample loop fetches it with v_readlane (the lane numbers are compile-time constants), instead of 16 bit reads per
+// sample in every lane.  A sample whose four mask values are all zero adds w * (feat * 0) = +-0 to the sum: its feature loads
+// are skipped (equal as values for finite features).
+//   windows != nullptr: one descriptor per row.  Else the mask tail's planes: row r is plane r of `planes` ([row][FH][plane_wpr]
+// words) restricted to rects[r], empty when valid[r] == 0 -- the descriptor (plane + y0 * wpr + (x0 >> 6), stride wpr) is formed
+// here.  roi_img == nullptr: every row reads image img0; total == nullptr: all n_max rows are live.  nchw: out [row][256][R][R]
+// (RoiFeaturesGenerator), else [row][R][R][256] (assoc_pooled, as roi_pool_nhwc writes it).
+__device__ __forceinline__ float crop_bit(const apse_mots_window& w, int y, int x) {
+    return ((window_word(w, y, x >> 6) >> (x & 63)) & 1ull) ? 1.f : 0.f;
+}
+// mask_resize_bilinear's value of output cell (oy, ox): sh = (float)FH / (float)OH, sw = (float)FW / (float)OW
+__device__ __forceinline__ float crop_cell(const apse_mots_window& w, int FH, int FW, float sh, float sw, int oy, int ox) {
+    float fy = sh * ((float)oy + 0.5f) - 0.5f;
+    float fx = sw * ((float)ox + 0.5f) - 0.5f;
+    fy = fy < 0.f ? 0.f : fy;
+    fx = fx < 0.f ? 0.f : fx;
+    const int y0 = (int)fy, x0 = (int)fx;
+    const int y1 = y0 + (y0 < FH - 1 ? 1 : 0), x1 = x0 + (x0 < FW - 1 ? 1 : 0);
+    const float ly = fy - (float)y0, lx = fx - (float)x0;
+    const float v00 = crop_bit(w, y0, x0), v01 = crop_bit(w, y0, x1);
+    const float v10 = crop_bit(w, y1, x0), v11 = crop_bit(w, y1, x1);
+    return (1.f - ly) * ((1.f - lx) * v00 + lx * v01) + ly * ((1.f - lx) * v10 + lx * v11);
+}
+__device__ __forceinline__ float crop_lane(float v, int l) {
+    return __int_as_float(__builtin_amdgcn_readlane(__float_as_int(v), l));
+}
+
+template <int SR>
+__global__ __launch_bounds__(256) void roi_align_windows(const void* __restrict__ feat, int st, int H, int W,
+                                                         const float* __restrict__ rois, const int* __restrict__ roi_img, int img0,
+                                                         const int* __restrict__ total, int n_max,
+                                                         const apse_mots_window* __restrict__ windows,
+                                                         const uint64_t* __restrict__ planes, const int* __restrict__ rects,
+                                                         const int* __restrict__ valid, int plane_wpr, int FH, int FW, int R,
+                                                         float scale, float* __restrict__ out, int nchw) {
+    constexpr int G = 2 * SR;                       // tap rows (and columns) of a bin; G * G <= 64 lanes
+    static_assert(G * G <= 64, "one tap cell per lane");
+    const int lane = threadIdx.x & 63;
+    const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    const int rr = R * R;
+    const int nl = total ? (*total < n_max ? *total : n_max) : n_max;
+    const float msh = (float)FH / (float)H, msw = (float)FW / (float)W;
+    const int ty = lane / G, tx = lane - ty * G;    // this lane's tap: row 2 iy + a, column 2 ix + b
+    for (int bin = blockIdx.x * 4 + wave; bin < nl * rr; bin += gridDim.x * 4) {
+        const int r = bin / rr;
+        const int pb = bin - r * rr;
+        const int ph = pb / R, pw = pb - ph * R;
+        const size_t f = (size_t)(roi_img ? roi_img[r] : img0) * H * W * 256 + lane * 4;
+        apse_mots_window wd;
+        if (windows) {
+            wd = windows[r];
+        } else {
+            wd.rect[0] = rects[r * 4 + 0]; wd.rect[1] = rects[r * 4 + 1]; wd.rect[2] = rects[r * 4 + 2]; wd.rect[3] = rects[r * 4 + 3];
+            wd.words_per_row = plane_wpr; wd.area = 0;
+            wd.bits = valid[r] ? const_cast<uint64_t*>(planes) + ((size_t)r * FH + wd.rect[1]) * plane_wpr + (wd.rect[0] >> 6) : nullptr;
+        }
+        const float x1 = rois[r * 4 + 0] * scale, y1 = rois[r * 4 + 1] * scale;
+        const float x2 = rois[r * 4 + 2] * scale, y2 = rois[r * 4 + 3] * scale;
+        const float rw = fmaxf(x2 - x1, 1.f), rh = fmaxf(y2 - y1, 1.f);
+        const float bw = rw / (float)R, bh = rh / (float)R;
+        float mv = 0.f;                             // mask value of this lane's tap cell (0 where the sample is skipped)
+        if (lane < G * G) {
+            const float yy = y1 + (float)ph * bh + ((float)(ty >> 1) + 0.5f) * bh / (float)SR;
+            const float xx = x1 + (float)pw * bw + ((float)(tx >> 1) + 0.5f) * bw / (float)SR;
+            if (!(yy < -1.f || yy > (float)H || xx < -1.f || xx > (float)W)) {
+                const float y = yy <= 0.f ? 0.f : yy, x = xx <= 0.f ? 0.f : xx;
+                int yl = (int)y, xl = (int)x, yh, xh;
+                if (yl >= H - 1) { yh = yl = H - 1; } else yh = yl + 1;
+                if (xl >= W - 1) { xh = xl = W - 1; } else xh = xl + 1;
+                mv = crop_cell(wd, FH, FW, msh, msw, (ty & 1) ? yh : yl, (tx & 1) ? xh : xl);
+            }
+        }
+        f32x4 acc = {0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+        for (int iy = 0; iy < SR; ++iy) {
+            const float yy = y1 + (float)ph * bh + ((float)iy + 0.5f) * bh / (float)SR;
+#pragma unroll
+            for (int ix = 0; ix < SR; ++ix) {
+                const float xx = x1 + (float)pw * bw + ((float)ix + 0.5f) * bw / (float)SR;
+                if (yy < -1.f || yy > (float)H || xx < -1.f || xx > (float)W) continue;
+                const float m1 = crop_lane(mv, (2 * iy) * G + 2 * ix), m2 = crop_lane(mv, (2 * iy) * G + 2 * ix + 1);
+                const float m3 = crop_lane(mv, (2 * iy + 1) * G + 2 * ix), m4 = crop_lane(mv, (2 * iy + 1) * G + 2 * ix + 1);
+                if (m1 == 0.f && m2 == 0.f && m3 == 0.f && m4 == 0.f) continue;
+                float y = yy <= 0.f ? 0.f : yy, x = xx <= 0.f ? 0.f : xx;
+                int yl = (int)y, xl = (int)x, yh, xh;
+                if (yl >= H - 1) { yh = yl = H - 1; y = (float)yl; } else yh = yl + 1;
+                if (xl >= W - 1) { xh = xl = W - 1; x = (float)xl; } else xh = xl + 1;
+                const float ly = y - (float)yl, lx = x - (float)xl, hy = 1.f - ly, hx = 1.f - lx;
+                const float w1 = hy * hx, w2 = hy * lx, w3 = ly * hx, w4 = ly * lx;
+                const f32x4 v1 = apse_ld4(feat, f + ((size_t)yl * W + xl) * 256, st) * m1;
+                const f32x4 v2 = apse_ld4(feat, f + ((size_t)yl * W + xh) * 256, st) * m2;
+                const f32x4 v3 = apse_ld4(feat, f + ((size_t)yh * W + xl) * 256, st) * m3;
+                const f32x4 v4 = apse_ld4(feat, f + ((size_t)yh * W + xh) * 256, st) * m4;
+                acc += w1 * v1 + w2 * v2 + w3 * v3 + w4 * v4;
+            }
+        }
+        acc = acc / (float)(SR * SR);
+        if (nchw) {
+            for (int k = 0; k < 4; ++k) out[((size_t)r * 256 + lane * 4 + k) * rr + pb] = acc[k];
+        } else {
+            *reinterpret_cast<f32x4*>(out + ((size_t)r * rr + pb) * 256 + lane * 4) = acc;
+        }
+    }
+}
+
 // F.normalize(x, p=2, dim=1, eps=1e-12) on [n][D] rows, one wave per row (D <= 256, D % 64 == 0 not required).
 __global__ __launch_bounds__(64) void l2_normalize_rows(const float* __restrict__ x, float* __restrict__ y, int D,
                                                         const int* __restrict__ total, int n_max) {
@@ -689,6 +806,24 @@ int apse_k_roi_align_masked(const void* feat, int st, int H, int W, int img0, co
     int blocks = (n * R * R + 3) / 4;
     if (blocks > 4096) blocks = 4096;
     hipLaunchKernelGGL(roi_align_masked, dim3(blocks), dim3(256), 0, s, feat, st, H, W, img0, rois, mask, n, R, SR, scale, out);
+    return hipGetLastError() == hipSuccess ? APSE_OK : APSE_E_HIP;
+}
+int apse_k_roi_align_windows(const void* feat, int st, int H, int W, const float* rois, const int* roi_img, int img0, const int* total,
+                             int n_max, const apse_mots_window* windows, const uint64_t* planes, const int* rects, const int* valid,
+                             int plane_wpr, int frame_h, int frame_w, int R, int SR, float scale, float* out, int nchw, hipStream_t s) {
+    if (R < 1 || R > 32 || (SR != 1 && SR != 2 && SR != 4) || H < 1 || W < 1 || frame_h < 1 || frame_w < 1 || st < 0 || st > 2 ||
+        (!windows && (!planes || !rects || !valid || plane_wpr < ((frame_w + 63) >> 6))))
+        return APSE_E_INVALID;
+    if (n_max <= 0) return APSE_OK;
+    int blocks = (n_max * R * R + 3) / 4;
+    if (blocks > 4096) blocks = 4096;
+#define APSE_CROP_LAUNCH(SRV)                                                                                                        \
+    hipLaunchKernelGGL(roi_align_windows<SRV>, dim3(blocks), dim3(256), 0, s, feat, st, H, W, rois, roi_img, img0, total, n_max, windows, \
+                       planes, rects, valid, plane_wpr, frame_h, frame_w, R, scale, out, nchw)
+    if (SR == 1) APSE_CROP_LAUNCH(1);
+    else if (SR == 2) APSE_CROP_LAUNCH(2);
+    else APSE_CROP_LAUNCH(4);
+#undef APSE_CROP_LAUNCH
     return hipGetLastError() == hipSuccess ? APSE_OK : APSE_E_HIP;
 }
 int apse_k_l2_normalize(const float* x, float* y, int D, const int* total, int n_max, hipStream_t s) {

@@ -13,6 +13,9 @@ within a squared pixel distance).  Neither needs an association head: ``weights=
 
 GPU work (detector, roi_pool, association FC + normalise, distance matrix, mask centroid /
 closest points) runs in ``libapse_hip.so``; the sequential id bookkeeping stays on the host.
+``crop_features=True`` (or ``cfg.APSE.CROP_FEATURES``) switches the RoI features of the 'embeddings' metric to the reference's
+mask-cropped branch (:166-180): ``roi_align(sampling_ratio=4)`` of p2 * the detection's mask, resized bilinearly to p2 -- in the
+fused stage (``apse_set_crop_features``) and in ``get_features_rois``; FPN models only.
 ``next_record`` drives the same association from a per-frame record, which is what rank 0
 does with the records gathered from the other GPUs in frame-sharded mode.
 """
@@ -21,6 +24,7 @@ import torch
 from scipy.optimize import linear_sum_assignment
 
 from .. import _lib
+from ..config import is_c4
 from ..networks.association_head import AssociationHead
 from ..structures.instances import Boxes, Instances
 from ..structures.object_instances import ObjectInstances
@@ -44,7 +48,7 @@ def require_embeddings_metric(metric, who):
 class RcnnTracker:
 
     def __init__(self, config, image_size, weights, association_metric='embeddings', DISPLAY_INFO=[], metadata=None,
-                 detector_state=None, bbox_center_dist_threshold=None):
+                 detector_state=None, bbox_center_dist_threshold=None, crop_features=False):
         if association_metric not in ASSOCIATION_METRICS:
             raise ValueError("association_metric %r: expected one of %s" % (association_metric, ", ".join(ASSOCIATION_METRICS)))
         if weights is None and association_metric == 'embeddings':
@@ -57,7 +61,14 @@ class RcnnTracker:
         self.BBOX_CENTER_DIST_THRESHOLD = bbox_center_dist_threshold
         self.ASSOCIATION_EMBEDDING_THRESHOLD = 0.6
         self.OBJECT_UNDETECTED_FRAMES_TH = 100
-        self.crop_features = False
+        self.crop_features = bool(crop_features) or bool(config.APSE.get("CROP_FEATURES", False))
+        if self.crop_features:
+            if is_c4(config):
+                raise NotImplementedError("crop_features cuts the RoI features from the FPN level p2 (256 channels): not available "
+                                          "for C4 (Res5ROIHeads) models")
+            # every detector context of this tracker (and of a PipelinedRcnnTracker's slots, built from predictor.cfg) gets the switch
+            config = config.clone()
+            config.APSE.CROP_FEATURES = True
         self.config = config
         self.image_size = image_size
         self.device = torch.device(config.MODEL.DEVICE)
@@ -216,9 +227,12 @@ class RcnnTracker:
         self.frame_count = 0
 
     def get_features_rois(self, detections, backbone_features, crop_features=False):
-        """roi_pool of p2 at the detections' boxes (rcnn_tracker.py:156-189, crop_features=False branch)."""
+        """roi_pool of p2 at the detections' boxes (rcnn_tracker.py:156-189, crop_features=False branch), or with
+        ``crop_features=True`` the branch :166-180: p2 * the detection's mask (``pred_masks``: WindowMasks, resized bilinearly to
+        p2 inside the kernel) through roi_align(sampling_ratio=4) -- ``apse_roi_features_windows`` on the p2 the detector context
+        holds for image 0 of its last forward, which is the map ``backbone_features`` exports."""
         if crop_features:
-            raise NotImplementedError("crop_features=True is dead at inference in the reference (rcnn_tracker.py:48)")
+            return self._cropped_features_rois(detections)
         features = backbone_features[self.config.MODEL.ROI_HEADS.IN_FEATURES[0]]
         spatial_scale = features.size()[3] / self.image_size[1]
         n = len(detections)
@@ -230,6 +244,30 @@ class RcnnTracker:
                                              ASSOCIATION_ROI_SIZE, float(spatial_scale), _lib.ptr(out), _lib.stream_ptr()),
                    None, "apse_roi_pool")
         return out.permute(0, 3, 1, 2)
+
+    def _cropped_features_rois(self, detections):
+        if is_c4(self.config):
+            raise NotImplementedError("crop_features cuts the RoI features from the FPN level p2 (256 channels): not available "
+                                      "for C4 (Res5ROIHeads) models")
+        from ..structures import device_windows as dw
+        model = self.predictor.model
+        if model._ctx is None:
+            raise _lib.ApseError("get_features_rois(crop_features=True) reads p2 of the detector's last forward: run a frame first")
+        masks = list(detections.pred_masks)
+        if not all(isinstance(m, WindowMask) for m in masks):
+            raise TypeError("get_features_rois(crop_features=True) takes Instances whose pred_masks are WindowMasks")
+        n = len(detections)
+        out = torch.empty((n, self.backbone_features_depth, ASSOCIATION_ROI_SIZE, ASSOCIATION_ROI_SIZE), device=self.device)
+        if n == 0:
+            return out
+        boxes = detections.pred_boxes.tensor.to(self.device, torch.float32).contiguous()
+        rects, wprs, ptrs, words, _ = dw.masks_words(masks, self.image_size, self.device)
+        windows = dw.upload(dw.fill_windows(rects, wprs, ptrs), self.device)
+        model._call("apse_roi_features_windows", 0, _lib.ptr(boxes), _lib.ptr(windows), n, ASSOCIATION_ROI_SIZE, _lib.ptr(out),
+                    _lib.stream_ptr())
+        torch.cuda.current_stream().synchronize()          # `words` (bits moved to the device) stay alive until the kernel is done
+        del words
+        return out
 
     def calculate_distance_matrix(self, detection_embeddings):
         """O x N squared L2 distances (rcnn_tracker.py:192-221).  Device embeddings -> HIP kernel; host

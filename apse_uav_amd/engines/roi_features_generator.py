@@ -11,7 +11,10 @@ backbone (stem + res2..res5 + FPN) on one frame, then on ``p2`` (``in_features[0
 
 The frame goes through the same HIP path as the tracker (PIL-exact resize + normalise + pad, implicit-GEMM
 backbone); the RoI stage is ``apse_roi_features`` (include/apse_hip.h).  ``objects_masks`` may be COCO RLE dicts
-(what the reference passes, decoded here by utils/rle.py instead of pycocotools), or bool/u8 arrays [H, W].
+(what the reference passes), ``WindowMask``s, or bool/u8 arrays [H, W].  RLE dicts and WindowMasks become bit windows on the
+device (``COCO_utils.DeviceBitmasks``: ``apse_mots_rle_to_bits``) and go through ``apse_roi_features_windows``, which resizes
+each mask from its bits inside the roi_align kernel; a list with a dense array in it takes the dense route (every mask decoded
+on the host, uploaded as [n][H][W] u8, resized into a scratch, then roi_align).  The features are bit-identical either way.
 Only backbone weights are needed: a checkpoint's non-backbone tensors may be absent (PartialCheckpointer,
 dcnn/utils/partial_checkpointer.py:8-24, keeps the ``backbone.`` part only).
 """
@@ -21,6 +24,7 @@ import torch
 from .. import _lib
 from ..config import is_c4
 from ..networks.track_rcnn import TrackRCNN
+from ..structures.window_mask import WindowMask
 from ..structures.yuv_frame import YuvBatch, YuvFrame
 from ..utils import rle
 from ..weights import load_detector_file, synthetic_detector_state, blocks_from_state
@@ -78,6 +82,8 @@ class RoiFeaturesGenerator:
         for k, m in enumerate(objects_masks):
             if isinstance(m, dict):
                 m = rle.decode(m)
+            elif isinstance(m, WindowMask):
+                m = m.dense()
             m = np.asarray(m.cpu() if hasattr(m, "cpu") else m)
             assert m.shape == (height, width), "mask %d has shape %s, frame is %s" % (k, m.shape, (height, width))
             out[k] = m != 0
@@ -113,6 +119,13 @@ class RoiFeaturesGenerator:
         masks_d = None
         if objects_masks is not None:
             assert len(objects_masks) == n, "one mask per object"
+            if all(isinstance(k, (dict, WindowMask)) for k in objects_masks):
+                from ..utils.COCO_utils import DeviceBitmasks
+                bitmasks = DeviceBitmasks(list(objects_masks), (height, width), self.device)     # holds the words until the sync below
+                m._call("apse_roi_features_windows", 0, _lib.ptr(boxes_d), _lib.ptr(bitmasks.windows), n, self.roi_size,
+                        _lib.ptr(rois), s)
+                torch.cuda.synchronize()
+                return ids, rois
             masks_d = torch.from_numpy(self._masks_dense(objects_masks, height, width)).to(self.device)
         m._call("apse_roi_features", 0, _lib.ptr(boxes_d), _lib.ptr(masks_d) if masks_d is not None else None, n, self.roi_size,
                 _lib.ptr(rois), s)

@@ -131,6 +131,7 @@ class TrackRCNN:
         self._host = None
         self._camera = None                   # FramePreprocessor: undistort + gamma fused into preprocess_frames
         self.tail_lane = None                 # None: cfg.APSE.TAIL_LANE; False: contexts without the tail lane (apse_config.tail_lane)
+        self.crop_features = bool(cfg.APSE.get("CROP_FEATURES", False))      # apse_set_crop_features of every context
         self._input_tag = None                # frames (objects) the network input was pre-staged with, or None
         self._running_tag = None              # (frames, rpn_levels) whose forward is already enqueued and not yet read, or None
         self.last_results = None
@@ -174,6 +175,16 @@ class TrackRCNN:
         _lib.check(lib.apse_set_camera(ctx, pc.mtx.ctypes.data_as(C.POINTER(C.c_double)), pc.dist.ctypes.data_as(C.POINTER(C.c_double)),
                                        int(pc.dist.size), _lib.ptr(pc.lut_host), int(pc.undistort), int(pc.gamma_correct)),
                    ctx, "apse_set_camera")
+
+    def set_crop_features(self, on):
+        """The association features of every context, live, cached or built later: ``roi_pool`` of p2 at the box (False, the
+        default ``cfg.APSE.CROP_FEATURES``) or ``roi_align`` of p2 * the detection's mask (apse_set_crop_features; FPN only)."""
+        on = bool(on)
+        if on and self.c4:
+            raise NotImplementedError("crop features read the FPN level p2: not available for C4 (Res5ROIHeads) models")
+        self.crop_features = on
+        for entry in self._cache.values():
+            _lib.check(_lib.load().apse_set_crop_features(entry[0], int(on)), entry[0], "apse_set_crop_features")
 
     def _drop_ctx(self):
         """Destroys every live context (the current one and the cached ones)."""
@@ -288,6 +299,8 @@ class TrackRCNN:
                        "apse_set_resize_tables")
             lay = _lib.ResultsLayout()
             _lib.check(lib.apse_results_describe(ctx, C.byref(lay)), ctx, "apse_results_describe")
+            if self.crop_features:
+                _lib.check(lib.apse_set_crop_features(ctx, 1), ctx, "apse_set_crop_features")
         except Exception:
             lib.apse_destroy(ctx)
             raise

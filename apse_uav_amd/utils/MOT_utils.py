@@ -2,7 +2,8 @@
 
 Same constructors, attributes and ``get_training_batch`` as the reference; ground truth is read by the plain host functions
 below (no GPU), frames with PIL as BGR (what cv2.imread returns), masks with utils/rle.py and boxes with ``rle_to_bbox``,
-a restatement of pycocotools' rleToBbox.  RoI features come from RoiFeaturesGenerator (the HIP backbone + roi_pool).
+a restatement of pycocotools' rleToBbox.  RoI features come from RoiFeaturesGenerator (the HIP backbone + roi_pool, or with
+``MOTSloader(crop_features=True)`` the mask-cropped roi_align of the frame's RLE masks, turned into bit windows on the device).
 
     MOTS layout: <dataset>/instances_txt/<seq>.txt, <dataset>/training/image_02/<seq>/%06d.png, a seqmap file
     MOT layout:  <sequence>/seqinfo.ini, <sequence>/gt/gt.txt (rows with conf == 1), <sequence>/img1/%06d.jpg
@@ -18,6 +19,7 @@ import numpy as np
 import torch
 from PIL import Image
 
+from ..config import is_c4
 from ..engines.roi_features_generator import RoiFeaturesGenerator
 from . import rle
 from .mots_evaluation import parse_mots_seqmap
@@ -227,7 +229,11 @@ class MOTloader:
 class MOTSloader:
     """Training data of the association head from KITTI MOTS-layout sequences (MOT_utils.py:134-245)."""
 
-    def __init__(self, config, dataset_path, seqmap_path, frames_in_batch=8, roi_size=8, cache_features=False):
+    def __init__(self, config, dataset_path, seqmap_path, frames_in_batch=8, roi_size=8, cache_features=False, crop_features=False):
+        if crop_features and is_c4(config):
+            raise NotImplementedError("crop_features cuts the RoI features from the FPN level p2: not available for C4 "
+                                      "(Res5ROIHeads) models")
+        self.crop_features = bool(crop_features)
         self.config = config
         self.frames_in_batch = frames_in_batch
         self.dataset_path = dataset_path
@@ -261,8 +267,8 @@ class MOTSloader:
 
     def rois_ids_from_frame(self, sequence_name, frame_number):
         frame = self.frame_from_sequence(sequence_name, frame_number)
-        frame_objects, _ = self.objects_masks_from_frame(sequence_name, frame_number)
-        return self.roi_generator.get_rois_features(frame, frame_objects)
+        frame_objects, frame_masks = self.objects_masks_from_frame(sequence_name, frame_number)
+        return self.roi_generator.get_rois_features(frame, frame_objects, frame_masks if self.crop_features else None)
 
     def get_training_batch(self, sequence_idx, batch_idx):
         """(ids [N], rois [N, C, roi_size, roi_size]) of ``frames_in_batch`` consecutive frames with objects."""

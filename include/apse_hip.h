@@ -193,7 +193,8 @@ int apse_set_detections(apse_ctx* ctx, const float* boxes_host, const int* class
  * (track_rcnn.py:51,57; mask_utils.py:6-38).  Idempotent on one detection list: a repeated call (a timing loop) gives the
  * same masses / centroids, not doubled ones. */
 int apse_mask_tail(apse_ctx* ctx, int batch, void* stream);
-/* roi_pool(p2) + AssociationHead (rcnn_tracker.py:156-189, association_head.py:16-27). */
+/* roi_pool(p2) + AssociationHead (rcnn_tracker.py:156-189, association_head.py:16-27); with apse_set_crop_features on, the
+ * mask-cropped roi_align instead of roi_pool (after apse_mask_tail of the same detection list). */
 int apse_embed(apse_ctx* ctx, int batch, void* stream);
 /* RoiFeaturesGenerator.get_rois_features (dcnn/engines/roi_features_generator.py:68-117; FPN only), to be called after
  * apse_backbone: RoI features of image `image` of the batch on p2 for the association-head training batches.
@@ -202,6 +203,23 @@ int apse_embed(apse_ctx* ctx, int batch, void* stream);
  * sampling_ratio=4) (:95-111).  out_dev: f32 [n][256][roi_size][roi_size]. */
 int apse_roi_features(apse_ctx* ctx, int image, const float* rois_dev, const uint8_t* masks_dev, int n, int roi_size,
                       float* out_dev, void* stream);
+/* apse_roi_features with the masks as bit windows: windows_dev is apse_mots_window[n] on the device (the struct under "MOTS
+ * evaluation" below; frame pixels, a bit counts only inside its rect, NULL bits or an empty rect = the empty mask, the row stride
+ * may exceed what the rect needs), e.g. what apse_mots_rle_to_bits filled.  One kernel evaluates the bilinear resize of each
+ * 0 / 1 mask to p2's size from the bits and takes roi_align(aligned=False, sampling_ratio=4) of p2 * mask: no dense mask, no
+ * scratch, and out_dev is bit for bit what apse_roi_features writes for the same masks given densely.  Same checks, same lane
+ * join; windows_dev must not be NULL when n > 0. */
+struct apse_mots_window;
+int apse_roi_features_windows(apse_ctx* ctx, int image, const float* rois_dev, const struct apse_mots_window* windows_dev, int n,
+                              int roi_size, float* out_dev, void* stream);
+/* Crop features (rcnn_tracker.py:166-180, get_features_rois(crop_features=True)): context state, default 0.  With it on,
+ * apse_embed replaces roi_pool by roi_align(aligned=False, sampling_ratio=4) of p2 * mask at the detections' boxes (same
+ * assoc_scale, same assoc_roi), each detection's mask being the bit plane and rect that apse_mask_tail wrote for the same detection
+ * list, resized bilinearly to p2's padded size inside the kernel; a detection whose `valid` is 0 reads the empty mask.  The FC, the
+ * normalise and the results layout are unchanged.  apse_embed then returns APSE_E_STATE when no apse_mask_tail has run since the
+ * detections were set (apse_box_head / apse_set_detections).  APSE_E_INVALID with on != 0 under C4 (arch 1): the branch reads p2
+ * with 256 channels. */
+int apse_set_crop_features(apse_ctx* ctx, int on);
 /* backbone + rpn + box_head + mask_tail + embed. */
 int apse_forward(apse_ctx* ctx, int batch, void* stream);
 

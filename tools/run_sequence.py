@@ -146,6 +146,8 @@ def main(argv=None):
                          "RPN / box branch -- the deterministic form of configs 1-4 (SURVEY 8d)")
     ap.add_argument("--in-flight", type=int, default=1,
                     help="single process: frames in flight on separate streams (engines/pipelined_tracker.py); 1 = plain loop")
+    ap.add_argument("--crop-features", action="store_true",
+                    help="associate on mask-cropped RoI features (cfg.APSE.CROP_FEATURES): for a head trained with --crop-features")
     ap.add_argument("--input-format", default="bgr", choices=["bgr", "nv12", "i420"],
                     help="frame format handed to the tracker (cfg.INPUT.FORMAT): nv12 / i420 frames are what a video decoder gives; "
                          "here the BGR source frames are encoded on the host first (apse_uav_amd/synthetic.py)")
@@ -192,6 +194,7 @@ def main(argv=None):
     cfg.APSE.DTYPE = args.dtype
     cfg.INPUT.FORMAT = args.input_format.upper()
     cfg.APSE.YUV_MATRIX = args.yuv_matrix
+    cfg.APSE.CROP_FEATURES = bool(args.crop_features)
     n, get_frame = frame_source(args, H, W)
     from apse_uav_amd.synthetic import encoded_source
     get_frame = encoded_source(get_frame, cfg.INPUT.FORMAT, args.yuv_matrix)

@@ -55,6 +55,8 @@ def main(argv=None):
     ap.add_argument("--detector-state", default="", help="torch.load-able detector state dict")
     ap.add_argument("--association-state", default="", help="torch.load-able association head state dict")
     ap.add_argument("--metric", default="embeddings", choices=["embeddings", "mask_iou"], help="association metric")
+    ap.add_argument("--crop-features", action="store_true",
+                    help="associate on mask-cropped RoI features (cfg.APSE.CROP_FEATURES): for a head trained with --crop-features")
     ap.add_argument("--input-format", default="bgr", choices=["bgr", "nv12", "i420"],
                     help="frame format handed to the tracker (cfg.INPUT.FORMAT); nv12 / i420: the BGR frames are encoded on the "
                          "host first (apse_uav_amd/synthetic.py), as a stand-in for a video decoder's output")
@@ -88,6 +90,7 @@ def main(argv=None):
         cfg = setup_cfg()
         cfg.INPUT.FORMAT = args.input_format.upper()
         cfg.APSE.YUV_MATRIX = args.yuv_matrix
+        cfg.APSE.CROP_FEATURES = bool(args.crop_features)
         tracker = RcnnTracker(cfg, size, assoc, association_metric=args.metric, detector_state=det)
         encode = encoded_source(lambda f: f, cfg.INPUT.FORMAT, args.yuv_matrix)
         out_dir = os.path.join(args.output, seq)

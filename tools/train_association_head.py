@@ -49,6 +49,9 @@ def get_parser():
     p.add_argument('--epochs', type=int, default=NUM_EPOCH)
     p.add_argument('--cache-features', action='store_true',
                    help='keep every batch\'s RoI features on the device after epoch 1 (100 KB per object at roi 10)')
+    p.add_argument('--crop-features', action='store_true',
+                   help='train on mask-cropped RoI features: p2 * the ground-truth mask, roi_align (the tracker then needs '
+                        'cfg.APSE.CROP_FEATURES / --crop-features too)')
     p.add_argument('--synthetic', action='store_true',
                    help='write a tiny MOTS-layout dataset and seeded detector weights to a temporary directory and train on them')
     return p
@@ -78,7 +81,8 @@ def main(argv=None):
         config.INPUT.MIN_SIZE_TEST, config.INPUT.MAX_SIZE_TEST = 256, 448
 
     dataloader = MOTSloader(config=config, dataset_path=dataset_path, seqmap_path=seqmap_path,
-                            frames_in_batch=FRAMES_IN_BATCH, roi_size=ROI_SIZE, cache_features=args.cache_features)
+                            frames_in_batch=FRAMES_IN_BATCH, roi_size=ROI_SIZE, cache_features=args.cache_features,
+                            crop_features=args.crop_features)
     print('Dataset loaded with {} batches and {} sequences'.format(dataloader.num_of_batches, len(dataloader.seqmap_names)))
     print('Training for', num_epoch, 'epochs')
     training_start_time = time.time()
